@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- CompaCT encode+decode throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|4|5] [--dump-outputs DIR]
     (N > 1: launched by the driver as python -m torch.distributed.run ... bench.py --gpus N ...)
 
 Workloads (BASELINE.json `configs`):
@@ -29,11 +29,13 @@ One JSON line on stdout (rank 0): metric/value as the driver contract says, plus
 """
 import argparse
 import ctypes as C
+import functools
 import hashlib
 import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -47,6 +49,7 @@ BS = 16
 N_ROT = 3
 HBM_PEAK_GBS = 8000.0
 PIPE_SRC = os.path.join(PKG, "csrc", "encode_stream.hip")
+SYNTH_SRC = os.path.join(PKG, "cct_hip", "synth.py")
 PMC_JSON = os.path.join(ROOT, "profiles", "r03_pmc_encode.json")
 WORKLOADS = {2: (512, 256), 4: (1024, 512), 5: (512, 256)}  # config -> (edge, slices per GPU and step)
 
@@ -75,13 +78,20 @@ def _cpu_model():
     return "unknown"
 
 
+@functools.lru_cache(maxsize=None)
+def _synth_tag():
+    """Hash of the phantom generator's source: a cached phantom is only used by the generator that made it."""
+    with open(SYNTH_SRC, "rb") as f:
+        return hashlib.sha1(f.read()).hexdigest()[:12]
+
+
 def _phantom_job(args):
     """ct_phantom(seed, edge, depth12), through a cache on local disk: the driver runs N = 1, 2, 4, 8 back to back and
     rank r of a wider run needs the seeds a narrower one has already made."""
     from cct_hip.synth import ct_phantom
     seed, edge, depth12 = args
     cache = os.environ.get("CCT_PHANTOM_CACHE", os.path.join("/tmp", f"cct_phantoms_{os.getuid()}"))
-    path = os.path.join(cache, f"{edge}_{int(depth12)}_{seed}.npy") if cache != "0" else None
+    path = os.path.join(cache, f"{edge}_{int(depth12)}_{seed}_{_synth_tag()}.npy") if cache != "0" else None
     if path:
         try:
             a = np.load(path)
@@ -171,6 +181,37 @@ def pmc_traffic():
         return None, None
 
 
+DUMP_BUDGET = 64 * 10**6  # bytes of array data --dump-outputs may write
+DUMP_SEED = 20231
+
+
+def dump_sample(n, W, H, file_bound):
+    """Slices whose rasters and files are dumped in full: a seeded choice that depends on the arguments only, as many
+    (at most 8) as fit the budget next to the per-slice arrays, every file counted at its bound."""
+    per_slice = 4 * (W * H + file_bound)  # float32 raster + float32 file bytes
+    k = max(1, min(8, n, (DUMP_BUDGET - 4 * 8 * n) // per_slice))
+    return np.sort(np.random.default_rng(DUMP_SEED).permutation(n)[:k])
+
+
+def dump_outputs(out_dir, sample, rasters, archive=None, offsets=None, sizes=None, status=None):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float32 / float64: the decoded rasters (CRC-32 of
+    every slice, the sampled slices in full) and, unless the step only decodes, the encoded .cct files (size, encode
+    status and CRC-32 of every file, the sampled files' bytes back to back)."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"sample_slices": sample.astype(np.float64),
+           "decoded_crc32": np.array([zlib.crc32(r.tobytes()) for r in rasters], dtype=np.float64),
+           "decoded_sample": rasters[sample].astype(np.float32)}
+    if archive is not None:
+        files = [archive[int(offsets[j]):int(offsets[j + 1])] for j in range(len(rasters))]
+        out["encoded_sizes"] = sizes.astype(np.float64)
+        out["encode_status"] = status.astype(np.float64)
+        out["encoded_crc32"] = np.array([zlib.crc32(f.tobytes()) for f in files], dtype=np.float64)
+        out["encoded_sample"] = np.concatenate([files[j] for j in sample]).astype(np.float32)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BUDGET
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -193,12 +234,17 @@ def main():
                     help="encode batches on the device at a time (library option encode_slots; 2 is worth -8 ... +8 %% end to end depending on "
                          "the box, but then every kernel's duration includes another batch's "
                          "DEFLATE pass next to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's slices) as DIR/<name>.npy: "
+                         "decoded rasters and .cct files, a seeded sample in full and a CRC-32 of every slice; at most 64 MB")
     args = ap.parse_args()
     edge, n = WORKLOADS[args.config]
     if args.slices:
         n = args.slices
     if args.steps is None:
         args.steps = 50 if edge == 512 else 8
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     W = H = edge
     npx = n * W * H
     decode_only = args.config == 5
@@ -361,6 +407,12 @@ def main():
     for j in (0, n // 2, n - 1):
         verified &= oracle.encode(batches[last][j]) == h_arch[kset][int(h_offs[kset][j]):int(h_offs[kset][j + 1])].tobytes()
     all_sizes = state["sizes"]
+    if args.dump_outputs and rank == 0:  # now: the runs below reuse these buffer sets
+        sample = dump_sample(n, W, H, out_stride)
+        if decode_only:
+            dump_outputs(args.dump_outputs, sample, back)
+        else:
+            dump_outputs(args.dump_outputs, sample, back, h_arch[kset], h_offs[kset], h_sizes[kset], h_status[kset])
 
     # ---- the same loop with the other encode-slot setting, outside the timed region (20 steps): what the setting is worth
     other = None

@@ -162,6 +162,37 @@ def test_bench_traffic_figure_is_tied_to_the_kernel_source(tmp_path, monkeypatch
     assert bench.pmc_traffic() == (None, None)
 
 
+def test_bench_dump_outputs_fit_the_budget_and_hold_the_outputs(tmp_path):
+    """bench.py --dump-outputs: the sampled slices depend on the arguments only, every workload's dump stays within 64 MB at
+    the file bound, and the arrays written are float32 / float64 copies of the rasters and files handed over."""
+    import zlib
+    sys.path.insert(0, ROOT)
+    import bench
+    from cct_hip import _ffi
+    L = _ffi.lib()
+    for edge, n in set(bench.WORKLOADS.values()):
+        bound = L.cct_file_bound(edge, edge, 16)
+        s = bench.dump_sample(n, edge, edge, bound)
+        assert np.array_equal(s, bench.dump_sample(n, edge, edge, bound)) and len(set(s.tolist())) == len(s) >= 1
+        assert len(s) * 4 * (edge * edge + bound) + 3 * 8 * n + 8 * len(s) <= bench.DUMP_BUDGET
+    rng = np.random.default_rng(0)
+    rasters = rng.integers(0, 4096, size=(5, 16, 16)).astype(np.uint16)
+    files = [rng.integers(0, 256, size=k).astype(np.uint8).tobytes() for k in (30, 1, 77, 5, 12)]
+    offs = np.concatenate([[0], np.cumsum([len(f) for f in files])]).astype(np.uint64)
+    sizes = np.array([len(f) for f in files], np.uint32)
+    s = bench.dump_sample(5, 16, 16, 100)
+    bench.dump_outputs(str(tmp_path / "d"), s, rasters, np.frombuffer(b"".join(files), np.uint8), offs, sizes,
+                       np.zeros(5, np.uint32))
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["decoded_sample"], rasters[s]) and np.array_equal(got["encoded_sizes"], sizes)
+    assert got["encoded_sample"].astype(np.uint8).tobytes() == b"".join(files[j] for j in s)
+    assert got["encoded_crc32"].tolist() == [zlib.crc32(f) for f in files]
+    assert got["decoded_crc32"].tolist() == [zlib.crc32(r.tobytes()) for r in rasters]
+    bench.dump_outputs(str(tmp_path / "dec"), s, rasters)  # decode only: no encoded arrays
+    assert sorted(p.stem for p in (tmp_path / "dec").iterdir()) == ["decoded_crc32", "decoded_sample", "sample_slices"]
+
+
 def test_bench_workloads_and_sharding_follow_baseline_json():
     """The bench configurations are BASELINE.json's configs[1], [3], [4]; the corpus of configs[2] shards as DESIGN 8 says."""
     import json
