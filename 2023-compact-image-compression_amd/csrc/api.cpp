@@ -166,7 +166,11 @@ struct Context {
 	int stream_tpg = STREAM_TPG;  // tuning option "stream_tpg": tiles per workgroup of the streaming kernel (1, 2, 4)
 	int pipe_tpw = 0, pipe_timing = 0;  // tuning options "pipe_tpw", "pipe_timing" (then "pipe_us_k1/k2/k3" hold the last kernel times)
 	float pipe_us[4] = {0, 0, 0, 0};
-	int last_path = -1; // read-only option "last_encode_path": which stage (i) implementation the last encode used (0 generic, 1 pipeline, 2 tile kernel, 3 streaming kernel)
+	int last_path = -1; // read-only option "last_encode_path": which stage (i) implementation the last encode used (0 generic, 1 pipeline, 2 tile kernel, 3 streaming kernel,
+	                    // 4 generic kernel with a run-time block size)
+	int runtime_bs = 0;  // option "runtime_block_size": 1 sends every block size through the run-time block size kernels (encode_kernel<0>,
+	                     // decode_kernel<0>), which otherwise run the sizes that are not powers of two only; for cross-checks and measurements
+	int last_dec_path = -1;  // read-only option "last_decode_path": 0 a decode_kernel compiled for the block size, 1 the run-time block size kernel
 	int dbg_skip = 0;   // option "debug_skip": phase-ablation mask for tuning runs (outputs invalid when set)
 	int device_deflate = 1;  // option "device_deflate": 0 = DEFLATE stage on the host thread team (libz)
 	int device_inflate = 1;  // option "device_inflate": 1 = INFLATE on the device (inflate_kernels.hip, speculative lane-parallel
@@ -602,14 +606,14 @@ int get_lut(int width, int height, const int32_t **out)
 	return CCT_OK;
 }
 
-bool bs_ok(int bs) { return bs == 4 || bs == 8 || bs == 16 || bs == 32 || bs == 64; }
+bool bs_ok(int bs) { return bs >= 3 && bs <= 64; }
 
 int check_shape(int n, int width, int height, int bs)
 {
 	if (n < 0) return fail(CCT_E_ARG, "negative batch size");
 	if (width <= 0 || height <= 0 || width > 65535 || height > 65535)
 		return fail(CCT_E_ARG, "shape %dx%d outside the 16-bit header fields", width, height);
-	if (!bs_ok(bs)) return fail(CCT_E_ARG, "block_size %d not supported by the HIP path (4, 8, 16, 32, 64)", bs);
+	if (!bs_ok(bs)) return fail(CCT_E_ARG, "block_size %d not supported by the HIP path (3 to 64)", bs);
 	const int64_t N = (int64_t)width * height;
 	if (N % bs != 0) return fail(CCT_E_SHAPE, "cannot reshape array of size %lld into blocks of %d", (long long)N, bs);
 	if (N >= (int64_t)1 << 30) return fail(CCT_E_ARG, "slices of 2^30 pixels or more are not supported");
@@ -701,7 +705,7 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 	if ((rc = E.e_lcur.ensure(per))) return rc;
 	a.ws_lidx = (uint32_t *)E.e_lidx.p; a.ws_lmask = (uint64_t *)E.e_lmask.p; a.ws_lcur = (uint8_t *)E.e_lcur.p;
 	const ShapeTables *tb = nullptr;
-	if ((flags & CCT_FLAG_FRACTAL) && bs == 16 && g_ctx.use_tiles) { if ((rc = get_tables(width, height, &tb))) return rc; }
+	if ((flags & CCT_FLAG_FRACTAL) && bs == 16 && g_ctx.use_tiles && !g_ctx.runtime_bs) { if ((rc = get_tables(width, height, &tb))) return rc; }
 	// a tile-path launch sequence (memset nodes + kernels), replayed as a graph from the second call with the same arguments
 	// on: no dispatch gaps between its nodes, fewer host calls
 	auto launch_or_replay = [&](const void *args, size_t args_bytes, int tag, const std::function<hipError_t()> &launch) -> int {
@@ -805,8 +809,9 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 		g_ctx.last_path = 2;
 		return CCT_OK;
 	}
-	HIP_TRY(launch_encode(a, n, bs, g_ctx.wg_threads, st));
-	g_ctx.last_path = 0;
+	const bool run_time = bs_run_time(bs, g_ctx.runtime_bs != 0);
+	HIP_TRY(launch_encode(a, n, bs, g_ctx.wg_threads, st, run_time));
+	g_ctx.last_path = run_time ? 4 : 0;
 	return CCT_OK;
 }
 
@@ -936,7 +941,7 @@ int decode_payload_locked(DecSlot &D, const uint8_t *d_payload, size_t stride, c
 		int rc0 = get_tables(width, height, &tb);
 		if (rc0) return rc0;
 		a.lut = tb->d_lut;
-		if (tb->tiled && g_ctx.use_tiles) {
+		if (tb->tiled && g_ctx.use_tiles && !g_ctx.runtime_bs) {
 			a.tile_org = tb->d_org; a.tile_orient = tb->d_orient; a.patterns = tb->d_pat;
 			a.n_tiles = tb->n_tiles; a.n_orient = tb->n_orient;
 		}
@@ -953,7 +958,9 @@ int decode_payload_locked(DecSlot &D, const uint8_t *d_payload, size_t stride, c
 	a.pcache_steps = (int)(stride / ((size_t)g_ctx.wg_threads * DEC_SEG) + 2);
 	if ((rc = D.d_pcache.ensure((size_t)n * a.pcache_steps * g_ctx.wg_threads * sizeof(uint2)))) return rc;
 	a.ws_pcache = (uint2 *)D.d_pcache.p;
-	HIP_TRY(launch_decode(a, n, bs, g_ctx.wg_threads, st));
+	const bool run_time = bs_run_time(bs, g_ctx.runtime_bs != 0);
+	HIP_TRY(launch_decode(a, n, bs, g_ctx.wg_threads, st, run_time));
+	g_ctx.last_dec_path = run_time ? 1 : 0;
 	if (st != D.stream) {
 		// the kernel is still queued on the caller's stream when the slot is released: whatever takes the slot next runs on
 		// D.stream and must not touch d_role / d_slot / d_jord / d_pcache before this launch is through
@@ -1900,6 +1907,7 @@ int cct_set_option(const char *key, int value)
 	if (!strcmp(key, "tile_path")) { g_ctx.use_tiles = (value >= 0 && value <= 4) ? value : 1; return CCT_OK; }
 	if (!strcmp(key, "stream_tpg")) { g_ctx.stream_tpg = (value == 1 || value == 2 || value == 4) ? value : STREAM_TPG; return CCT_OK; }
 	if (!strcmp(key, "debug_skip")) { g_ctx.dbg_skip = value; return CCT_OK; }
+	if (!strcmp(key, "runtime_block_size")) { g_ctx.runtime_bs = value ? 1 : 0; return CCT_OK; }
 	if (!strcmp(key, "pipe_tpw")) { g_ctx.pipe_tpw = value; return CCT_OK; }
 	if (!strcmp(key, "pipe_timing")) { g_ctx.pipe_timing = value; return CCT_OK; }
 	if (!strcmp(key, "device_deflate")) { g_ctx.device_deflate = value ? 1 : 0; return CCT_OK; }
@@ -1928,6 +1936,8 @@ int cct_get_option(const char *key, int *value)
 	if (!strcmp(key, "tile_path")) { *value = g_ctx.use_tiles; return CCT_OK; }
 	if (!strcmp(key, "stream_tpg")) { *value = g_ctx.stream_tpg; return CCT_OK; }
 	if (!strcmp(key, "last_encode_path")) { *value = g_ctx.last_path; return CCT_OK; }
+	if (!strcmp(key, "runtime_block_size")) { *value = g_ctx.runtime_bs; return CCT_OK; }
+	if (!strcmp(key, "last_decode_path")) { *value = g_ctx.last_dec_path; return CCT_OK; }
 	if (!strncmp(key, "pipe_us_k", 9) && key[9] >= '1' && key[9] <= '4') { *value = (int)(g_ctx.pipe_us[key[9] - '1'] * 10.0f); return CCT_OK; }
 	if (!strcmp(key, "device_deflate")) { *value = g_ctx.device_deflate; return CCT_OK; }
 	if (!strcmp(key, "device_inflate")) { *value = g_ctx.device_inflate; return CCT_OK; }

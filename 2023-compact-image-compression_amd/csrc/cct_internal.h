@@ -9,10 +9,18 @@
 namespace cct {
 
 // ---- encode kernel geometry ----------------------------------------------------------
-constexpr int ENC_CH = 8192;          // pixels per chunk staged in LDS (multiple of every block size)
+constexpr int ENC_CH = 8192;          // pixels per chunk staged in LDS (a multiple of every power-of-two block size; with any other
+                                      // size a chunk is the ENC_CH / bs whole blocks that fit, CB * bs <= ENC_CH pixels)
 constexpr int ENC_RING = 4;           // chunks resident in the LDS ring (power of two)
 constexpr int ENC_LIST_CAP = 1536;    // difficult-block records kept in LDS; the rest spill to HBM
-constexpr int ENC_STG_BYTES = 2 * ENC_CH + ENC_CH / 8 + 64;  // token staging for one chunk + carry
+// Token staging for one chunk + carry: two bytes per pixel token, one jump byte per meshed pair, carry and EOF in the 64.
+// The jump term: a pair takes two blocks, so a chunk of CB = ENC_CH / bs blocks leads at most CB / 2 pairs, <= ENC_CH / 8
+// for bs >= 4.  At bs 3 (CB / 2 = 1365) only block 0 can mesh: a block is difficult when 2 * chg >= 3, so chg = 2 (of at
+// most 2 changes), its cur = chg + enter <= 3, and a candidate fits when up + 1 < cur - 2 <= 1, which no up >= 0 meets;
+// block 0 is the exception (Q4: every candidate fits), so a bs-3 slice has at most one jump byte.  (Pairs that lead from the
+// last 63 blocks of a chunk into the next one add their partners' tokens to this chunk; that slack runs into l_mask, which
+// pass 2 of encode_kernel no longer reads.)
+constexpr int ENC_STG_BYTES = 2 * ENC_CH + ENC_CH / 8 + 64;
 constexpr int ENC_MAX_LDS_ROLE = 48 * 1024;  // role[] lives in LDS when NB <= this
 
 constexpr uint8_t ROLE_PARTNER = 0xFF; // block consumed as the second half of a meshed pair
@@ -32,7 +40,10 @@ struct EncArgs {
 	uint32_t *stats;          // optional n * 4: short, full, jump tokens, difficult blocks
 	uint8_t *roles_out;       // optional n * NB: final role of every block (BLOCK_JUMPS)
 	uint32_t dbg_skip;        // tuning only (option "debug_skip"): phases to skip, results then invalid
+	int bs;                   // block size, set by launch_encode, read by encode_kernel<0> (run-time block size) only; fills the tail
+	                          // padding, so the struct keeps its size and the other kernels their argument layout
 };
+static_assert(sizeof(EncArgs) == 120, "EncArgs layout: bs must stay in the tail padding");
 
 // tile-staged fast path (block_size 16, traversal made of aligned 64x64 tiles)
 constexpr int TILE_MAX_TILES = 1024;
@@ -113,7 +124,12 @@ inline size_t stream_ws_bytes(int n, int gps) { return ((size_t)n * gps * 32 + (
 hipError_t launch_encode_stream(const StreamArgs &sa, int n, hipStream_t s);
 
 size_t enc_lds_bytes(int NB, bool *role_in_lds);
-hipError_t launch_encode(const EncArgs &a, int n, int block_size, int threads, hipStream_t s);
+// Block sizes 4, 8, 16, 32 and 64 have kernels compiled for them; every other size from 3 to 64 runs the run-time block size
+// kernels (encode_kernel<0>, decode_kernel<0>), which `force` (option "runtime_block_size") selects for every size.
+inline bool bs_run_time(int bs, bool force) { return force || (bs & (bs - 1)) != 0; }
+
+// run_time: encode_kernel<0> (launch_encode sets a.bs) even for a power of two (see bs_run_time)
+hipError_t launch_encode(const EncArgs &a, int n, int block_size, int threads, hipStream_t s, bool run_time);
 
 // ---- decode kernel geometry ----------------------------------------------------------
 constexpr int DEC_SEG = 16;           // payload bytes parsed per lane per step
@@ -131,12 +147,29 @@ struct DecArgs {
 	// traversal made of aligned 64x64 tiles (same tables as encode_tiles_kernel): position -> raster offset from LDS
 	const uint32_t *tile_org; const uint8_t *tile_orient; const uint16_t *patterns;
 	int n_tiles, n_orient, width;   // n_tiles == 0: use lut
+	uint32_t bs_mul;                // decode_kernel<0> only: ord / bs == __umulhi(ord, bs_mul) >> bs_shift (bs_divider)
 	// pass A leaves every lane's view of every parsing step here (pixel ordinal | entry state << 31, value before the
 	// segment) so that pass B does not repeat the workgroup scans: n * pcache_steps * threads entries
 	uint2 *ws_pcache; int pcache_steps;
+	uint16_t bs, bs_shift;          // decode_kernel<0> only (set by launch_decode): the block size and the shift of its divider
 };
+// bs, bs_shift and bs_mul fill padding: the struct keeps its size and the templated kernels their argument layout
+static_assert(sizeof(DecArgs) == 144, "DecArgs layout: the run-time block size fields must stay in padding");
 
-hipError_t launch_decode(const DecArgs &a, int n, int block_size, int threads, hipStream_t s);
+// Division by a run-time block size d, 3 <= d <= 64, as a multiply-high and a shift: with s = floor(log2(d - 1)) and
+// m = ceil(2^(32+s) / d) < 2^32, floor(x * m / 2^(32+s)) == floor(x / d) for every x < 2^31.  (m * d = 2^(32+s) + e with
+// 0 <= e < d <= 2^(s+1); the product overshoots x / d by x * e / (d * 2^(32+s)) < 1 / d, less than the distance of x / d to
+// the next integer.)  check_shape limits slices to 2^30 pixels.  Mirrored by tests/test_block_size_golden.py.
+inline void bs_divider(int d, uint32_t *mul, uint32_t *shift)
+{
+	uint32_t s = 0;
+	while ((2u << s) <= (uint32_t)(d - 1)) s++;
+	*shift = s;
+	*mul = (uint32_t)((((uint64_t)1 << (32 + s)) + (uint64_t)d - 1) / (uint64_t)d);
+}
+
+// run_time: decode_kernel<0> (launch_decode sets a.bs, a.bs_mul, a.bs_shift) even for a power of two (see bs_run_time)
+hipError_t launch_decode(const DecArgs &a, int n, int block_size, int threads, hipStream_t s, bool run_time);
 
 // ---- device DEFLATE (zlib 1.2.11 level 9 restatement, deflate_kernels.hip) ----------------
 struct BlockMeta {          // one DEFLATE block of a slice

@@ -209,9 +209,12 @@ __device__ __forceinline__ Parse parse_step(const uint4 &w, uint32_t nxt, int nv
 // workspace: pass B looks both up for every pixel (fits up to 24 K blocks, e.g. 512 x 512 at block size 16)
 // TILED: the traversal is made of aligned 64x64 tiles; the position -> raster map comes from the pattern tables of
 // encode_tiles_kernel staged in LDS (<= 32 KB) instead of one 4-byte HBM/L2 load per pixel.
+// BS == 0 (not TILED): the block size is a.bs (any size from 3 to 64; launch_decode picks it for the sizes that are not powers
+// of two), and a pixel ordinal is divided by it with the multiply-high and shift of bs_divider (cct_internal.h).
 template <int BS, bool TAB_LDS, bool TILED = false>
 __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 {
+	static_assert(BS != 0 || !TILED, "the tiled variant exists for block size 16 only");
 	extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
 	__shared__ uint32_t scratch[64];
 	__shared__ uint32_t l_jord[DEC_JLIST_CAP];
@@ -227,6 +230,9 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 	const uint32_t Lr = min((uint32_t)a.stride, L) > 0 ? min((uint32_t)a.stride, L) - 1u : 0u;
 	const int32_t *lut = a.lut;
 	uint16_t *out = a.images + (size_t)s * N;
+	const uint32_t bs = BS ? (uint32_t)BS : (uint32_t)a.bs;
+	auto bdiv = [&](uint32_t x) -> uint32_t { return BS ? x / (uint32_t)BS : __umulhi(x, a.bs_mul) >> a.bs_shift; };
+	auto bmod = [&](uint32_t x) -> uint32_t { return BS ? x % (uint32_t)BS : x - bdiv(x) * bs; };
 	typedef __attribute__((address_space(3))) uint8_t lds_u8;
 	typedef __attribute__((address_space(3))) uint32_t lds_u32;
 	lds_u32 *l_slot = (lds_u32 *)dyn_lds;                       // NB words
@@ -355,8 +361,8 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 			const uint32_t ord = uni(ord_n), j = uni(j_n);
 			if (k + 1 < nj) fetch(k + 1, ord_n, j_n);
 			if (ord >= (uint32_t)N) break;  // tokens past the last pixel are never read
-			if (ord % BS != 0) { bad = true; break; }
-			const uint32_t sslot = ord / BS;
+			if (bmod(ord) != 0) { bad = true; break; }
+			const uint32_t sslot = bdiv(ord);
 			if (sslot < slots_done) { bad = true; break; }
 			uint32_t remaining = sslot - slots_done;  // single blocks between the two pairs
 			while (remaining) {
@@ -448,7 +454,8 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 			const uint32_t jm = starts & sm.J;
 			if (jm & (jm << 1)) flags |= CCT_ST_STREAM;  // two jump bytes in a row
 			if (nvalid > 0 && ((fulls >> (nvalid - 1)) & 1u) && seg_start + (uint32_t)nvalid >= Lr) flags |= CCT_ST_STREAM;  // second byte missing
-			if constexpr (BS >= 16) {
+			// a wave-uniform choice for BS == 0: a lane's 16 pixels span at most two slots for every bs >= 16, for no bs < 16
+			if (BS ? BS >= 16 : bs >= 16) {
 				// A lane's <= 16 pixels fall into at most two stream slots: both slots' entry, partner and tile data are fetched
 				// before the loop.  The loop itself runs over the 16 byte positions with a compile-time index (a byte is a bit-field
 				// extract, not a select chain) and skips the positions that open no pixel token.
@@ -461,7 +468,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 					const uint32_t ent = slot_rd(min(sl, (uint32_t)NB - 1u));
 					const uint32_t blk0 = ent & 0x3FFFFFFFu; si.kind = ent >> 30;
 					const uint32_t blk1 = si.kind ? blk0 + role_rd(blk0) : blk0;
-					si.pos0 = blk0 * BS; si.pos1 = blk1 * BS;
+					si.pos0 = blk0 * bs; si.pos1 = blk1 * bs;
 					if (TILED) {
 						const uint32_t t0 = si.pos0 >> 12, t1 = si.pos1 >> 12, b0 = si.pos0 & 4095u, b1 = si.pos1 & 4095u;
 						si.org0 = l_torg[t0]; si.idx0 = (uint32_t)l_tori[t0] * PAT_STRIDE + b0 + (b0 >> 4);
@@ -469,7 +476,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 					}
 					return si;
 				};
-				const uint32_t slA = ord / BS;
+				const uint32_t slA = bdiv(ord);
 				const SlotInfo A = slot_info(slA), B = slot_info(slA + 1u);
 				DECB(1);
 				const uint32_t ws[5] = {w.x, w.y, w.z, w.w, nxt};
@@ -481,11 +488,11 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 					// (reserved tags 110xxxxx / 1111xxxx: no branch of core.py:500-516 is taken, the previous pixel repeats)
 					val += ((sm.S >> i) & 1u) ? tok_delta_short(c) : ((fulls >> i) & 1u) ? tok_delta_full(c, c1) : 0;
 					if ((uint32_t)val > 65535u) flags |= CCT_ST_OVERFLOW;  // to_bytes(2), core.py:506 (negative or too large)
-					const uint32_t sl = ord / BS, t = ord % BS;
+					const uint32_t sl = bdiv(ord), t = bmod(ord);
 					const bool inA = sl == slA;
 					const uint32_t kind = inA ? A.kind : B.kind;
 					uint32_t odd = 0, off = t;
-					if (kind) { const uint32_t mm = (kind - 1u) * BS + t; odd = mm & 1u; off = mm >> 1; }  // index inside the 2*bs interleave
+					if (kind) { const uint32_t mm = (kind - 1u) * bs + t; odd = mm & 1u; off = mm >> 1; }  // index inside the 2*bs interleave
 					uint32_t ras;
 					if (TILED) {
 						const uint32_t org = inA ? (odd ? A.org1 : A.org0) : (odd ? B.org1 : B.org0);
@@ -506,24 +513,24 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 					else if ((fulls >> i) & 1u) val += tok_delta_full(c, seg_byte(w, nxt, i + 1));
 					// (reserved tags 110xxxxx / 1111xxxx: no branch of core.py:500-516 is taken, the previous pixel repeats)
 					if (val < 0 || val > 65535) flags |= CCT_ST_OVERFLOW;  // to_bytes(2), core.py:506
-					const uint32_t sl = ord / BS, t = ord % BS;
+					const uint32_t sl = bdiv(ord), t = bmod(ord);
 					if (sl != cur_sl) {
 						cur_sl = sl;
 						const uint32_t ent = slot_rd(sl);
 						blk0 = ent & 0x3FFFFFFFu; kind = ent >> 30;
 						blk1 = kind ? blk0 + role_rd(blk0) : blk0;
 						if (TILED) {
-							const uint32_t t0 = (blk0 * BS) >> 12, t1 = (blk1 * BS) >> 12;
+							const uint32_t t0 = (blk0 * bs) >> 12, t1 = (blk1 * bs) >> 12;
 							org0 = l_torg[t0]; pat0 = (uint32_t)l_tori[t0] * PAT_STRIDE;
 							org1 = l_torg[t1]; pat1 = (uint32_t)l_tori[t1] * PAT_STRIDE;
 						}
 					}
 					uint32_t pos, odd = 0;
-					if (kind == 0) pos = blk0 * BS + t;
+					if (kind == 0) pos = blk0 * bs + t;
 					else {
-						const uint32_t mm = (kind - 1u) * BS + t;  // index inside the 2*bs interleave
+						const uint32_t mm = (kind - 1u) * bs + t;  // index inside the 2*bs interleave
 						odd = mm & 1u;
-						pos = (odd ? blk1 : blk0) * BS + (mm >> 1);
+						pos = (odd ? blk1 : blk0) * bs + (mm >> 1);
 					}
 					uint32_t ras;
 					if (TILED) {
@@ -555,19 +562,28 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 
 }  // namespace
 
-hipError_t launch_decode(const DecArgs &a, int n, int block_size, int threads, hipStream_t s)
+hipError_t launch_decode(const DecArgs &args, int n, int block_size, int threads, hipStream_t s, bool run_time)
 {
+	if (block_size < 3 || block_size > 64) return hipErrorInvalidValue;
+	run_time = bs_run_time(block_size, run_time);
+	DecArgs a = args;
+	if (run_time) {
+		uint32_t mul, shift;
+		bs_divider(block_size, &mul, &shift);
+		a.bs = (uint16_t)block_size; a.bs_mul = mul; a.bs_shift = (uint16_t)shift;
+	}
 	const size_t tab_bytes = (((size_t)a.NB * 5 + 15) & ~(size_t)15) + 16;
 	const bool tab_lds = tab_bytes <= 100 * 1024;
 	const size_t tile_bytes = (size_t)a.n_orient * (4096 + 256) * 2 + (size_t)a.n_tiles * 5 + 16;
-	const bool tiled = tab_lds && block_size == 16 && a.lut && a.n_tiles > 0 && tab_bytes + tile_bytes <= 144 * 1024 && a.width <= 1024;
+	const bool tiled = !run_time && tab_lds && block_size == 16 && a.lut && a.n_tiles > 0 && tab_bytes + tile_bytes <= 144 * 1024 && a.width <= 1024;
 	void (*k)(DecArgs) = nullptr;
-	switch (block_size) {
+	switch (run_time ? 0 : block_size) {
 	case 4: k = tab_lds ? decode_kernel<4, true> : decode_kernel<4, false>; break;
 	case 8: k = tab_lds ? decode_kernel<8, true> : decode_kernel<8, false>; break;
 	case 16: k = tiled ? decode_kernel<16, true, true> : tab_lds ? decode_kernel<16, true> : decode_kernel<16, false>; break;
 	case 32: k = tab_lds ? decode_kernel<32, true> : decode_kernel<32, false>; break;
 	case 64: k = tab_lds ? decode_kernel<64, true> : decode_kernel<64, false>; break;
+	case 0: k = tab_lds ? decode_kernel<0, true> : decode_kernel<0, false>; break;
 	default: return hipErrorInvalidValue;
 	}
 	const size_t lds = tab_lds ? tab_bytes + (tiled ? tile_bytes : 0) : 0;

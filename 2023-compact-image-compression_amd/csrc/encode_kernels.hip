@@ -74,6 +74,12 @@ struct DiffList {
 	}
 };
 
+// BS == 0: the block size is a.bs (any size from 3 to 64; launch_encode picks it for the sizes that are not powers of two).
+// A chunk is then the CB = ENC_CH / bs whole blocks that fit, CHP = CB * bs <= ENC_CH pixels: four chunks still fit the ring
+// without overlap, and the 63-block look-ahead of a difficult block (<= 4032 pixels < CHP) still lies in its chunk and the next.
+// (The per-block loops are unrolled for the compiled sizes; with a run-time count the compiler leaves them rolled and says so.)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"
 template <int BS>
 __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 {
@@ -98,19 +104,29 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 	DiffList dl{l_idx, l_cur, l_mask,
 	            a.ws_lidx + (size_t)s * NB, a.ws_lcur + (size_t)s * NB, a.ws_lmask + (size_t)s * NB};
 
-	constexpr int CB = ENC_CH / BS;  // blocks per chunk
-	const int nch = (N + ENC_CH - 1) / ENC_CH;
+	const int bs = BS ? BS : a.bs;
+	const int CB = ENC_CH / bs;  // blocks per chunk
+	const int CHP = CB * bs;     // pixels per chunk (ENC_CH for a power of two)
+	const int nch = (N + CHP - 1) / CHP;
 
 	if (tid == 0) { scratch[32] = 0; scratch[33] = 0; scratch[34] = 0; }
 
 	auto fill = [&](int c) {
-		const int k0 = c * ENC_CH;
-		const int npx = min(ENC_CH, N - k0);
-		uint16_t *dst = ring + (k0 & (RING_PX - 1));
-		if (lut) {
-			for (int k = tid; k < npx; k += T) dst[k] = img[lut[k0 + k]];
-		} else {
-			for (int k = tid; k < npx; k += T) dst[k] = img[k0 + k];
+		const int k0 = c * CHP;
+		const int npx = min(CHP, N - k0);
+		if (BS) {
+			uint16_t *dst = ring + (k0 & (RING_PX - 1));
+			if (lut) {
+				for (int k = tid; k < npx; k += T) dst[k] = img[lut[k0 + k]];
+			} else {
+				for (int k = tid; k < npx; k += T) dst[k] = img[k0 + k];
+			}
+		} else {  // CHP does not divide RING_PX: a chunk may wrap round the end of the ring
+			if (lut) {
+				for (int k = tid; k < npx; k += T) ring[(k0 + k) & (RING_PX - 1)] = img[lut[k0 + k]];
+			} else {
+				for (int k = tid; k < npx; k += T) ring[(k0 + k) & (RING_PX - 1)] = img[k0 + k];
+			}
 		}
 	};
 	auto D = [&](int k) -> int { return (int)ring[k & (RING_PX - 1)]; };
@@ -136,17 +152,17 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 					const int b = c * CB + bl;
 					uint32_t diff = 0, cur = 0;
 					if (act) {
-						const int k0 = b * BS;
+						const int k0 = b * bs;
 						int prev = Dseg(k0);
 						uint32_t chg = 0;
 #pragma unroll
-						for (int t = 1; t < BS; t++) {
+						for (int t = 1; t < bs; t++) {
 							const int v = Dseg(k0 + t);
 							const int d = v - prev;
 							chg += (d > 64 || d < -64) ? 1u : 0u;  // |d| > 64, cluster.py:38-39
 							prev = v;
 						}
-						if (2 * chg >= (uint32_t)BS) {  // cluster.py:58
+						if (2 * chg >= (uint32_t)bs) {  // cluster.py:58 (changes >= block_size / 2, odd sizes included)
 							diff = 1;
 							uint32_t enter = 0;
 							if (k0 > 0) {
@@ -171,11 +187,11 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 				const int p = i + lane;
 				bool fit = false;
 				if (lane >= 1 && p < NB) {
-					const int ka = i * BS, kb = p * BS;
+					const int ka = i * bs, kb = p * bs;
 					uint32_t up = 0;
 					int bprev = 0;
 #pragma unroll
-					for (int t = 0; t < BS; t++) {
+					for (int t = 0; t < bs; t++) {
 						const int av = Dseg(ka + t), bv = Dseg(kb + t);
 						if (t > 0) up += (av - bprev >= 65) ? 1u : 0u;  // A[t] - B[t-1]
 						up += (bv - av >= 65) ? 1u : 0u;               // B[t] - A[t]
@@ -250,14 +266,14 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 						int rq = seg ? (int)role[q] : 0;
 						while (rq == ROLE_PARTNER) { q--; rq = (int)role[q]; }
 						const int src = q + rq;  // rq = 0 for a single
-						pv = D(src * BS + BS - 1);
+						pv = D(src * bs + bs - 1);
 					}
-					const int ka = b * BS;
+					const int ka = b * bs;
 					int prev = pv;
 					uint32_t n2 = 0;
 					if (r == 0) {
 #pragma unroll
-						for (int t = 0; t < BS; t++) {
+						for (int t = 0; t < bs; t++) {
 							const int v = D(ka + t);
 							const int d = v - prev;
 							const bool two = (d < -63 || d > 64);  // core.py:316
@@ -265,12 +281,12 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 							q7 |= (d < -2047 || d > 2048);
 							prev = v;
 						}
-						nbytes = BS + n2;
+						nbytes = bs + n2;
 						my_full += n2;
 					} else {
-						const int kb = (b + r) * BS;
+						const int kb = (b + r) * bs;
 #pragma unroll
-						for (int t = 0; t < BS; t++) {
+						for (int t = 0; t < bs; t++) {
 							const int va = D(ka + t), vb = D(kb + t);
 							const int d1 = va - prev, d2 = vb - va;
 							n2 += (d1 < -63 || d1 > 64) ? 1u : 0u;
@@ -278,7 +294,7 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 							q7 |= (d1 < -2047 || d1 > 2048) || (d2 < -2047 || d2 > 2048);
 							prev = vb;
 						}
-						nbytes = 2 * BS + n2 + 1;
+						nbytes = 2 * bs + n2 + 1;
 						my_full += n2;
 						my_jump += 1;
 					}
@@ -289,7 +305,7 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 			const uint32_t off = wg_excl_scan(nbytes, scratch, tot);
 			if (nbytes) {
 				uint8_t *w = stg + carry + chunk_bytes + off;
-				const int ka = b * BS;
+				const int ka = b * bs;
 				int prev = pv;
 				auto put = [&](int d) {
 					if (d < -63 || d > 64) {  // full delta, core.py:322-323
@@ -301,16 +317,16 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 				};
 				if (r == 0) {
 #pragma unroll
-					for (int t = 0; t < BS; t++) {
+					for (int t = 0; t < bs; t++) {
 						const int v = D(ka + t);
 						put(v - prev);
 						prev = v;
 					}
 				} else {
 					*w++ = (uint8_t)(0x80 | r);  // jump tag, core.py:290-294
-					const int kb = (b + r) * BS;
+					const int kb = (b + r) * bs;
 #pragma unroll
-					for (int t = 0; t < BS; t++) {
+					for (int t = 0; t < bs; t++) {
 						const int va = D(ka + t), vb = D(kb + t);
 						put(va - prev);
 						put(vb - va);
@@ -362,6 +378,8 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 	}
 }
 
+#pragma clang diagnostic pop
+
 }  // namespace
 
 size_t enc_lds_bytes(int NB, bool *role_in_lds)
@@ -373,18 +391,21 @@ size_t enc_lds_bytes(int NB, bool *role_in_lds)
 	return base;
 }
 
-hipError_t launch_encode(const EncArgs &a, int n, int block_size, int threads, hipStream_t s)
+hipError_t launch_encode(const EncArgs &args, int n, int block_size, int threads, hipStream_t s, bool run_time)
 {
+	if (block_size < 3 || block_size > 64) return hipErrorInvalidValue;
+	EncArgs a = args;
+	a.bs = block_size;
 	bool in_lds;
 	const size_t lds = enc_lds_bytes(a.NB, &in_lds);
 	void (*k)(EncArgs) = nullptr;
-	switch (block_size) {
+	switch (bs_run_time(block_size, run_time) ? 0 : block_size) {
 	case 4: k = encode_kernel<4>; break;
 	case 8: k = encode_kernel<8>; break;
 	case 16: k = encode_kernel<16>; break;
 	case 32: k = encode_kernel<32>; break;
 	case 64: k = encode_kernel<64>; break;
-	default: return hipErrorInvalidValue;
+	default: k = encode_kernel<0>; break;
 	}
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
 	                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

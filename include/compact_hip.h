@@ -59,7 +59,7 @@ extern "C" {
 #define CCT_E_CAP 6       /* caller buffer too small */
 #define CCT_E_NOMEM 7
 #define CCT_E_DEVICE 8    /* no usable gfx950 device / HIP runtime error */
-#define CCT_E_ARG 9       /* unsupported argument (block_size not in {4,8,16,32,64}, n<0, ...) */
+#define CCT_E_ARG 9       /* unsupported argument (block_size outside 3..64, n<0, ...) */
 #define CCT_E_MIXED 10    /* decode batch whose members differ in shape or flags */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
