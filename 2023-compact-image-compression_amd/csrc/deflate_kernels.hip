@@ -1086,8 +1086,8 @@ __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 
 // ------------------------------------------------------------------ 4. Huffman trees per block (trees.c)
 // One WAVE per (slice, block).  trees.c's heap decides ties by heap position, so the heap itself is replayed
-// by lane 0; everything around it (histogram, leaf list, bit-length statistics, code assignment) is done by
-// all 64 lanes, and the tables the serial parts index are staged in LDS (a __constant__ lookup with a
+// (with its sifts overlapped, one lane each: tree_heap); everything around it (histogram, leaf list, bit-length
+// statistics, code assignment) is done by all 64 lanes, and the tables the serial parts index are staged in LDS (a __constant__ lookup with a
 // per-lane index is a global load: ~10x the latency of an LDS read when nothing hides it).
 // The working set decides how many blocks a CU works on at once (the serial heap replay is pure LDS latency, so
 // resident waves are what hides it): 7.3 KB lets 13 waves share the ~96 KB a CU hands out, which is one wave for every
@@ -1101,7 +1101,7 @@ struct TreeScratch {  // one block's working set, in LDS
 	// heap entries carry their own sort key: freq << 15 | depth << 10 | node, so that trees.c's smaller(n, m)
 	// is (e_n >> 10) <= (e_m >> 10) and one 64-bit LDS read fetches both children (freq <= 16384: 15 bits;
 	// depth <= 21 for that total weight: 5 bits; node < 573: 10 bits)
-	alignas(16) uint32_t heap[HEAP_SIZE + 3];
+	alignas(16) uint32_t heap[HEAP_SIZE + 11];  // + a sink slot for each lane of the heap replay (tree_heap)
 	uint32_t bl_count[MAX_BITS + 1];
 	uint16_t next_code[MAX_BITS + 1];
 	int heap_len, heap_max, max_code, overflow, lmax, dmax;
@@ -1132,91 +1132,24 @@ __device__ __forceinline__ uint32_t static_llen(int n) { return n <= 143 ? 8u : 
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 struct TreeView { lds_u16 *freq, *dad, *len, *code; };
 
-// trees.c pqdownheap.  Every level is an LDS round trip on the critical path of the tree kernel, so two levels are
-// fetched at once: the pair of children and, below them, the four grandchildren (contiguous, 16-byte aligned).
-// The replay runs on one lane, but nothing in it differs between lanes: every loaded value is passed through
-// v_readfirstlane so that the compiler keeps the state in SGPRs and branches with s_cbranch instead of juggling the
-// exec mask around every `if` (that overhead, not the LDS latency, was most of the cost of a level).
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+// trees.c pqdownheap(k) on the lane's own node: the level-parallel heapify runs one per lane (disjoint subtrees)
 __device__ __forceinline__ void pqdownheap(TreeScratch &S, int k, int hl)
 {
-	const uint32_t v = uni(S.heap[k]);
-	const uint32_t vk = v >> 10;
-	int j = k << 1;
-	while (j <= hl) {
-		uint2 pr = *reinterpret_cast<const uint2 *>(&S.heap[j]);  // j is even: children j, j+1 in one read
-		uint4 gc = *reinterpret_cast<const uint4 *>(&S.heap[min(2 * j, (HEAP_SIZE & ~3))]);  // only used when 2j <= hl
-		pr.x = uni(pr.x); pr.y = uni(pr.y);
-		gc.x = uni(gc.x); gc.y = uni(gc.y); gc.z = uni(gc.z); gc.w = uni(gc.w);
-		uint32_t e = pr.x;
-		int c = j;
-		if (j < hl && (pr.y >> 10) <= (pr.x >> 10)) { c = j + 1; e = pr.y; }
-		if (vk <= (e >> 10)) break;
+	// smaller(a, b) of trees.c is (a >> 10) <= (b >> 10) on these entries, i.e. a <= (b | 1023): one OR instead of two shifts
+	const uint32_t v = S.heap[k];
+	for (int j = k << 1; j <= hl; j = k << 1) {
+		const uint2 pr = *reinterpret_cast<const uint2 *>(&S.heap[j]);  // j is even: children j, j+1 in one read
+		const int right = (j < hl && pr.y <= (pr.x | 1023u)) ? 1 : 0;
+		const uint32_t e = right ? pr.y : pr.x;
+		if (v <= (e | 1023u)) break;
 		S.heap[k] = e;
-		k = c;
-		j = c << 1;
-		if (j > hl) break;
-		const bool left = (c & 1) == 0;
-		const uint32_t x2 = left ? gc.x : gc.z, y2 = left ? gc.y : gc.w;
-		e = x2;
-		c = j;
-		if (j < hl && (y2 >> 10) <= (x2 >> 10)) { c = j + 1; e = y2; }
-		if (vk <= (e >> 10)) break;
-		S.heap[k] = e;
-		k = c;
-		j = c << 1;
+		k = j + right;
 	}
 	S.heap[k] = v;
 }
 
-// pqdownheap(1) for a value the caller holds in a register: heap[1] is a hole, v sinks from there.  Returns what ends up
-// at heap[1], so that the caller never reads the root back.
-// All blocks of a batch replay their heaps at the same time, 13 waves to a CU, and what they compete for is instruction
-// issue: a CU has ONE scalar unit, and lane-masked control flow (every `if`, every early exit) is mostly scalar
-// instructions.  So this runs a fixed number of levels without a branch: once v has found its place the remaining
-// levels still execute, reading harmlessly and storing to the unused heap[0].
-__device__ __forceinline__ uint32_t sift_root(TreeScratch &S, uint32_t v, int hl, int levels)
-{
-	// smaller(a, b) of trees.c is (a >> 10) <= (b >> 10) on these entries, i.e. a <= (b | 1023): one OR instead of two shifts
-	if (levels == 0) { S.heap[1] = v; return v; }  // (uniform) a heap of one entry
-	// first level, hole at the root: what lands there is the value to return
-	const uint2 p0 = *reinterpret_cast<const uint2 *>(&S.heap[2]);
-	uint32_t right = (2 < hl && p0.y <= (p0.x | 1023u)) ? 1u : 0u;
-	uint32_t e = right ? p0.y : p0.x;
-	uint32_t moving = v > (e | 1023u) ? 1u : 0u;  // hl >= 2 here
-	const uint32_t rootv = moving ? e : v;
-	S.heap[1] = rootv;
-	uint32_t k = 2u + right;
-	// levels 1 .. levels-2: k lies above the last full level (depth < levels - 1), so both children exist (2k + 1 < 2^levels <= hl)
-	// and nothing needs a bound -- a third fewer instructions per level than the general step below, and these are most levels
-	for (int l = 1; l < levels - 1; l++) {
-		const uint32_t j = k << 1;
-		const uint2 pr = *reinterpret_cast<const uint2 *>(&S.heap[j]);
-		right = pr.y <= (pr.x | 1023u) ? 1u : 0u;
-		e = right ? pr.y : pr.x;
-		const uint32_t go = (moving && v > (e | 1023u)) ? 1u : 0u;
-		S.heap[moving ? k : 0u] = go ? e : v;  // the hole at k receives the smaller child, or v (which then stays there)
-		k = go ? j + right : k;
-		moving = go;
-	}
-	if (levels >= 2) {  // (uniform) the last level: children may lie past the end of the heap
-		const uint32_t j = k << 1;
-		const uint2 pr = *reinterpret_cast<const uint2 *>(&S.heap[min(j, (uint32_t)(HEAP_SIZE - 1))]);
-		right = (j < (uint32_t)hl && pr.y <= (pr.x | 1023u)) ? 1u : 0u;
-		e = right ? pr.y : pr.x;
-		const uint32_t go = (moving && j <= (uint32_t)hl && v > (e | 1023u)) ? 1u : 0u;
-		S.heap[moving ? k : 0u] = go ? e : v;
-		k = go ? j + right : k;
-		moving = go;
-	}
-	S.heap[moving ? k : 0u] = v;
-	return rootv;
-}
-
-
-// build_tree + gen_bitlen + gen_codes (trees.c:486-700) in five phases.  The heap replay and the overflow repair are
-// serial (one lane per block: dfl_tree_kernel runs them for several blocks at once, one block per lane); the phases
-// around them use all 64 lanes on one block at a time.
+// build_tree + gen_bitlen + gen_codes (trees.c:486-700) in five phases.  The overflow repair is serial (one lane per
+// block); the heap replay runs a few sifts side by side, and the phases around them use all 64 lanes on one block at a time.
 // kind: 0 literal/length, 1 distance, 2 bit-length
 __device__ __forceinline__ TreeView view_of(TreeScratch &S, int kind)
 {
@@ -1246,41 +1179,100 @@ __device__ void tree_leaves(TreeScratch &S, int kind)
 	if (lane == 0) { S.heap_len = (int)nleaf; S.max_code = max_code; }
 }
 
-// (one lane) the heap replay proper (trees.c:625-668)
+// (whole wave) the heap replay proper (trees.c:625-668), exact to the heap position, so that ties are decided as zlib does.
+// A sift is a chain of dependent LDS round trips, one per heap level; the replay overlaps them instead of running them in
+// a row (tools/tree_schedule_model.cpp models this schedule and checks it against trees.c):
+//  - heapify: trees.c sifts every node of a depth before any node above it, and the nodes of one depth have disjoint
+//    subtrees, so one round per depth sifts all of them at once, one lane each;
+//  - main loop: the sifts A (pqremove: heap[h] sinks from the root) and B (the new node sinks from the root) depend on each
+//    other only at the root.  So they run one lane each, TREE_SIFTS lanes round robin, every sift one level per tick, and a
+//    new one starts every other tick at the earliest (a tick reads the child pairs, then writes the holes: a sift two
+//    levels behind the one ahead reads only what that one has written).  B needs the root left by A's first level, the next
+//    A the root left by B's first level.  A also takes the last slot h: it waits while h lies in the subtree of a moving
+//    sift's hole.  Then no sift in flight ever touches h again, and its bound check agrees with the sequential one.
+constexpr int TREE_SIFTS = 8;  // at most 5 in flight: one starts every other tick, none lasts more than 9 ticks
 __device__ void tree_heap(TreeScratch &S, int kind)
 {
 	const TreeView t = view_of(S, kind);
-	int n, m, node, max_code = (int)uni((uint32_t)S.max_code);
-	int heap_len = (int)uni((uint32_t)S.heap_len), heap_max = HEAP_SIZE;  // in registers: every LDS access of this loop is on the critical path
-	while (heap_len < 2) {
-		node = max_code < 2 ? ++max_code : 0;
-		t.freq[node] = 1; S.opt_len--;
-		S.heap[++heap_len] = (1u << 15) | (uint32_t)node;
-		if (kind == 0) S.static_len -= static_llen(node);
-		else if (kind == 1) S.static_len -= 5;
+	const int lane = threadIdx.x;
+	int max_code = S.max_code, h = S.heap_len;
+	while (h < 2) {  // (uniform) at least two codes, trees.c:612-621
+		const int node = max_code < 2 ? ++max_code : 0;
+		h++;
+		if (lane == 0) {
+			t.freq[node] = 1; S.opt_len--;
+			S.heap[h] = (1u << 15) | (uint32_t)node;
+			if (kind == 0) S.static_len -= static_llen(node);
+			else if (kind == 1) S.static_len -= 5;
+		}
 	}
-	for (n = heap_len / 2; n >= 1; n--) pqdownheap(S, n, heap_len);
-	node = elems_of(kind);
-	uint32_t top = S.heap[1];
-	do {
-		const uint32_t en = top;
-		const uint32_t lastv = S.heap[heap_len];
-		heap_len--;
-		const int levels = 31 - __clz(heap_len | 1);  // levels below the root: floor(log2(heap_len))
-		const uint32_t em = sift_root(S, lastv, heap_len, levels);
-		n = (int)(en & 1023u); m = (int)(em & 1023u);
-		S.heap[--heap_max] = en; S.heap[--heap_max] = em;
-		const uint32_t f = (en >> 15) + (em >> 15);
-		const uint32_t dn = (en >> 10) & 31u, dm = (em >> 10) & 31u;
-		const uint32_t d = (dn >= dm ? dn : dm) + 1;
-		t.freq[node] = (uint16_t)f;
-		t.dad[n] = t.dad[m] = (uint16_t)node;
-		top = sift_root(S, (f << 15) | (d << 10) | (uint32_t)node, heap_len, levels);
-		node++;
-	} while (heap_len >= 2);
-	S.heap[--heap_max] = top;
-	S.heap_len = heap_len; S.heap_max = heap_max;
-	S.max_code = max_code;
+	__syncthreads();
+	for (int d = 31 - __clz(h >> 1); d >= 0; d--) {  // heapify, deepest inner level first
+		const int lo = 1 << d, hi = min((2 << d) - 1, h >> 1);
+		for (int n0 = lo; n0 <= hi; n0 += 64) {
+			if (n0 + lane <= hi) pqdownheap(S, n0 + lane, h);
+			__builtin_amdgcn_wave_barrier();  // one wave: LDS order is program order; keep the compiler to it as well
+		}
+	}
+	if (lane < TREE_SIFTS) {
+		// the lane's sift: value v, hole k, heap length hl.  A lane whose sift is over keeps reading below its last hole
+		// (harmless) and writes to a slot of its own past the heap: the step has no branch
+		uint32_t v = 0, k = 1, hl = 0, w = 0;
+		bool moving = false;
+		const uint32_t sink = HEAP_SIZE + 3 + lane;
+		auto tick = [&]() {  // one level of every sift in flight: read the child pair, then write the hole
+			const uint32_t j = k << 1;  // <= 2 * 286: the pair lies inside heap[]
+			const uint2 pr = *reinterpret_cast<const uint2 *>(&S.heap[j]);
+			const uint32_t right = (j < hl && pr.y <= (pr.x | 1023u)) ? 1u : 0u;
+			const uint32_t e = right ? pr.y : pr.x;
+			const bool go = moving && j <= hl && v > (e | 1023u);
+			w = go ? e : v;  // the hole at k receives the smaller child, or v (which then stays there)
+			uint32_t at = moving ? k : sink;
+			asm volatile("" : "+v"(at), "+v"(w));  // both as selects: left alone, the compiler splits the store into two branches
+			S.heap[at] = w;
+			k = go ? j + right : k;
+			moving = go;
+			__builtin_amdgcn_wave_barrier();  // one wave: LDS order is program order; keep the compiler to it as well
+		};
+		auto start = [&](int slot, uint32_t x) {
+			const bool me = lane == slot;
+			v = me ? x : v; k = me ? 1u : k; hl = me ? (uint32_t)h : hl; moving = moving || me;
+		};
+		int node = elems_of(kind), hm = HEAP_SIZE, slot = 0;
+		uint32_t en = S.heap[1];  // the root the next A removes
+		for (;;) {  // one iteration of trees.c's loop: A, an idle tick, B, an idle tick
+			// A takes the last slot h: not while h lies in the subtree of a moving sift's hole
+			while (__ballot(moving && ((uint32_t)h >> (__clz(k | 1u) - __clz(h))) == k)) tick();
+			h--;
+			start(slot, S.heap[h + 1]);
+			tick();
+			const uint32_t em = (uint32_t)__builtin_amdgcn_readlane((int)w, slot);  // A has left em at the root
+			const uint32_t f = (en >> 15) + (em >> 15);
+			const uint32_t dn = (en >> 10) & 31u, dm = (em >> 10) & 31u;
+			const uint32_t d = (dn >= dm ? dn : dm) + 1;
+			if (lane == 0) {
+				S.heap[hm - 1] = en; S.heap[hm - 2] = em;
+				t.freq[node] = (uint16_t)f;
+				t.dad[en & 1023u] = t.dad[em & 1023u] = (uint16_t)node;
+			}
+			hm -= 2;
+			slot = (slot + 1) & (TREE_SIFTS - 1);
+			tick();
+			start(slot, (f << 15) | (d << 10) | (uint32_t)node);  // B: the new node
+			tick();
+			en = (uint32_t)__builtin_amdgcn_readlane((int)w, slot);
+			slot = (slot + 1) & (TREE_SIFTS - 1);
+			node++;
+			if (h < 2) break;
+			tick();
+		}
+		while (__ballot(moving)) tick();
+		if (lane == 0) {
+			S.heap[--hm] = en;
+			S.heap_len = h; S.heap_max = hm;
+			S.max_code = max_code;
+		}
+	}
 }
 
 // (whole wave) gen_bitlen's first loop and its statistics
@@ -1519,9 +1511,8 @@ __device__ void send_header(TreeScratch &S)
 }
 
 // One wave per TREE_BLOCKS consecutive blocks of a slice: histograms + trees (trees.c _tr_flush_block).  The serial
-// parts of a block (heap replay, run-length scan of the code lengths, header bits) keep one lane busy and cost the wave a
-// full instruction stream each; with four blocks per wave, lanes 0..3 run them side by side and the instruction count per
-// block drops accordingly.  The parallel parts take the blocks in turn.
+// parts of a block (overflow repair, block type) run on lane q for block m0 + q; the heap replay and the parallel parts
+// take the blocks in turn.
 constexpr int TREE_BLOCKS = 1;
 __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 {
@@ -1636,7 +1627,7 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		for (int q = 0; q < nb; q++) tree_leaves(S4[q], kind);
 		__syncthreads();
 		TREE_STAMP();
-		if (owner) tree_heap(S4[lane], kind);
+		for (int q = 0; q < nb; q++) tree_heap(S4[q], kind);
 		__syncthreads();
 		TREE_STAMP();
 		for (int q = 0; q < nb; q++) tree_depths(S4[q], kind);
