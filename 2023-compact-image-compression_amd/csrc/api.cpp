@@ -49,15 +49,13 @@ struct ShapeTables {  // everything that depends on (width, height) only; lives 
 	uint32_t *d_org = nullptr;
 	uint8_t *d_orient = nullptr;
 	uint16_t *d_pat = nullptr;
-	// staged pipeline (encode_pipe.hip): every tile is a 16x16 grid of 4x4-pixel traversal blocks
-	bool pipe = false;
+	// streaming kernel (encode_stream.hip): every tile is a 16x16 grid of 4x4-pixel traversal blocks
+	bool stream = false;
 	uint32_t *d_ptab = nullptr;       // n_orient * 128 * 4
-	uint32_t *d_ptab2 = nullptr;      // n_orient * 2 * 64 * 4
-	uint32_t *d_btab = nullptr;       // n_orient * 256
 	uint32_t *d_otab = nullptr;       // 4 * 16
 	uint32_t *d_ttab = nullptr;       // 16 * 4
-	uint32_t *d_htab = nullptr;       // n_orient * 32 * 2 (encode_stream.hip: the look-ahead quadrant of a tile)
-	PipeTiles tiles;                  // host copy: travels in the kernel arguments
+	uint32_t *d_htab = nullptr;       // n_orient * 32 * 2: the look-ahead quadrant of a tile
+	StreamTiles tiles;                // host copy: travels in the kernel arguments
 };
 
 // Everything one encode batch in flight owns: stream, workspaces, the captured DEFLATE graph.  There are two of them.
@@ -72,10 +70,6 @@ struct EncSlot {
 	struct ZGraph { std::vector<uint8_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; uint64_t last_use = 0; };
 	std::vector<ZGraph> z_graphs;  // a batch deflated in several passes has one argument set per pass (round 2 kept ONE graph and
 	uint64_t z_clock = 0;          // captured it again for every pass of such a batch: 5 ms per step at 512 x 1024^2)
-	// the memset + four launches of the transform+pack pipeline, likewise (a few argument sets: callers rotate batches)
-	struct PipeGraph { std::vector<uint8_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; uint64_t last_use = 0; };
-	std::vector<PipeGraph> p_graphs;
-	uint64_t p_clock = 0;
 	// packed archives leave the device on their own stream from one of two buffers, after the slot has been
 	// released: the next encode call may start its kernels while this one's files are still on the wire
 	hipStream_t stream_copy = nullptr;
@@ -84,8 +78,7 @@ struct EncSlot {
 	unsigned pack_slot = 0;
 	// encode workspaces
 	DevBuf e_role, e_lidx, e_lmask, e_lcur, e_images, e_payload, e_sizes, e_status, e_stats;
-	DevBuf e_toff, e_pairrec, e_spill, e_tflag;  // staged pipeline: tile offsets, meshed-pair records, difficult-list spill
-	DevBuf e_hand;                               // streaming kernel: hand-off words and tickets
+	DevBuf e_pairrec, e_hand;  // streaming kernel: meshed-pair records, hand-off words and tickets
 	DevBuf h_stage;  // pinned host staging (payloads)
 	DevBuf h_small[2];  // pinned landing place of a call's sizes / status / statistics (a copy to pageable memory blocks the host until it has happened)
 	// device DEFLATE workspaces
@@ -108,8 +101,8 @@ struct EncSlot {
 	int n_bufs = 0;
 	EncSlot()
 	{
-		DevBuf *b[] = {&e_role, &e_lidx, &e_lmask, &e_lcur, &e_images, &e_payload, &e_sizes, &e_status, &e_stats, &e_toff, &e_pairrec,
-		               &e_spill, &e_tflag, &e_hand, &h_stage, &z_vals_in, &z_vals_out, &z_mr, &z_rec, &z_exitp, &z_exitc,
+		DevBuf *b[] = {&e_role, &e_lidx, &e_lmask, &e_lcur, &e_images, &e_payload, &e_sizes, &e_status, &e_stats, &e_pairrec,
+		               &e_hand, &h_stage, &z_vals_in, &z_vals_out, &z_mr, &z_rec, &z_exitp, &z_exitc,
 		               &z_sym, &z_bentry, &z_bsym, &z_small, &z_bend, &z_meta, &z_tables, &z_sorttmp, &z_out, &z_outsizes, &z_in,
 		               &z_insizes, &z_packed, &z_packoffs, &z_packed2[0], &z_packed2[1], &z_gen, &z_runs, &h_small[0], &h_small[1]};
 		for (DevBuf *p : b) all_bufs[n_bufs++] = p;
@@ -161,13 +154,11 @@ struct Context {
 	hipStream_t stream_dec = nullptr;  // decode runs on its own stream so it can overlap an encode in flight
 	std::map<std::pair<int, int>, ShapeTables> luts;  // (width,height) -> device tables
 	int use_tiles = 1;  // option "tile_path": 1 default choice among the tile paths (the streaming kernel wherever it applies), 4 the
-	                    // streaming kernel (encode_stream.hip), 3 the four-kernel pipeline (encode_pipe.hip), 2 the
-	                    // one-workgroup-per-slice tile kernel, 0 the generic LUT-gather kernel
+	                    // streaming kernel (encode_stream.hip), 2 the one-workgroup-per-slice tile kernel, 0 the generic LUT-gather
+	                    // kernel (3, the four-kernel pipeline of round 2, is removed and refused)
 	int stream_tpg = STREAM_TPG;  // tuning option "stream_tpg": tiles per workgroup of the streaming kernel (1, 2, 4)
-	int pipe_tpw = 0, pipe_timing = 0;  // tuning options "pipe_tpw", "pipe_timing" (then "pipe_us_k1/k2/k3" hold the last kernel times)
-	float pipe_us[4] = {0, 0, 0, 0};
-	int last_path = -1; // read-only option "last_encode_path": which stage (i) implementation the last encode used (0 generic, 1 pipeline, 2 tile kernel, 3 streaming kernel,
-	                    // 4 generic kernel with a run-time block size)
+	int last_path = -1; // read-only option "last_encode_path": which stage (i) implementation the last encode used (0 generic, 2 tile kernel, 3 streaming kernel,
+	                    // 4 generic kernel with a run-time block size; 1, the removed pipeline, is not reused)
 	int runtime_bs = 0;  // option "runtime_block_size": 1 sends every block size through the run-time block size kernels (encode_kernel<0>,
 	                     // decode_kernel<0>), which otherwise run the sizes that are not powers of two only; for cross-checks and measurements
 	int last_dec_path = -1;  // read-only option "last_decode_path": 0 a decode_kernel compiled for the block size, 1 the run-time block size kernel
@@ -334,18 +325,18 @@ bool forked_after_init() { return g_ctx.ready && g_ctx.pid != getpid(); }
 
 namespace {
 
-// Tables of the staged pipeline.  Inside every 64x64 tile the traversal must walk aligned 4x4-pixel blocks (16
+// Tables of the streaming kernel.  Inside every 64x64 tile the traversal must walk aligned 4x4-pixel blocks (16
 // positions each), and every block must be walked quadrant by quadrant (2x2 pixels, 4 positions each) with quarter 0
 // = top-left or bottom-right quadrant, quarter 2 = the other one, quarter 1 = bottom-left or top-right, quarter 3 = the
 // other one.  The generalized Hilbert curve on power-of-two squares does; anything else keeps the older kernels.
-void build_pipe_tables(const std::vector<int32_t> &O, int width, const std::vector<uint32_t> &org,
-                       const std::vector<uint8_t> &orient, ShapeTables &t)
+void build_stream_tables(const std::vector<int32_t> &O, int width, const std::vector<uint32_t> &org,
+                         const std::vector<uint8_t> &orient, ShapeTables &t)
 {
-	t.pipe = false;
+	t.stream = false;
 	const int nt = (int)org.size();
 	const int no = t.n_orient;
 	std::vector<uint16_t> rtab((size_t)no * 256, 0xFFFF);
-	std::vector<uint32_t> tile_last(no, 0), tile_mid(no, 0);
+	std::vector<uint32_t> tile_last(no, 0);
 	std::vector<std::vector<int>> bpat;  // block orientations: raster index (row*4+col) of the 16 positions
 	for (int ti = 0; ti < nt; ti++) {
 		const int32_t *k = O.data() + (size_t)ti * 4096;
@@ -371,11 +362,10 @@ void build_pipe_tables(const std::vector<int32_t> &O, int width, const std::vect
 			slot = ent;
 		}
 		tile_last[to] = (uint32_t)(k[4095] - (int)org[ti]);
-		tile_mid[to] = (uint32_t)(k[2047] - (int)org[ti]);
 	}
 	for (uint16_t e : rtab) if (e == 0xFFFF) return;
-	// per-lane entries of a tile workgroup and the block table of the mask kernel
-	std::vector<uint32_t> ptab((size_t)no * 128 * 4, 0), btab((size_t)no * 256, 0);
+	// one entry per block pair of a tile
+	std::vector<uint32_t> ptab((size_t)no * 128 * 4, 0);
 	{
 		std::vector<int> done(no, 0);
 		for (int ti = 0; ti < nt; ti++) {
@@ -392,19 +382,12 @@ void build_pipe_tables(const std::vector<int32_t> &O, int width, const std::vect
 					e[1 + h] = kb == 0 ? 0xFFFFFFFFu : (uint32_t)(k[kb * 16 - 1] - (int)org[ti]);
 				}
 			}
-			for (int b = 0; b < 256; b++) {
-				int lo = k[b * 16];
-				for (int i = 1; i < 16; i++) lo = std::min(lo, k[b * 16 + i]);
-				uint32_t bo = 0;
-				for (int r = 0; r < 256; r++) if ((rtab[(size_t)to * 256 + r] & 0xFF) == b) bo = rtab[(size_t)to * 256 + r] >> 8;
-				btab[(size_t)to * 256 + b] = (uint32_t)(lo - (int)org[ti]) | bo << 24;
-			}
 		}
 	}
-	// half-tile waves: the 64 block pairs whose blocks lie in the first / second 128 traversal blocks, raster order
-	std::vector<uint32_t> ptab2((size_t)no * 2 * 64 * 4, 0);
+	// half tiles: the block pairs whose blocks lie in the first / second 128 traversal blocks
 	for (int to = 0; to < no; to++)
 		for (int half = 0; half < 2; half++) {
+			uint32_t reg[64];  // raster offset inside the tile of every such pair's 8x4-pixel region, raster order
 			int cnt = 0;
 			for (int lane = 0; lane < 128; lane++) {
 				const uint32_t *e = ptab.data() + ((size_t)to * 128 + lane) * 4;
@@ -412,34 +395,29 @@ void build_pipe_tables(const std::vector<int32_t> &O, int width, const std::vect
 				if ((ka >> 7) != (kb >> 7)) return;  // a pair of blocks straddles the halves: not the structure assumed
 				if ((ka >> 7) != half) continue;
 				if (cnt == 64) return;
-				uint32_t *d = ptab2.data() + (((size_t)to * 2 + half) * 64 + cnt) * 4;
-				d[0] = e[0]; d[1] = e[1]; d[2] = e[2];
-				d[3] = (uint32_t)((lane >> 3) * 4 * width + (lane & 7) * 8);
-				cnt++;
+				reg[cnt++] = (uint32_t)((lane >> 3) * 4 * width + (lane & 7) * 8);
 			}
 			if (cnt != 64) return;
 			// the half must be a 64x32 (block rows r0..r0+7) or a 32x64 (block-pair columns c0..c0+3) rectangle
-			const uint32_t *d0 = ptab2.data() + ((size_t)to * 2 + half) * 64 * 4;
-			uint32_t geom = 0xFFFFFFFFu;
-			for (int vertical = 0; vertical < 2 && geom == 0xFFFFFFFFu; vertical++)
-				for (int first = 0; first < 16 && geom == 0xFFFFFFFFu; first += vertical ? 4 : 8) {
+			bool rect = false;
+			for (int vertical = 0; vertical < 2 && !rect; vertical++)
+				for (int first = 0; first < 16 && !rect; first += vertical ? 4 : 8) {
 					bool ok = true;
 					for (int l = 0; l < 64 && ok; l++) {
 						const uint32_t want = vertical ? (uint32_t)((l >> 2) * 4 * width + (first + (l & 3)) * 8)
 						                               : (uint32_t)((first + (l >> 3)) * 4 * width + (l & 7) * 8);
-						ok = d0[l * 4 + 3] == want;
+						ok = reg[l] == want;
 					}
-					if (ok) geom = (uint32_t)vertical | (uint32_t)first << 8;
+					rect = ok;
 				}
-			if (geom == 0xFFFFFFFFu) return;
-			t.tiles.geom[to * 2 + half] = geom;
+			if (!rect) return;
 		}
 	if (nt > 256) return;
 	for (int ti = 0; ti < nt; ti++) {
 		if (org[ti] >= (1u << 24)) return;
 		t.tiles.orgo[ti] = org[ti] | ((uint32_t)orient[ti] << 24);
 	}
-	for (int to = 0; to < no; to++) { t.tiles.last[to] = tile_last[to]; t.tiles.mid[to] = tile_mid[to]; }
+	for (int to = 0; to < no; to++) t.tiles.last[to] = tile_last[to];
 	std::vector<uint32_t> otab(64, 0);
 	for (size_t bo = 0; bo < bpat.size(); bo++) {
 		const std::vector<int> &pat = bpat[bo];
@@ -504,18 +482,14 @@ void build_pipe_tables(const std::vector<int32_t> &O, int width, const std::vect
 		t.tiles.qorg[to] = (uint32_t)(r0 * 4 * width + c0 * 8);
 	}
 	if (hipMalloc(&t.d_ptab, ptab.size() * 4) != hipSuccess) return;
-	if (hipMalloc(&t.d_btab, btab.size() * 4) != hipSuccess) return;
-	if (hipMalloc(&t.d_ptab2, ptab2.size() * 4) != hipSuccess) return;
-	if (hipMemcpy(t.d_ptab2, ptab2.data(), ptab2.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return;
 	if (hipMalloc(&t.d_htab, htab.size() * 4) != hipSuccess) return;
 	if (hipMemcpy(t.d_htab, htab.data(), htab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return;
 	if (hipMalloc(&t.d_otab, otab.size() * 4) != hipSuccess) return;
 	if (hipMalloc(&t.d_ttab, ttab.size() * 4) != hipSuccess) return;
 	if (hipMemcpy(t.d_ptab, ptab.data(), ptab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return;
-	if (hipMemcpy(t.d_btab, btab.data(), btab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return;
 	if (hipMemcpy(t.d_otab, otab.data(), otab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return;
 	if (hipMemcpy(t.d_ttab, ttab.data(), ttab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return;
-	t.pipe = true;
+	t.stream = true;
 }
 
 // Does the traversal decompose into aligned 64x64 tiles (4096 consecutive positions each)?  If so
@@ -565,7 +539,7 @@ void build_tile_tables(const std::vector<int32_t> &O, int width, ShapeTables &t)
 	t.n_tiles = nt;
 	t.n_orient = (int)pats.size();
 	t.tiled = true;
-	build_pipe_tables(O, width, org, orient, t);
+	build_stream_tables(O, width, org, orient, t);
 }
 
 int get_tables(int width, int height, const ShapeTables **out)
@@ -706,57 +680,13 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 	a.ws_lidx = (uint32_t *)E.e_lidx.p; a.ws_lmask = (uint64_t *)E.e_lmask.p; a.ws_lcur = (uint8_t *)E.e_lcur.p;
 	const ShapeTables *tb = nullptr;
 	if ((flags & CCT_FLAG_FRACTAL) && bs == 16 && g_ctx.use_tiles && !g_ctx.runtime_bs) { if ((rc = get_tables(width, height, &tb))) return rc; }
-	// a tile-path launch sequence (memset nodes + kernels), replayed as a graph from the second call with the same arguments
-	// on: no dispatch gaps between its nodes, fewer host calls
-	auto launch_or_replay = [&](const void *args, size_t args_bytes, int tag, const std::function<hipError_t()> &launch) -> int {
-		if (!g_ctx.use_graph) { HIP_TRY(launch()); return CCT_OK; }
-		std::vector<uint8_t> key(args_bytes + 2 * sizeof(int));
-		memcpy(key.data(), args, args_bytes);
-		memcpy(key.data() + args_bytes, &n, sizeof(int));
-		memcpy(key.data() + args_bytes + sizeof(int), &tag, sizeof(int));
-		EncSlot::PipeGraph *pg = nullptr;
-		for (auto &gr : E.p_graphs) if (gr.key == key) pg = &gr;
-		if (!pg) {
-			if (E.p_graphs.size() >= 6) {  // forget the least recently used argument set
-				size_t old = 0;
-				for (size_t i = 1; i < E.p_graphs.size(); i++) if (E.p_graphs[i].last_use < E.p_graphs[old].last_use) old = i;
-				exclusive_section([&]() -> int {
-					if (E.p_graphs[old].exec) (void)hipGraphExecDestroy(E.p_graphs[old].exec);
-					if (E.p_graphs[old].graph) (void)hipGraphDestroy(E.p_graphs[old].graph);
-					return 0;
-				});
-				E.p_graphs.erase(E.p_graphs.begin() + (long)old);
-			}
-			E.p_graphs.emplace_back();
-			E.p_graphs.back().key = key;
-			E.p_graphs.back().last_use = ++E.p_clock;
-			HIP_TRY(launch());  // first sight: plain launches (also sets the kernel attributes)
-			return CCT_OK;
-		}
-		pg->last_use = ++E.p_clock;
-		if (!pg->exec) {
-			const int crc = exclusive_section([&]() -> int {  // nothing else of the library runs during a capture (host.h)
-				HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-				hipError_t le = launch();
-				hipError_t ce = hipStreamEndCapture(st, &pg->graph);
-				if (le != hipSuccess) return fail(CCT_E_DEVICE, "tile-path capture: %s", hipGetErrorString(le));
-				HIP_TRY(ce);
-				HIP_TRY(hipGraphInstantiate(&pg->exec, pg->graph, nullptr, nullptr, 0));
-				return CCT_OK;
-			});
-			if (crc) return crc;
-		}
-		HIP_TRY(hipGraphLaunch(pg->exec, st));
-		return CCT_OK;
-	};
 	// Choice among the tile paths (option "tile_path"): 1 = default: the streaming kernel (encode_stream.hip) wherever it
-	// applies; 4 forces it, 3 the four-kernel pipeline of round 2, 2 the one-workgroup-per-slice tile kernel of round 1,
-	// 0 the generic table-gather kernel.
-	const bool pipe_ok = tb && tb->tiled && tb->pipe && NB <= PIPE_MAX_NB && !g_ctx.dbg_skip;
+	// applies; 4 forces it, 2 the one-workgroup-per-slice tile kernel of round 1, 0 the generic table-gather kernel.
+	const bool stream_ok = tb && tb->tiled && tb->stream && NB <= STREAM_MAX_NB && !g_ctx.dbg_skip;
 	const int tpg = g_ctx.stream_tpg;
 	const int gps = tb ? (tb->n_tiles + tpg - 1) / tpg : 0;
-	if (pipe_ok && (g_ctx.use_tiles == 1 || g_ctx.use_tiles == 4)) {
-		if ((rc = E.e_pairrec.ensure((size_t)n * (NB / 2) * PIPE_PAIR_REC))) return rc;
+	if (stream_ok && (g_ctx.use_tiles == 1 || g_ctx.use_tiles == 4)) {
+		if ((rc = E.e_pairrec.ensure((size_t)n * (NB / 2) * STREAM_PAIR_REC))) return rc;
 		if ((rc = E.e_hand.ensure(stream_ws_bytes(n, gps)))) return rc;
 		StreamArgs sa{};
 		sa.e = a;
@@ -766,34 +696,9 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 		sa.hand = (uint64_t *)E.e_hand.p; sa.ticket = (uint32_t *)(sa.hand + (size_t)n * gps * 4);
 		sa.spill_mask = (uint64_t *)E.e_lmask.p; sa.spill_idx = (uint16_t *)E.e_lidx.p; sa.pairrec = (uint8_t *)E.e_pairrec.p;
 		g_ctx.last_path = 3;
-		static const bool sstamps = getenv("CCT_STREAM_STAMPS") != nullptr;
-		(void)sstamps;
 		// two memsets and one kernel: launched plainly.  Replayed as a graph the three nodes took 0.20 ms in the bench against 0.15
 		// (profiles/r03_graph_ab.log): a graph pays between its nodes what it saves on the host, and there is nothing to save here
 		HIP_TRY(launch_encode_stream(sa, n, st));
-		return CCT_OK;
-	}
-	if (pipe_ok && g_ctx.use_tiles == 3) {
-		const int NT = tb->n_tiles;
-		if ((rc = E.e_role.ensure(per))) return rc;
-		if ((rc = E.e_toff.ensure((size_t)n * (2 * NT + 1) * 4))) return rc;
-		if ((rc = E.e_pairrec.ensure((size_t)n * (NB / 2) * PIPE_PAIR_REC))) return rc;
-		if ((rc = E.e_spill.ensure(per * 4))) return rc;
-		if ((rc = E.e_tflag.ensure((size_t)n * (NT + 1) * 4 + (size_t)n * NT * 4))) return rc;
-		PipeArgs pa{};
-		pa.e = a;
-		pa.tiles = tb->tiles; pa.ptab = tb->d_ptab; pa.ptab2 = tb->d_ptab2; pa.btab = tb->d_btab; pa.otab = tb->d_otab;
-		pa.ttab = tb->d_ttab;
-		pa.n_orient = tb->n_orient; pa.n_tiles = NT; pa.row_pitch = width;
-		pa.ssz = (uint8_t *)E.e_lcur.p; pa.mask = (uint64_t *)E.e_lmask.p; pa.roles = (uint8_t *)E.e_role.p;
-		pa.spec = (uint32_t *)E.e_lidx.p; pa.toff = (uint32_t *)E.e_toff.p; pa.pairrec = (uint8_t *)E.e_pairrec.p;
-		pa.spill_idx = (uint32_t *)E.e_spill.p;
-		pa.tflag = (uint32_t *)E.e_tflag.p; pa.tcount = pa.tflag + (size_t)n * NT; pa.tlist = pa.tcount + n;
-		PipeTune tune{g_ctx.pipe_tpw, g_ctx.pipe_timing ? g_ctx.pipe_us : nullptr};
-		g_ctx.last_path = 1;
-		static const bool stamps = getenv("CCT_PIPE_STAMPS") != nullptr;
-		if (!g_ctx.pipe_timing && !stamps) return launch_or_replay(&pa, sizeof pa, tune.tpw, [&]() { return launch_encode_pipe(pa, n, st, &tune); });
-		HIP_TRY(launch_encode_pipe(pa, n, st, &tune));
 		return CCT_OK;
 	}
 	if (tb && tb->tiled) {
@@ -1001,7 +906,6 @@ int cct_shutdown(void)
 		if (E.stream) (void)hipStreamSynchronize(E.stream);
 		if (E.stream_copy) (void)hipStreamSynchronize(E.stream_copy);
 		for (auto &g : E.z_graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
-		for (auto &g : E.p_graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
 		for (int i = 0; i < E.n_bufs; i++) E.all_bufs[i]->release();
 		hipEvent_t evs[] = {E.ev_k0s[0], E.ev_k1s[0], E.ev_z0s[0], E.ev_z1s[0], E.ev_k0s[1], E.ev_k1s[1], E.ev_z0s[1], E.ev_z1s[1],
 		                    E.ev_small[0], E.ev_small[1], E.ev_pack[0], E.ev_pack[1], E.ev_copied[0], E.ev_copied[1],
@@ -1015,7 +919,7 @@ int cct_shutdown(void)
 	if (g_gate) { (void)hipFree(g_gate); g_gate = nullptr; }
 	for (auto &kv : g_ctx.luts) {
 		ShapeTables &t = kv.second;
-		void *ptrs[] = {t.d_lut, t.d_org, t.d_orient, t.d_pat, t.d_ptab, t.d_ptab2, t.d_btab, t.d_otab, t.d_ttab, t.d_htab};
+		void *ptrs[] = {t.d_lut, t.d_org, t.d_orient, t.d_pat, t.d_ptab, t.d_otab, t.d_ttab, t.d_htab};
 		for (void *p : ptrs) if (p) (void)hipFree(p);
 	}
 	for (int k = 0; k < N_DEC_SLOTS; k++) {
@@ -1904,12 +1808,13 @@ int cct_set_option(const char *key, int value)
 {
 	std::lock_guard<std::mutex> lk(g_mu);
 	if (!strcmp(key, "zlib_threads")) { if (value < 1) return fail(CCT_E_ARG, "zlib_threads < 1"); g_ctx.zlib_threads = value; return CCT_OK; }
-	if (!strcmp(key, "tile_path")) { g_ctx.use_tiles = (value >= 0 && value <= 4) ? value : 1; return CCT_OK; }
+	if (!strcmp(key, "tile_path")) {
+		if (value == 3) return fail(CCT_E_ARG, "tile_path 3 (the four-kernel pipeline) has been removed");
+		g_ctx.use_tiles = (value >= 0 && value <= 4) ? value : 1; return CCT_OK;
+	}
 	if (!strcmp(key, "stream_tpg")) { g_ctx.stream_tpg = (value == 1 || value == 2 || value == 4) ? value : STREAM_TPG; return CCT_OK; }
 	if (!strcmp(key, "debug_skip")) { g_ctx.dbg_skip = value; return CCT_OK; }
 	if (!strcmp(key, "runtime_block_size")) { g_ctx.runtime_bs = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "pipe_tpw")) { g_ctx.pipe_tpw = value; return CCT_OK; }
-	if (!strcmp(key, "pipe_timing")) { g_ctx.pipe_timing = value; return CCT_OK; }
 	if (!strcmp(key, "device_deflate")) { g_ctx.device_deflate = value ? 1 : 0; return CCT_OK; }
 	if (!strcmp(key, "device_inflate")) { g_ctx.device_inflate = value ? 1 : 0; return CCT_OK; }
 	if (!strcmp(key, "deflate_graph")) { g_ctx.use_graph = value ? 1 : 0; return CCT_OK; }
@@ -1938,7 +1843,6 @@ int cct_get_option(const char *key, int *value)
 	if (!strcmp(key, "last_encode_path")) { *value = g_ctx.last_path; return CCT_OK; }
 	if (!strcmp(key, "runtime_block_size")) { *value = g_ctx.runtime_bs; return CCT_OK; }
 	if (!strcmp(key, "last_decode_path")) { *value = g_ctx.last_dec_path; return CCT_OK; }
-	if (!strncmp(key, "pipe_us_k", 9) && key[9] >= '1' && key[9] <= '4') { *value = (int)(g_ctx.pipe_us[key[9] - '1'] * 10.0f); return CCT_OK; }
 	if (!strcmp(key, "device_deflate")) { *value = g_ctx.device_deflate; return CCT_OK; }
 	if (!strcmp(key, "device_inflate")) { *value = g_ctx.device_inflate; return CCT_OK; }
 	if (!strcmp(key, "deflate_graph")) { *value = g_ctx.use_graph; return CCT_OK; }

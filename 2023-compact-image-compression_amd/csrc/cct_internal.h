@@ -58,67 +58,37 @@ struct TileEncArgs {
 size_t enc_tiles_lds_bytes(int NB, bool *role_in_lds);
 hipError_t launch_encode_tiles(const TileEncArgs &ta, int n, hipStream_t s);
 
-// staged pipeline (encode_pipe.hip): analyse -> resolve -> pack, tile-parallel, same applicability as the tile path
-// up to 1024x1024 (larger tiled shapes stay on encode_tiles_kernel)
-constexpr int PIPE_MAX_NB = 65536;          // blocks per slice (the resolve kernel keeps role[] in LDS)
-constexpr int PIPE_DEFAULT_MAX_NB = 16384;  // largest slice for which the pipeline is the default choice (see api.cpp)
-constexpr int PIPE_PAIR_REC = 80;           // bytes per meshed-pair record: jump byte + up to 64 token bytes, padded to 16
+// single streaming pass (encode_stream.hip): one kernel, every pixel read once.  block_size 16, a traversal made of at most 256
+// aligned 64x64 tiles with the block structure build_stream_tables (api.cpp) checks
+constexpr int STREAM_MAX_NB = 65536;        // blocks per slice
+constexpr int STREAM_PAIR_REC = 80;         // bytes per meshed-pair record: jump byte + up to 64 token bytes, padded to 16
 constexpr uint32_t CCT_ST_INTERNAL = 0x80000000u;  // the kernels disagree about a size: a bug, never a data property
-struct PipeTiles {             // small per-shape tables carried IN the kernel arguments: one scalar load, no pointer to chase
+struct StreamTiles {           // small per-shape tables carried IN the kernel arguments: one scalar load, no pointer to chase
 	uint32_t orgo[256];          // raster index of each tile's top-left pixel (< 2^24) | tile orientation << 24: ONE scalar load gives
 	                             // both (a byte array indexed by the tile became a vector load the next table lookup had to wait for)
 	uint32_t last[TILE_MAX_ORIENT];  // raster offset inside the tile of the tile's last traversal position
-	uint32_t mid[TILE_MAX_ORIENT];   // the same for position 2047 (the last pixel of the first half tile)
 	uint32_t qorg[TILE_MAX_ORIENT];  // raster offset inside the tile of the 32x32-pixel quadrant its first 64 traversal blocks cover
-	uint32_t geom[TILE_MAX_ORIENT * 2];  // region of half h of orientation o: bit 0 = vertical split (32x64 pixels), bits 8.. = first
-	                                     // block row (horizontal split) or first block-pair column (vertical split)
 };
-struct PipeArgs {
-	EncArgs e;                   // e.lut must be the traversal table
-	PipeTiles tiles;
-	const uint32_t *ptab;        // n_orient * 128 entries of 4 dwords, one per lane of a tile workgroup (lane = block row * 8 + block pair):
-	                             //   [0] traversal block index | orientation << 8 of the left block, the same << 16 for the right block
-	                             //   [1], [2] raster offset inside the tile of the pixel that precedes the left / right block in
-	                             //   traversal order (0xFFFFFFFF: the block opens the tile)
-	const uint32_t *ptab2;       // n_orient * 2 * 64 entries of 4 dwords, one per lane of a half-tile wave (half = 128 traversal blocks):
-	                             //   [0..2] as ptab, [3] raster offset inside the tile of the lane's 8x4-pixel region
-	const uint32_t *btab;        // n_orient * 256: traversal block of a tile -> raster offset of its top-left pixel | orientation << 24
-	const uint32_t *otab;        // 4 * 16 dwords per block orientation: eight v_perm selectors, quadrant choice bits
-	const uint32_t *ttab;        // 16 * 4 dwords: token byte selectors and length for the 16 two-byte masks of a 4-pixel group
-	int n_orient, n_tiles, row_pitch;
-	uint8_t *ssz;                // n * NB: token bytes of every block emitted alone after its traversal predecessor | 0x80 if difficult
-	uint64_t *mask;              // n * NB: candidate fit masks, valid for difficult blocks
-	uint32_t *tflag;             // n * n_tiles: tile has difficult blocks; then
-	uint32_t *tcount;            // n (contiguous with tflag, one memset): tiles listed per slice
-	uint32_t *tlist;             // n * n_tiles: the listed tiles of every slice (work of the mask kernel)
-	uint8_t *roles;              // n * NB: the block partition
-	uint32_t *spec;              // n * NB: leaders: pair record << 8 | group bytes; blocks after a meshed block: predecessor pixel
-	uint32_t *toff;              // n * (2 * n_tiles + 1): payload offset of every half tile's first token, then the token total
-	uint8_t *pairrec;            // n * (NB / 2) * PIPE_PAIR_REC
-	uint32_t *spill_idx;         // n * NB: ordered difficult-block list beyond the LDS capacity of the resolve kernel
-};
-struct PipeTune {   // tuning runs only
-	int tpw;           // tiles per analyse workgroup (0: default)
-	float *times_us;   // if set: the four kernels are timed with events (synchronises): [analyse, masks, resolve, pack]
-};
-hipError_t launch_encode_pipe(const PipeArgs &pa, int n, hipStream_t s, const PipeTune *tune = nullptr);
-
-// single streaming pass (encode_stream.hip): same applicability as the pipeline; one kernel, every pixel read once
 constexpr int STREAM_TPG = 4;       // default tiles per group = waves per workgroup (1, 2 or 4: option "stream_tpg")
 struct StreamArgs {
 	EncArgs e;
-	PipeTiles tiles;
-	const uint32_t *ptab;        // as PipeArgs::ptab
+	StreamTiles tiles;
+	const uint32_t *ptab;        // n_orient * 128 entries of 4 dwords, one per block pair of a tile (entry = block row * 8 + block pair):
+	                             //   [0] traversal block index | orientation << 8 of the left block, the same << 16 for the right block
+	                             //   [1], [2] raster offset inside the tile of the pixel that precedes the left / right block in
+	                             //   traversal order (0xFFFFFFFF: the block opens the tile)
 	const uint32_t *htab;        // n_orient * 32 entries of 2 dwords: the 32 block pairs (8 rows x 4) of the quadrant a tile's first 64
 	                             //   traversal blocks cover (origin: tiles.qorg): [0] as ptab[0], [1] raster offset of the pair inside the tile
-	const uint32_t *otab, *ttab; // as PipeArgs (ttab entry: selectors, token bytes, kept bits of the low bytes)
+	const uint32_t *otab;        // 4 * 16 dwords per block orientation: eight v_perm selectors, quadrant choice bits
+	const uint32_t *ttab;        // 16 * 4 dwords: token byte selectors and length for the 16 two-byte masks of a 4-pixel group, kept
+	                             //   bits of the low bytes
 	int n_tiles, row_pitch, gps, tpg; // gps: groups per slice, tpg: tiles per group
 	int dbg;                     // tuning runs only (CCT_STREAM_DBG): 1 no carry wait, 2 no look-back (results then invalid), 4 wrong group guess (results valid)
 	uint64_t *hand;              // n * gps * 4 hand-off words, then
 	uint32_t *ticket;            // n group tickets (one allocation: zeroed by one memset before every launch)
 	uint64_t *spill_mask;        // n * NB: candidate masks beyond the LDS list of a tile
 	uint16_t *spill_idx;         // n * NB: their blocks
-	uint8_t *pairrec;            // n * (NB / 2) * PIPE_PAIR_REC: meshed pairs beyond one per lane
+	uint8_t *pairrec;            // n * (NB / 2) * STREAM_PAIR_REC: meshed pairs beyond one per lane
 };
 inline size_t stream_ws_bytes(int n, int gps) { return ((size_t)n * gps * 32 + (size_t)n * 4 + 15) & ~(size_t)15; }
 hipError_t launch_encode_stream(const StreamArgs &sa, int n, hipStream_t s);

@@ -1,7 +1,7 @@
 // CompaCT encode, stage (i) -- traversal, segmentation / mesh, delta coding, tag-byte pack (core.py:212-330 with
 // curve.py:45-138 and cluster.py:20-199 underneath) -- as ONE streaming kernel: every pixel is read from HBM once and
-// every payload byte written once.  Same applicability as encode_pipe.hip (block_size 16, traversal made of aligned 64x64
-// tiles whose 4x4-pixel blocks are traversal blocks: every power-of-two square up to 1024x1024).
+// every payload byte written once.  Applies to block_size 16 and a traversal made of aligned 64x64 tiles whose 4x4-pixel
+// blocks are traversal blocks (build_stream_tables in api.cpp): every power-of-two square up to 1024x1024.
 //
 //   grid = slices x groups; a group = SW consecutive tiles (SW x 256 traversal blocks); one 256-lane workgroup per group,
 //   one wave per tile.  A workgroup draws its group index from a per-slice ticket, so every group it ever waits for is
@@ -120,7 +120,7 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v)  // a value every lane
 }
 
 // Rows 0..3 of a 4x4 block as (columns 0-1, columns 2-3) dwords -> its 16 pixels in traversal order (see
-// build_pipe_tables in api.cpp for the structure this relies on and verifies).
+// build_stream_tables in api.cpp for the structure this relies on and verifies).
 __device__ __forceinline__ void permute_block(uint32_t l0, uint32_t h0, uint32_t l1, uint32_t h1, uint32_t l2, uint32_t h2,
                                               uint32_t l3, uint32_t h3, const LDS(uint32_t) *ot, uint32_t d[8])
 {
@@ -752,10 +752,10 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 	}
 	if (npairs > (uint32_t)PAIR_FAST) {
 		// more pairs than lanes (dense noise): the rest leave their bytes in HBM records and are copied into the image later
-		uint8_t *rec0 = a.pairrec + ((size_t)sl * (NB / 2) + (size_t)g * (NBG / 2)) * PIPE_PAIR_REC;
+		uint8_t *rec0 = a.pairrec + ((size_t)sl * (NB / 2) + (size_t)g * (NBG / 2)) * STREAM_PAIR_REC;
 		for (uint32_t e = PAIR_FAST + tid; e < npairs; e += ST) {
 			const int i = pairs[e], j = roles[i], p = i + j;
-			uint8_t *out = rec0 + (size_t)(e - PAIR_FAST) * PIPE_PAIR_REC;
+			uint8_t *out = rec0 + (size_t)(e - PAIR_FAST) * STREAM_PAIR_REC;
 			int n = 0;
 			out[n++] = (uint8_t)(0x80 | j);  // core.py:290-294
 			int prev = (int)prev_px_final(i);
@@ -854,11 +854,11 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 		(void)emit16(px_ + 8, p_mb >> 16, o, stg, ttab);
 	}
 	if (npairs > (uint32_t)PAIR_FAST) {
-		const uint8_t *rec0 = a.pairrec + ((size_t)sl * (NB / 2) + (size_t)g * (NBG / 2)) * PIPE_PAIR_REC;
+		const uint8_t *rec0 = a.pairrec + ((size_t)sl * (NB / 2) + (size_t)g * (NBG / 2)) * STREAM_PAIR_REC;
 		for (uint32_t e = PAIR_FAST + tid; e < npairs; e += ST) {
 			const int i = pairs[e], p = i + roles[i];
 			const uint32_t n = 33u + (roles[p] & 0x7Fu), o = boff[i];
-			const uint8_t *src = rec0 + (size_t)(e - PAIR_FAST) * PIPE_PAIR_REC;
+			const uint8_t *src = rec0 + (size_t)(e - PAIR_FAST) * STREAM_PAIR_REC;
 			for (uint32_t j = 0; j < n; j++) stg[o + j] = src[j];
 		}
 	}

@@ -102,15 +102,20 @@ def test_options_round_trip_without_a_device():
     L = _ffi.lib()
     v = C.c_int(-1)
     for key, given, want in ((b"encode_slots", 2, 2), (b"encode_slots", 7, 2), (b"encode_slots", 0, 1), (b"decode_slots", 1, 1),
-                             (b"decode_slots", 5, 2), (b"tile_path", 3, 3), (b"tile_path", 4, 4),
+                             (b"decode_slots", 5, 2), (b"tile_path", 2, 2), (b"tile_path", 4, 4),
                              (b"tile_path", 9, 1), (b"device_inflate", 5, 1), (b"deflate_graph", 0, 0), (b"deflate_graph", 1, 1),
                              (b"deflate_compact_records", 0, 0), (b"deflate_compact_records", 3, 1),
                              (b"decode_yields", 0, 0), (b"decode_yields", 2, 1), (b"queue_ahead", 0, 0), (b"queue_ahead", 1, 1),
                              (b"deflate_fork", 0, 0), (b"deflate_fork", 1, 1)):
         assert L.cct_set_option(key, given) == 0
         assert L.cct_get_option(key, C.byref(v)) == 0 and v.value == want, (key, given, v.value)
+    # tile_path 3 (the four-kernel pipeline) is removed: refused, and the current choice stays
+    assert L.cct_set_option(b"tile_path", 4) == 0 and L.cct_set_option(b"tile_path", 3) != 0
+    assert L.cct_get_option(b"tile_path", C.byref(v)) == 0 and v.value == 4
     assert L.cct_set_option(b"encode_slots", 1) == 0 and L.cct_set_option(b"tile_path", 1) == 0
     assert L.cct_set_option(b"deflate_ways", 2) != 0      # removed in round 2
+    assert L.cct_set_option(b"pipe_tpw", 1) != 0          # removed with the pipeline
+    assert L.cct_set_option(b"pipe_timing", 1) != 0
     assert L.cct_set_option(b"no_such_option", 1) != 0
     assert L.cct_get_option(b"no_such_option", C.byref(v)) != 0
 

@@ -468,9 +468,9 @@ def _last_path(L):
 
 @pytest.mark.parametrize("n_px", [128, 256, 512, 1024])
 def test_tile_path_equals_generic_path(hip, n_px):
-    """Four implementations of stage (i) must agree byte for byte (payload, sizes, statistics, block roles) -- and
-    with the oracle: the streaming kernel (encode_stream.hip, the default), the four-kernel pipeline (encode_pipe.hip),
-    the one-workgroup-per-slice tile kernel and the generic LUT-gather kernel.  The test also checks that each path
+    """Three implementations of stage (i) must agree byte for byte (payload, sizes, statistics, block roles) -- and
+    with the oracle: the streaming kernel (encode_stream.hip, the default) with 4, 2 and 1 tiles per workgroup, the
+    one-workgroup-per-slice tile kernel and the generic LUT-gather kernel.  The test also checks that each path
     really ran (no silent fallback)."""
     from oracle import oracle
     from cct_hip import DeviceBuffer, codec_params, encode_payload_dev, _ffi
@@ -490,7 +490,7 @@ def test_tile_path_equals_generic_path(hip, n_px):
     d_img = DeviceBuffer.from_numpy(imgs)
     res = []
     # option value, implementation that must have run, tiles per workgroup of the streaming kernel (4 is the default)
-    for tile, ran, tpg in ((4, 3, 4), (4, 3, 2), (4, 3, 1), (3, 1, 4), (2, 2, 4), (0, 0, 4)):
+    for tile, ran, tpg in ((4, 3, 4), (4, 3, 2), (4, 3, 1), (2, 2, 4), (0, 0, 4)):
         _ffi.check(L.cct_set_option(b"tile_path", tile))
         _ffi.check(L.cct_set_option(b"stream_tpg", tpg))
         d_pay, d_sz, d_st = DeviceBuffer(n * stride), DeviceBuffer(4 * n), DeviceBuffer(4 * n)
@@ -514,7 +514,9 @@ def test_tile_path_equals_generic_path(hip, n_px):
 
 
 def test_default_path_by_shape(hip):
-    """The default choice among the tile paths: the streaming kernel wherever the traversal is made of 64x64 tiles of 4x4 blocks."""
+    """The default choice among the tile paths: the streaming kernel wherever the traversal is made of 64x64 tiles of 4x4 blocks
+    and there are at most 256 tiles, the tile kernel for more (2048x2048: 1024 tiles)."""
+    from oracle import oracle
     from cct_hip import _ffi
     L = _ffi.lib()
     cfg = hip.default_config()
@@ -522,13 +524,17 @@ def test_default_path_by_shape(hip):
     assert _last_path(L) == 3
     hip.encode_batch(gi.ct_phantom(3, 1024)[None], cfg)
     assert _last_path(L) == 3
+    big = gi.ct_phantom(3, 2048)
+    f = hip.encode_batch(big[None], cfg)[0]
+    assert _last_path(L) == 2
+    assert f == oracle.encode(big)
     hip.encode_batch(gi.ct_phantom(3, 64)[None], cfg)   # one tile only: not a tiled shape -> generic kernel
     assert _last_path(L) == 0
 
 
-@pytest.mark.parametrize("tile, ran", [(4, 3), (3, 1)])
-def test_pipeline_signed_and_flag_variants(hip, tile, ran):
-    """The streaming kernel and the staged pipeline with int16 input (segmentation sees signed values), segmentation off
+@pytest.mark.parametrize("tile, ran", [(4, 3), (2, 2)])
+def test_tile_paths_signed_and_flag_variants(hip, tile, ran):
+    """The streaming kernel and the tile kernel with int16 input (segmentation sees signed values), segmentation off
     and EOF handling, against the oracle, on 512x512."""
     from oracle import oracle
     from cct_hip import _ffi
@@ -554,8 +560,8 @@ def test_pipeline_signed_and_flag_variants(hip, tile, ran):
 
 
 def test_config4_1024_square_batch(hip):
-    """BASELINE configs[3]: 1024x1024 slices, block_size 16 -> tile kernel with role[] in the HBM
-    workspace (65536 blocks do not fit LDS next to the rings); checked against the oracle."""
+    """BASELINE configs[3]: 1024x1024 slices, block_size 16 -> the streaming kernel at its largest shape (256 tiles,
+    65536 blocks); checked against the oracle."""
     from oracle import oracle
     cfg = hip.default_config()
     imgs = np.stack([gi.ct_phantom(80 + i, 1024) for i in range(4)])

@@ -1,4 +1,5 @@
-// Hardware probes behind the design of csrc/encode_pipe.hip (run on the GPU box: tools/microbench/run.sh).
+// Hardware probes behind the design of the tile-parallel encode front end, which csrc/encode_stream.hip inherited (run on
+// the GPU box: tools/microbench/run.sh).
 //   1. do ds_write_b32 / ds_write_b64 at byte addresses that are not multiples of 4 store the bytes at that address?
 //   2. wave-instruction rates of ds_write_b8, ds_write_b32, ds_or_b32, ds_write_b64 (all lanes, conflict-free)
 //   3. HBM read rate: 16 B per lane in raster order against 8 B per lane, four rows per 4x4-pixel block with the
@@ -104,7 +105,7 @@ __global__ void __launch_bounds__(256) read_blocks_kernel(const uint16_t *in, in
 }
 
 // one wave per 64x32-pixel half tile of a 512x512 slice: lane = 8x4 pixels, four 16-byte row loads (eight 128-byte
-// lines per wave-instruction, 1 KB apart) -- the front end of encode_pipe.hip
+// lines per wave-instruction, 1 KB apart) -- the tile-parallel front end (round 2), which encode_stream.hip inherited
 __global__ void __launch_bounds__(64) read_halftiles_kernel(const uint16_t *in, uint32_t *out, int rows_per_lane)
 {
 	const int ht = blockIdx.x & 127, sl = blockIdx.x >> 7;
