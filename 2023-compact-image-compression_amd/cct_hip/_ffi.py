@@ -13,6 +13,12 @@ LIB_PATH = os.environ.get("CCT_HIP_LIB") or os.path.join(_HERE, "libcompact_hip.
 # error codes (include/compact_hip.h)
 OK, E_MAGIC, E_ZLIB, E_OVERFLOW, E_STREAM, E_SHAPE, E_CAP, E_NOMEM, E_DEVICE, E_ARG, E_MIXED = range(11)
 FLAG_FRACTAL, FLAG_SEGMENTATION, FLAG_DEFLATE, FLAG_SIGNED_SEG = 1, 2, 4, 8
+FLAG_LEVEL_MASK = 0xF00
+
+
+def flag_deflate_level(level):
+    """CCT_FLAG_DEFLATE_LEVEL(level): the zlib level field of the encoder flags (0 = level 9)."""
+    return (int(level) & 15) << 8
 ST_Q7, ST_CAP, ST_OVERFLOW, ST_STREAM = 1, 2, 4, 8
 ROLE_PARTNER = 0xFF
 
@@ -66,6 +72,8 @@ _SIGS = {
                                           C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cct_zlib_compress_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cct_zlib_compress_batch_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]),
     "cct_zlib_decompress_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "cct_read_header": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.POINTER(Header)]),
     "cct_decode_payload_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

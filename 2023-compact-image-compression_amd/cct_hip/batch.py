@@ -25,8 +25,27 @@ def magic_bytes(config):
     return b[-4:].rjust(4, b"\0")
 
 
+def deflate_level(config):
+    """config['encoder']['deflate_level'] -> zlib level of the DEFLATE stage: absent -> 9 (what the reference writes),
+    -1 -> 6 (Z_DEFAULT_COMPRESSION), 4 .. 9 as given.  Levels 0 to 3 run deflate_stored / deflate_fast, which the
+    device does not implement: ValueError, as for anything else."""
+    level = config["encoder"].get("deflate_level")
+    if level is None:
+        return 9
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise ValueError(f"deflate_level must be an integer, got {level!r}")
+    level = int(level)
+    if level == -1:
+        return 6
+    if not 4 <= level <= 9:
+        raise ValueError(f"deflate_level {level}: supported levels are -1 and 4 to 9 "
+                         "(0 to 3 are deflate_stored / deflate_fast, not on the device)")
+    return level
+
+
 def codec_params(config, dtype=None):
-    """config dict -> (flags, block_size, eof, magic, channels, bytes_per_channel)."""
+    """config dict -> (flags, block_size, eof, magic, channels, bytes_per_channel).  An optional
+    config['encoder']['deflate_level'] sets the CCT_FLAG_DEFLATE_LEVEL field (absent: field 0 = level 9)."""
     enc = config["encoder"]
     tr = enc["transforms"]
     flags = 0
@@ -38,6 +57,8 @@ def codec_params(config, dtype=None):
         flags |= _ffi.FLAG_DEFLATE
     if dtype is not None and np.dtype(dtype).kind == "i":
         flags |= _ffi.FLAG_SIGNED_SEG
+    if enc.get("deflate_level") is not None:
+        flags |= _ffi.flag_deflate_level(deflate_level(config))
     eof = enc.get("end_of_file")
     return (flags, int(config["block_size"]), -1 if eof is None else int(eof) % 256, magic_bytes(config),
             int(enc["channels"]), int(enc["bytes_per_channel"]))
@@ -265,10 +286,15 @@ def decode_batch(files, config=None, out_dev=None):
     return out
 
 
-def zlib_compress_batch(blobs):
+def zlib_compress_batch(blobs, level=9):
     """DEFLATE stage alone on the device: [bytes] -> [zlib streams], each byte-identical to
-    zlib.compress(blob, level=9) (what the reference calls at core.py:340)."""
+    zlib.compress(blob, level) -- level 9 by default (what the reference calls at core.py:340), 4 to 8, or
+    -1 for zlib's default 6.  Levels 0 to 3 are not on the device (ValueError)."""
     import zlib
+    level = int(level)
+    if level != -1 and not 4 <= level <= 9:
+        raise ValueError(f"zlib level {level}: supported levels are -1 and 4 to 9 "
+                         "(0 to 3 are deflate_stored / deflate_fast, not on the device)")
     L = _ffi.lib()
     n = len(blobs)
     if n == 0:
@@ -281,7 +307,8 @@ def zlib_compress_batch(blobs):
     out_stride = (len(zlib.compress(b"", 0)) + in_stride + (in_stride >> 12) + (in_stride >> 14) + (in_stride >> 25) + 13 + 128 + 63) & ~63
     out = np.empty((n, out_stride), dtype=np.uint8)
     sizes = np.zeros(n, dtype=np.uint32)
-    _ffi.check(L.cct_zlib_compress_batch(data, offs.ctypes.data, n, out.ctypes.data, out_stride, sizes.ctypes.data))
+    _ffi.check(L.cct_zlib_compress_batch_level(data, offs.ctypes.data, n, level, out.ctypes.data, out_stride,
+                                               sizes.ctypes.data))
     return [out[i, : sizes[i]].tobytes() for i in range(n)]
 
 

@@ -725,12 +725,14 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 // passes, the run list, the block walk) left half of the 256 CUs idle.
 constexpr size_t DEFLATE_PASS_BYTES = (size_t)1 << 30;
 
-// DEFLATE (zlib level 9 stream) of n device-resident byte strings on the device; output slice i =
+// DEFLATE (zlib stream of `level`, 4 .. 9) of n device-resident byte strings on the device; output slice i =
 // 13 header bytes + zlib stream at d_out + i*out_stride (E.z_out), sizes in E.z_outsizes.
 int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint32_t *d_in_sizes, int n, const uint8_t header13[13],
-                   size_t out_stride)
+                   size_t out_stride, int level)
 {
 	if (in_stride % 256 != 0 || out_stride % 4 != 0) return fail(CCT_E_ARG, "deflate strides must be multiples of 256 / 4");
+	DeflateArgs a{};
+	if (!deflate_level_args(level, a)) return fail(CCT_E_ARG, "zlib level %d is not on the device", level);
 	const size_t EB = (size_t)n * in_stride;
 	if (EB >= ((size_t)1 << 32)) return fail(CCT_E_ARG, "deflate batch of %zu bytes exceeds the 4 GiB sort limit; split the batch", EB);
 	const int max_blocks = (int)(in_stride / 16383 + 2);
@@ -762,7 +764,6 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 		const int crc = exclusive_section([&]() -> int { HIP_TRY(hipStreamCreateWithFlags(&E.stream_side, hipStreamNonBlocking)); return CCT_OK; });
 		if (crc) return crc;
 	}
-	DeflateArgs a{};
 	a.in = d_in; a.in_stride = in_stride; a.in_sizes = d_in_sizes;
 	a.rec_in = (uint64_t *)E.z_vals_in.p; a.rec_out = (uint64_t *)E.z_vals_out.p;
 	a.pos_mask = (g_ctx.compact_recs && in_stride < ((size_t)1 << 22)) ? (1u << 22) - 1u : 0xFFFFFFFFu;
@@ -1110,7 +1111,7 @@ int cct_encode_payload_dev(const uint16_t *d_images, int n, int width, int heigh
 	int rc = check_shape(n, width, height, block_size);
 	if (rc) return rc;
 	if ((rc = ensure_ctx())) return rc;
-	return encode_payload_locked(g_enc[0], g_ctx.stream, d_images, n, width, height, block_size, flags, eof_byte, d_payload, payload_stride,
+	return encode_payload_locked(g_enc[0], g_ctx.stream, d_images, n, width, height, block_size, flags & ~CCT_FLAG_LEVEL_MASK, eof_byte, d_payload, payload_stride,
 	                             d_payload_sizes, d_status, d_stats, d_roles);
 }
 
@@ -1128,6 +1129,13 @@ static EncSlot &acquire_encode_slot(std::unique_lock<std::mutex> &lk)
 		}
 		std::this_thread::sleep_for(std::chrono::microseconds(50));
 	}
+}
+
+// CCT_FLAG_DEFLATE_LEVEL field -> zlib level (a clear field is level 9, what the reference writes); -1 for a refused field
+static int flags_deflate_level(uint32_t flags)
+{
+	const int f = (int)((flags & CCT_FLAG_LEVEL_MASK) >> 8);
+	return f == 0 ? 9 : (f >= 4 && f <= 9) ? f : -1;
 }
 
 // core.py:193-210 (big-endian fields, values masked to a byte / 16 bits)
@@ -1256,9 +1264,9 @@ static int files_to_strided(FilesOut &f, uint8_t *h_first, size_t out_stride)
 	return CCT_OK;
 }
 
-// DEFLATE (or none) on the host thread team: payloads come back, libz level 9 per slice (core.py:340), header in front
+// DEFLATE (or none) on the host thread team: payloads come back, libz at `level` per slice (9: core.py:340), header in front
 static int files_on_host(EncSlot &E, int n, size_t stride, const std::vector<uint32_t> &psz, const uint8_t hdr13[13], bool defl,
-                         uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, const uint32_t *h_status)
+                         int level, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, const uint32_t *h_status)
 {
 	const double t_copy0 = now_ms();
 	uint8_t *stage = (uint8_t *)E.h_stage.p;
@@ -1275,9 +1283,9 @@ static int files_on_host(EncSlot &E, int n, size_t stride, const std::vector<uin
 		uint8_t *o = h_out + (size_t)i * out_stride;
 		memcpy(o, hdr13, 13);
 		const uint8_t *pl = stage + (size_t)i * stride;
-		if (defl) {  // zlib.compress(data, level=9), core.py:340
+		if (defl) {  // zlib.compress(data, level), core.py:340 with level 9
 			uLongf dl = (uLongf)(out_stride - 13);
-			const int zr = compress2(o + 13, &dl, pl, psz[i], 9);
+			const int zr = compress2(o + 13, &dl, pl, psz[i], level);
 			if (zr != Z_OK) { zerr.store(zr); h_out_sizes[i] = 0; return; }
 			h_out_sizes[i] = 13 + (uint32_t)dl;
 		} else {
@@ -1300,6 +1308,11 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 	const bool packed = h_packed_offsets != nullptr;
 	const double t_call0 = now_ms();
 	EncodeInFlight in_flight;  // decode calls that start meanwhile pick the INFLATE geometry that shares the device best
+	const int level = flags_deflate_level(flags);
+	if (level < 0)
+		return fail(CCT_E_ARG, "deflate level field %u: levels 4 .. 9 only (1 .. 3 are deflate_fast: not on the device)",
+		            (flags & CCT_FLAG_LEVEL_MASK) >> 8);
+	flags &= ~CCT_FLAG_LEVEL_MASK;  // the payload stage and the .cct header do not depend on it
 	int rc = check_shape(n, width, height, block_size);
 	if (rc) return rc;
 	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device
@@ -1371,7 +1384,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 	uint8_t hdr13[13];
 	make_header13(hdr13, magic, width, height, channels, bytes_per_channel, flags);
 	if (defl && g_ctx.device_deflate) {
-		// DEFLATE on the device: zlib.compress(data, level=9) (core.py:340) restated in deflate_kernels.hip
+		// DEFLATE on the device: zlib.compress(data, level) (core.py:340, level 9) restated in deflate_kernels.hip
 		if (!one_pass)
 			for (int i = 0; i < n; i++)
 				if (h_status[i] & CCT_ST_CAP) return fail(CCT_E_CAP, "slice %d overflowed its payload stride", i);
@@ -1390,7 +1403,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 			const int nc = std::min(chunk, n - c0);
 			HIP_TRY(hipEventRecord(ev_z0, E.stream));
 			rc = deflate_locked(E, (const uint8_t *)E.e_payload.p + (size_t)c0 * stride, stride,
-			                    (const uint32_t *)E.e_sizes.p + c0, nc, hdr13, zstride);
+			                    (const uint32_t *)E.e_sizes.p + c0, nc, hdr13, zstride, level);
 			if (rc) return rc;
 			HIP_TRY(hipEventRecord(ev_z1, E.stream));
 			g_gate_passes_issued.fetch_add(1, std::memory_order_relaxed);
@@ -1476,7 +1489,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 		if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
 		return CCT_OK;
 	}
-	rc = files_on_host(E, n, stride, psz, hdr13, defl, h_out, out_stride, h_out_sizes, h_status);
+	rc = files_on_host(E, n, stride, psz, hdr13, defl, level, h_out, out_stride, h_out_sizes, h_status);
 	if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
 	return rc;
 }
@@ -1500,8 +1513,8 @@ int cct_encode_batch_packed(const uint16_t *images, int images_on_device, int n,
 	                         bytes_per_channel, h_archive, archive_cap, h_out_sizes, h_status, h_payload_sizes, h_stats, h_offsets);
 }
 
-int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, uint8_t *h_out, size_t out_stride,
-                            uint32_t *h_out_sizes)
+static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, uint8_t *h_out,
+                                    size_t out_stride, uint32_t *h_out_sizes)
 {
 	std::lock_guard<std::mutex> lk(g_mu);
 	ApiCall in_call;
@@ -1528,10 +1541,19 @@ int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int 
 	}
 	HIP_TRY(hipMemcpyAsync(E.z_insizes.p, isz.data(), (size_t)n * 4, hipMemcpyHostToDevice, E.stream));
 	uint8_t hdr13[13] = {0};
-	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride);
+	struct Events {  // the DEFLATE pass alone, for cct_last_timings
+		hipEvent_t e[2] = {nullptr, nullptr};
+		~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+	} ev;
+	HIP_TRY(hipEventCreate(&ev.e[0]));
+	HIP_TRY(hipEventCreate(&ev.e[1]));
+	HIP_TRY(hipEventRecord(ev.e[0], E.stream));
+	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride, level);
 	if (rc) return rc;
+	HIP_TRY(hipEventRecord(ev.e[1], E.stream));
 	HIP_TRY(hipMemcpyAsync(osz.data(), E.z_outsizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
 	HIP_TRY(hipStreamSynchronize(E.stream));
+	HIP_TRY(hipEventElapsedTime(&tl_deflate_ms, ev.e[0], ev.e[1]));
 	for (int i = 0; i < n; i++) {
 		h_out_sizes[i] = osz[i] - 13;
 		HIP_TRY(hipMemcpyAsync(h_out + (size_t)i * out_stride, (uint8_t *)E.z_out.p + (size_t)i * zstride + 13, osz[i] - 13,
@@ -1539,6 +1561,21 @@ int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int 
 	}
 	HIP_TRY(hipStreamSynchronize(E.stream));
 	return CCT_OK;
+}
+
+int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, uint8_t *h_out, size_t out_stride,
+                            uint32_t *h_out_sizes)
+{
+	return zlib_compress_batch_impl(h_in, h_offsets, n, 9, h_out, out_stride, h_out_sizes);
+}
+
+int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, uint8_t *h_out,
+                                  size_t out_stride, uint32_t *h_out_sizes)
+{
+	if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION
+	if (level >= 0 && level <= 3) return fail(CCT_E_ARG, "zlib level %d: deflate_stored / deflate_fast: not on the device", level);
+	if (level < 4 || level > 9) return fail(CCT_E_ARG, "zlib level %d: levels are -1 and 4 .. 9", level);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, level, h_out, out_stride, h_out_sizes);
 }
 
 // take a free decode slot (see DecSlot)

@@ -174,7 +174,11 @@ struct DeflateArgs {
 	int max_blocks;
 	uint8_t *out; size_t out_stride; uint32_t *out_sizes;            // whole .cct files (header + zlib stream)
 	uint8_t header13[16];
+	// the zlib level (4 .. 9, all deflate_slow): deflate.c configuration_table entries and the second header byte
+	uint32_t good, max_lazy, nice, max_chain, zlib_flg;
 };
+// a level's fields of DeflateArgs (deflate_kernels.hip); false for levels outside 4 .. 9
+bool deflate_level_args(int level, DeflateArgs &a);
 hipError_t deflate_init_tables();
 size_t deflate_sort_temp_bytes(size_t total, int n);
 hipError_t launch_pack(const uint8_t *src, size_t stride, const uint32_t *sizes, int n, uint64_t *offsets, uint8_t *dst,

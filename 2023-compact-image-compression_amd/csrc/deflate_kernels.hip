@@ -1,15 +1,19 @@
-// Device DEFLATE, byte-identical to zlib 1.2.11 `deflate(level 9, wbits 15, memLevel 8, default
-// strategy, one-shot Z_FINISH)` -- the stream CPython's zlib.compress(data, level=9) produces for
-// the reference (src/codec/core.py:340).  zlib is a third-party dependency of the reference and is
-// not vendored there; the algorithm is restated here in data-parallel form (CPU model of the same
-// restatement, pinned against libz: oracle/deflate_model.c).
+// Device DEFLATE, byte-identical to zlib 1.2.11 `deflate(level L, wbits 15, memLevel 8, default
+// strategy, one-shot Z_FINISH)` for L = 4 .. 9 -- level 9 is the stream CPython's zlib.compress(data,
+// level=9) produces for the reference (src/codec/core.py:340).  zlib is a third-party dependency of the
+// reference and is not vendored there; the algorithm is restated here in data-parallel form (CPU model
+// of the same restatement, pinned against libz: oracle/deflate_model.c for level 9,
+// tools/deflate_level_model.c for every level).  All six levels run deflate_slow, which inserts every
+// string into the hash chains; the level enters only through good / max_lazy / nice / max_chain
+// (DeflateArgs) in the match and decision kernels, and the second zlib header byte.
 //
 //   sort      stable two-pass LSD radix sort of (hash, position) per slice, the 15-bit rolling hash of 3 bytes
 //             (deflate.c UPDATE_HASH) computed on the fly: a bucket in position order IS zlib's hash chain
 //             (head/prev), walked backwards
 //   runs      ordered list of the runs of >= 3 equal bytes and, per position, the equal bytes ahead
-//   match     what longest_match() returns over the first 4096 / 1024 chain entries (max_chain, and
-//             max_chain>>2 once prev_length >= good_match), with the NIL / MAX_DIST / lookahead rules of
+//   match     what longest_match() returns over the first max_chain / max_chain>>2 chain entries ("full", and
+//             "quarter" once prev_length >= good_match), stopping at the first entry that reaches nice_match
+//             (capped by the lookahead), with the NIL / MAX_DIST / lookahead rules of
 //             deflate.c: one lane per position for short chains, one wave per position for long ones, and
 //             the run list instead of the chain for strings that start a run (their bucket holds every
 //             position of every run of that byte)
@@ -56,32 +60,32 @@ __constant__ uint16_t c_static_dcode[30];
 
 __device__ __forceinline__ int d_code(uint32_t dist) { return dist < 256 ? c_dist_code[dist] : c_dist_code[256 + (dist >> 7)]; }
 
-struct MatchRec { uint16_t len4096, len1024, dist4096, dist1024; };
+struct MatchRec { uint16_t len_full, len_quarter, dist_full, dist_quarter; };
 // Match records are only stored where there is something to say (a match of >= MIN_MATCH bytes): a record counts when it
 // carries the tag of the current pass -- 14 bits in the spare upper bits of the two length fields (lengths are <= 258), taken
 // from a device counter that dfl_offsets_kernel advances at the start of every pass (1 .. 16383; the host clears the buffer
 // before the counter would come round, api.cpp deflate_locked).  Writing a "no match" record for every position instead cost
 // 0.17 ms per batch (555 MB of stores), as much as the scattered stores it had saved in the match kernel.
 constexpr uint32_t GEN_MAX = 16383;
-__device__ __forceinline__ uint2 pack_match(uint32_t len4096, uint32_t len1024, uint32_t dist4096, uint32_t dist1024, uint32_t gen)
+__device__ __forceinline__ uint2 pack_match(uint32_t len_full, uint32_t len_quarter, uint32_t dist_full, uint32_t dist_quarter, uint32_t gen)
 {
-	return make_uint2((len4096 | ((gen & 127u) << 9)) | ((len1024 | ((gen >> 7) << 9)) << 16), dist4096 | (dist1024 << 16));
+	return make_uint2((len_full | ((gen & 127u) << 9)) | ((len_quarter | ((gen >> 7) << 9)) << 16), dist_full | (dist_quarter << 16));
 }
 // The record of position p as the parse reads it: the stored one if it carries this pass's tag; else "no match" -- or, deep
 // inside a run (in[p-1] == in[p] and at least max_len equal bytes ahead), the chain head p-1 at the cap, which nobody stores:
-// rw = run-length word of p (dfl_run_len_kernel).
+// rw = run-length word of p (dfl_run_len_kernel).  At every level the walk stops at that head: max_len >= nice_eff.
 __device__ __forceinline__ MatchRec checked_match(MatchRec r, uint32_t gen, uint32_t rw, uint32_t p, uint32_t L)
 {
-	const uint32_t tag = (uint32_t)(r.len4096 >> 9) | ((uint32_t)(r.len1024 >> 9) << 7);
+	const uint32_t tag = (uint32_t)(r.len_full >> 9) | ((uint32_t)(r.len_quarter >> 9) << 7);
 	const uint32_t lookahead = L - min(p, L);
 	const uint32_t max_len = lookahead < (uint32_t)MAX_MATCH ? lookahead : (uint32_t)MAX_MATCH;
 	const bool maximal = (rw >> 15) && (rw & 0x7FFFu) >= max_len && p + 2 < L;
 	MatchRec o;
 	const bool ok = tag == gen;
-	o.len4096 = ok ? (uint16_t)(r.len4096 & 511u) : (uint16_t)(maximal ? max_len : 0u);
-	o.len1024 = ok ? (uint16_t)(r.len1024 & 511u) : (uint16_t)(maximal ? max_len : 0u);
-	o.dist4096 = ok ? r.dist4096 : (uint16_t)(maximal ? 1u : 0u);
-	o.dist1024 = ok ? r.dist1024 : (uint16_t)(maximal ? 1u : 0u);
+	o.len_full = ok ? (uint16_t)(r.len_full & 511u) : (uint16_t)(maximal ? max_len : 0u);
+	o.len_quarter = ok ? (uint16_t)(r.len_quarter & 511u) : (uint16_t)(maximal ? max_len : 0u);
+	o.dist_full = ok ? r.dist_full : (uint16_t)(maximal ? 1u : 0u);
+	o.dist_quarter = ok ? r.dist_quarter : (uint16_t)(maximal ? 1u : 0u);
 	return o;
 }
 
@@ -280,7 +284,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 // Pass A: one lane per position walks at most LIGHT_STEPS candidates; positions whose chain is
 // longer ("heavy": long runs of one byte put tens of thousands of strings in one bucket) are queued.
 // Pass B: one WAVE per heavy position, 64 candidates per step.
-constexpr int LIGHT_STEPS = 12;
+constexpr int LIGHT_STEPS = 12;  // below max_chain at every level (16 .. 4096): the light walk never reaches the chain limit
 
 // Block -> (slice, part) for the kernels that touch one slice's arrays at random (hash order): match records
 // are scattered 8-byte stores and the string loads are scattered too, so they only stay on chip if the whole
@@ -457,13 +461,16 @@ __device__ __forceinline__ uint32_t rec_pos(uint64_t r, uint32_t pos_mask) { ret
 constexpr uint32_t COMPACT_POS_BITS = 22, COMPACT_POS_MASK = (1u << COMPACT_POS_BITS) - 1u;
 
 // longest_match over at most LIGHT_STEPS chain entries, strings read from the input (wide records, and the last seven positions
-// of a slice with compact ones).  kind: 0 = best/best_q hold the result, 1 = heavy (longer chain), 2 = starts a run (run_r).
+// of a slice with compact ones).  kind: 0 = best/best_q (full chain) and best1/best_q1 (the first `quarter` entries) hold the
+// result, 1 = heavy (longer chain), 2 = starts a run (run_r).
 __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const uint64_t *recs, const uint16_t *rl, uint32_t pos_mask,
-                                                        uint32_t L, uint32_t i, uint32_t p, uint32_t h,
-                                                        int &kind, int &best, uint32_t &best_q, uint32_t &run_r)
+                                                        uint32_t L, uint32_t i, uint32_t p, uint32_t h, uint32_t nice, int quarter,
+                                                        int &kind, int &best, uint32_t &best_q, int &best1, uint32_t &best_q1,
+                                                        uint32_t &run_r)
 {
 	const uint32_t lookahead = L - p;
 	const int max_len = lookahead < (uint32_t)MAX_MATCH ? (int)lookahead : MAX_MATCH;
+	const int nice_eff = (int)min(lookahead, nice);  // nice_match clamped to the lookahead (<= max_len)
 	const uint32_t nil_q = nil_candidate(p, lookahead);
 	int count = 0;
 	const uint8_t *sp = in + p;
@@ -479,7 +486,7 @@ __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const
 	if (in_run) {
 		const uint32_t rw = rl[p];
 		run_r = rw & 0x7FFFu;  // >= 3, <= max_len by construction
-		if ((rw >> 15) && (int)run_r >= max_len) { best = max_len; best_q = p - 1; }  // chain head p-1 is already maximal
+		if ((rw >> 15) && (int)run_r >= nice_eff) { best = best1 = (int)run_r; best_q = best_q1 = p - 1; }  // chain head p-1 yields r: the walk ends there
 		else kind = 2;
 		return;
 	}
@@ -492,7 +499,7 @@ __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const
 		if (q == 0 || q == nil_q) break;                         // NIL ends the chain
 		if (count == 0 ? dist > (uint32_t)MAX_DIST : dist >= (uint32_t)MAX_DIST) break;
 		const uint8_t *mp = in + q;
-		if (best < max_len) {                                    // only a longer match can replace the best
+		{                                                        // (best < nice_eff here: the walk ends when it is reached)
 			int len = 0;
 			if (wide) {  // one 8-byte load decides most candidates (the loads of mp are the uncoalesced ones)
 				if (best < 8 || mp[best] == sp[best]) {
@@ -502,10 +509,13 @@ __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const
 					len = d ? (__ffsll((long long)d) - 1) >> 3 : common_prefix(mp, sp, 8, max_len);
 				}
 			} else if (mp[best] == sp[best]) len = common_prefix(mp, sp, 0, max_len);
-			if (len > best) { best = len; best_q = q; }
+			if (len > best) {
+				best = len; best_q = q;
+				if (count < quarter) { best1 = len; best_q1 = q; }  // still inside the first max_chain >> 2 entries
+			}
 		}
 		count++;
-		if (best >= max_len) break;                              // len >= nice_match
+		if (best >= nice_eff) break;                             // len >= nice_match: the first such entry ends the walk
 	}
 }
 
@@ -515,7 +525,9 @@ __device__ __forceinline__ uint32_t wave_shift_up(uint32_t v, uint32_t fill)
 	return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
 }
 
-template <bool CMP>
+// QL: the quarter chain (max_chain >> 2) ends inside the light walk (levels 4 and 5), so the lane records it on its own;
+// otherwise the light walk never gets past it and the quarter record is the full one.
+template <bool CMP, bool QL>
 __global__ void dfl_match_kernel(DeflateArgs a, int n)
 {
 	int s; uint32_t part, nparts;
@@ -531,12 +543,13 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 	const int lane = threadIdx.x & 63;
 	const uint64_t lt_mask = (1ull << lane) - 1ull;
 	const uint32_t gen = *a.gen;
+	const int quarter = QL ? (int)(a.max_chain >> 2) : LIGHT_STEPS + 1;
 	for (uint32_t i0 = part * blockDim.x; i0 < npos; i0 += nparts * blockDim.x) {  // wave-uniform trip count
 		const uint32_t i = i0 + threadIdx.x;
 		const bool valid = i < npos;
 		int kind = 0;  // 0: record written, 1: queue for the cooperative heavy pass, 2: queue for the run pass
-		int best = 0;
-		uint32_t best_q = 0, run_r = 0;
+		int best = 0, best1 = 0;
+		uint32_t best_q = 0, best_q1 = 0, run_r = 0;
 		const uint64_t ri = recs[min(i, npos - 1)];
 		const uint32_t p = rec_pos(ri, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu);
 		const uint32_t h = rec_hash(ri);
@@ -550,6 +563,7 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 			const uint32_t lo_i = (uint32_t)ri, hi_i = (uint32_t)(ri >> 32), lo_b = (uint32_t)rb, hi_b = (uint32_t)(rb >> 32);
 			const uint32_t lookahead = L - p;
 			const int max_len = lookahead < (uint32_t)MAX_MATCH ? (int)lookahead : MAX_MATCH;
+			const int nice_eff = (int)min(lookahead, a.nice);  // nice_match clamped to the lookahead (<= max_len)
 			const bool fast = valid && p + 8 <= L;  // max_len >= 8; the compact fields of the record are those of the string
 			from_memory = valid && !fast;
 			const uint32_t nil_q = nil_candidate(p, lookahead);
@@ -558,7 +572,9 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 			if (fast && in_run) {  // the record carries the run-length word in place of bytes 3 and 4
 				const uint32_t rw = (hi_i >> 15) & 0xFFFFu;
 				run_r = rw & 0x7FFFu;
-				if (!((rw >> 15) && (int)run_r >= max_len)) kind = 2;  // else: chain head p-1 at the cap, which the parse knows from the run-length word (checked_match)
+				if (!((rw >> 15) && (int)run_r >= nice_eff)) kind = 2;
+				else if ((int)run_r < max_len) { best = best1 = (int)run_r; best_q = best_q1 = p - 1; found = true; }  // chain head p-1 reaches nice
+				// (else: chain head p-1 at the cap, which the parse knows from the run-length word, checked_match)
 			}
 			bool act = fast && !in_run;
 			// NIL (position 0, and the slide_hash quirk, which sits at distance MAX_DIST exactly) and the window as one bound on the
@@ -581,25 +597,30 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 					if (k == LIGHT_STEPS + 1) { kind = 1; act = false; }  // a 13th entry: heavy
 					else {
 						// three bytes in common (less never counts): then x holds the differences of bytes 3 and 4 only
-						if (best < max_len && (((lo_i ^ clo) >> 22) | (x >> 31)) == 0) {
+						if (best < nice_eff && (((lo_i ^ clo) >> 22) | (x >> 31)) == 0) {
 							int len;
 							if (x & 0x007F8000u) len = 3;
 							else if (x) len = 4;
 							else if (best < 5 || in[q + best] == in[p + best]) len = common_prefix(in + q, in + p, 5, max_len);
 							else len = 0;
-							if (len > best) { best = len; best_q = q; found = true; }
+							if (len > best) {
+								best = len; best_q = q; found = true;
+								if (QL && k <= quarter) { best1 = len; best_q1 = q; }
+							}
 						}
-						if (best >= max_len) act = false;  // len >= nice_match
+						if (best >= nice_eff) act = false;  // len >= nice_match: the first such entry ends the walk
 					}
 				}
 			}
 		}
 		if (from_memory) {
-			light_match_from_memory(in, recs, rl, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu, L, i, p, h, kind, best, best_q, run_r);
+			light_match_from_memory(in, recs, rl, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu, L, i, p, h, a.nice, quarter, kind, best, best_q,
+			                        best1, best_q1, run_r);
 			found = kind == 0 && best >= MIN_MATCH;
 		}
 		if (found && kind == 0) {  // shorter than MIN_MATCH never counts (match_of); queued positions are written by their kernels
-			mr[p] = pack_match((uint32_t)best, (uint32_t)best, p - best_q, p - best_q, gen);
+			if (!QL) { best1 = best; best_q1 = best_q; }
+			mr[p] = pack_match((uint32_t)best, (uint32_t)best1, p - best_q, best1 ? p - best_q1 : 0u, gen);
 		}
 		// wave-aggregated appends: one atomic per wave and list
 		const uint64_t bh = __ballot(kind == 1), br = __ballot(kind == 2);
@@ -614,27 +635,44 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 	}
 }
 
-// Wave-cooperative longest_match for one position whose chain is long: 64 candidates per step.
-// Returns the packed MatchRec (lo = len4096 | len1024 << 16, hi = dist4096 | dist1024 << 16), wave-uniform.
+// Wave-cooperative longest_match for one position whose chain is long: 64 candidates per step, at most max_chain in all.
+// Returns the packed MatchRec (lo = len_full | len_quarter << 16, hi = dist_full | dist_quarter << 16), wave-uniform.
+// In chain order the walk ends at the first entry whose length reaches nice_eff, so in a step that is the lowest such lane and
+// no later lane counts; the quarter walk is the prefix of the first max_chain >> 2 entries (4, 8, 32 of them at levels 4 to 6:
+// inside the first step).
 __device__ __forceinline__ void coop_longest_match(const uint8_t *in, const uint64_t *recs, uint32_t L,
-                                                   uint32_t i, uint32_t p, uint32_t pos_mask, int lane, uint32_t &lo, uint32_t &hi)
+                                                   uint32_t i, uint32_t p, uint32_t pos_mask, int lane, uint32_t nice, uint32_t max_chain,
+                                                   uint32_t &lo, uint32_t &hi)
 {
 	const uint32_t h = rec_hash(recs[i]);
 	const uint32_t lookahead = L - p;
 	const int max_len = lookahead < (uint32_t)MAX_MATCH ? (int)lookahead : MAX_MATCH;
+	const int nice_eff = (int)min(lookahead, nice);  // nice_match clamped to the lookahead (<= max_len)
+	const uint32_t quarter = max_chain >> 2;
+	const int steps = (int)((max_chain + 63) >> 6);
 	const uint32_t nil_q = nil_candidate(p, lookahead);
 	const uint8_t *sp = in + p;
 	int best = 0;
 	uint32_t best_q = 0;
-	int len1024 = -1;
-	uint32_t q1024 = 0;
+	int len_q = -1;
+	uint32_t q_q = 0;
+	// longest length among the lanes of `cand`, earliest candidate (lowest lane) that reaches it
+	auto pick = [&](uint64_t cand, int len, uint32_t q, int &b_len, uint32_t &b_q) {
+		for (int b = 8; b >= 0; b--) {
+			const uint64_t mb = __ballot((len >> b) & 1) & cand;
+			if (mb) cand = mb;
+		}
+		const int win = __builtin_amdgcn_readfirstlane(__ffsll((long long)cand) - 1);
+		b_len = __builtin_amdgcn_readlane(len, win);
+		b_q = (uint32_t)__builtin_amdgcn_readlane((int)q, win);
+	};
 	auto rec_of_round = [&](int r) { const int64_t j = (int64_t)i - 1 - (int64_t)(r * 64 + lane); return recs[j >= 0 ? j : 0]; };
 	uint64_t rj_next = rec_of_round(0);
-	for (int r = 0; r < 64; r++) {  // 64 x 64 = max_chain_length 4096 candidates
+	for (int r = 0; r < steps; r++) {
 		const int64_t j = (int64_t)i - 1 - (int64_t)(r * 64 + lane);
 		const uint64_t rj = j >= 0 ? rj_next : ~0ull;
 		rj_next = rec_of_round(r + 1);  // (requested before this round's strings are compared)
-		const bool in_chain = j >= 0 && rec_hash(rj) == h;
+		const bool in_chain = j >= 0 && rec_hash(rj) == h && (uint32_t)(r * 64 + lane) < max_chain;
 		const uint32_t q = in_chain ? rec_pos(rj, pos_mask) : 0u;
 		const uint32_t dist = p - q;
 		const bool term = !in_chain || q == 0 || q == nil_q ||
@@ -642,27 +680,28 @@ __device__ __forceinline__ void coop_longest_match(const uint8_t *in, const uint
 		const uint64_t tmask = __ballot(term);
 		const int nvalid = tmask ? (__ffsll((long long)tmask) - 1) : 64;
 		int len = 0;
-		if (lane < nvalid && best < max_len) {
+		if (lane < nvalid) {  // (best < nice_eff here: the walk ends when it is reached)
 			const uint8_t *mp = in + q;
 			if (mp[best] == sp[best]) len = common_prefix(mp, sp, 0, max_len);
 		}
-		// longest length in this step, earliest candidate (lowest lane) that reaches it
-		uint64_t cand = __ballot(len > best);
-		if (cand) {
-			for (int b = 8; b >= 0; b--) {
-				const uint64_t mb = __ballot((len >> b) & 1) & cand;
-				if (mb) cand = mb;
-			}
-			const int win = __builtin_amdgcn_readfirstlane(__ffsll((long long)cand) - 1);
-			best = __builtin_amdgcn_readlane(len, win);
-			best_q = (uint32_t)__builtin_amdgcn_readlane((int)q, win);
+		const uint64_t nice_m = __ballot(len >= nice_eff);
+		const uint64_t upto = nice_m ? ((nice_m & (0 - nice_m)) << 1) - 1u : ~0ull;  // lanes up to the first that reaches nice
+		const int best_before = best;
+		const uint32_t best_q_before = best_q;
+		const uint64_t cand = __ballot(len > best_before) & upto;
+		if (cand) pick(cand, len, q, best, best_q);
+		const uint32_t qb = quarter - (uint32_t)(r * 64);  // the quarter walk ends inside this step, after lane qb - 1
+		if ((uint32_t)(r * 64) < quarter && qb <= 64u) {
+			const uint64_t cq = cand & (qb == 64u ? ~0ull : (1ull << qb) - 1u);
+			if (cq == cand) { len_q = best; q_q = best_q; }
+			else if (cq) pick(cq, len, q, len_q, q_q);
+			else { len_q = best_before; q_q = best_q_before; }
 		}
-		if (r == 15 && nvalid == 64) { len1024 = best; q1024 = best_q; }  // after exactly 1024 candidates
-		if (best >= max_len || nvalid < 64) break;
+		if (nice_m || nvalid < 64) break;
 	}
-	if (len1024 < 0) { len1024 = best; q1024 = best_q; }
-	lo = (uint32_t)best | ((uint32_t)len1024 << 16);
-	hi = (best ? p - best_q : 0u) | ((len1024 ? p - q1024 : 0u) << 16);
+	if (len_q < 0) { len_q = best; q_q = best_q; }
+	lo = (uint32_t)best | ((uint32_t)len_q << 16);
+	hi = (best ? p - best_q : 0u) | ((len_q ? p - q_q : 0u) << 16);
 }
 
 __global__ void __launch_bounds__(256) dfl_match_heavy_kernel(DeflateArgs a, int n)
@@ -682,7 +721,7 @@ __global__ void __launch_bounds__(256) dfl_match_heavy_kernel(DeflateArgs a, int
 		const uint32_t i = heavy[e];
 		const uint32_t p = rec_pos(recs[i], a.pos_mask);
 		uint32_t lo, hi;
-		coop_longest_match(in, recs, L, i, p, a.pos_mask, lane, lo, hi);
+		coop_longest_match(in, recs, L, i, p, a.pos_mask, lane, a.nice, a.max_chain, lo, hi);
 		if (lane == 0) mr[p] = pack_match(lo & 0xFFFFu, lo >> 16, hi & 0xFFFFu, hi >> 16, gen);
 	}
 }
@@ -690,7 +729,7 @@ __global__ void __launch_bounds__(256) dfl_match_heavy_kernel(DeflateArgs a, int
 // ------------------------------------------------------------------ 2c. positions deep inside a run of one byte
 // For p with in[p-3..p+2] all equal to b and r further b's ahead (r < max_len), the chain head is p-1
 // and yields exactly r.  Only a candidate q that is r bytes before the END of an earlier run of b,
-// followed by the same byte c = in[p+r], can be longer.  So instead of 4096 chain steps the lane scans
+// followed by the same byte c = in[p+r], can be longer.  So instead of max_chain chain steps the lane scans
 // the (much shorter) list of run ends backwards.  Chain-length limits translate into position limits
 // through the sorted order: the first K chain entries are the sorted indices i-1 .. i-K.
 // Ordered lists of the ends AND starts of runs of >= 3 equal bytes, per slice, from the run-length words: position p puts
@@ -784,8 +823,12 @@ __global__ void __launch_bounds__(256) dfl_run_info_kernel(DeflateArgs a)
 //     follows both runs when e_j - q == r; descending q inside a run, the first position reaching the run's
 //     maximum is q = e_j - r (run long enough) or the lowest position still inside the chain limits.
 // So the lane scans run ends backwards, one O(1) step per run.  The limits of deflate.c become position
-// limits: the first K chain entries are the sorted indices i-1 .. i-K (K = 4096, and 1024 for the
-// good_match variant); distance < MAX_DIST; position 0 is NIL.
+// limits: the first K chain entries are the sorted indices i-1 .. i-K (K = max_chain, and max_chain >> 2
+// for the good_match variant); distance < MAX_DIST; position 0 is NIL.
+// nice_match: inside a run the candidates come as d = e_j - q = 3, 4, ...; the walk ends at the first that
+// reaches nice_eff.  When nice_eff < r that is q = e_j - nice_eff with length exactly nice_eff, before the
+// longer extension at q = e_j - r is seen: a run is counted down to k = min(r, nice_eff) bytes at most
+// (proved against the chain walk in tools/deflate_level_model.c, run_rule).
 __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n)
 {
 	int s; uint32_t part, nparts;
@@ -801,17 +844,20 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 	const uint32_t *rl = re + (a.in_stride >> 1);
 	const uint32_t nre = a.run_end_count[s];
 	const uint32_t gen = *a.gen;
+	const uint32_t quarter = a.max_chain >> 2;
 	for (uint32_t e = part * blockDim.x + threadIdx.x; e < ndeep; e += nparts * blockDim.x) {
 		const uint32_t i = *(deep - e);
 		// the four records a position can need depend on its sorted index only: requested together (clamped, not tested)
 		const uint64_t ri = recs[i];
-		const uint64_t r_head = recs[i >= 1 ? i - 1 : 0], r_1024 = recs[i >= 1024 ? i - 1024 : 0], r_4096 = recs[i >= 4096 ? i - 4096 : 0];
+		const uint64_t r_head = recs[i >= 1 ? i - 1 : 0], r_quarter = recs[i >= quarter ? i - quarter : 0], r_full = recs[i >= a.max_chain ? i - a.max_chain : 0];
 		const uint32_t p = rec_pos(ri, a.pos_mask);
 		const uint32_t h = rec_hash(ri);
 		const uint32_t lookahead = L - p;
 		const uint32_t max_len = lookahead < (uint32_t)MAX_MATCH ? lookahead : (uint32_t)MAX_MATCH;
+		const uint32_t nice_eff = min(lookahead, a.nice);  // nice_match clamped to the lookahead (<= max_len)
 		const uint8_t b = in[p], b_prev = in[p >= 1 ? p - 1 : 0];
 		const uint32_t r = a.run_len[base + p] & 0x7FFFu;  // run length from p, capped at max_len
+		const uint32_t k = min(r, nice_eff);               // bytes of an earlier run that can count
 		const bool has_prev = p >= 2 && b_prev == b;  // position 0 is NIL
 		uint32_t best4 = has_prev ? r : 0u, q4 = p - 1, best1 = best4, q1 = p - 1;
 		bool scan = true;
@@ -827,13 +873,13 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 				scan = false;
 			}
 		}
-		if (scan && best4 < max_len) {
+		if (scan && best4 < nice_eff) {
 			const bool ext_ok = r < max_len;  // bytes after the run can only matter below the cap
 			const uint8_t c = ext_ok ? in[p + r] : 0;
 			const uint32_t qw = p >= (uint32_t)MAX_DIST ? p - (uint32_t)MAX_DIST + 1 : 1u;  // dist < MAX_DIST, q != NIL
 			uint32_t qmin4 = qw, qmin1 = qw;
-			if (i >= 4096 && rec_hash(r_4096) == h) qmin4 = max(qmin4, rec_pos(r_4096, a.pos_mask));
-			if (i >= 1024 && rec_hash(r_1024) == h) qmin1 = max(qmin1, rec_pos(r_1024, a.pos_mask));
+			if (i >= a.max_chain && rec_hash(r_full) == h) qmin4 = max(qmin4, rec_pos(r_full, a.pos_mask));
+			if (i >= quarter && rec_hash(r_quarter) == h) qmin1 = max(qmin1, rec_pos(r_quarter, a.pos_mask));
 			// number of run ends <= p (none lies strictly inside p's own run): an end x comes from position x - 3, so these are the
 			// entries of the positions below p - 2 -- the rank table gives those below the 8-aligned part, the rest is a step or two
 			uint32_t lo = 0;
@@ -847,9 +893,9 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 				const uint32_t x = x_n;
 				const uint32_t lw = lw_n;          // min(run length, 511) | run byte << 16
 				{ const int64_t tn = t > 0 ? t - 1 : 0; x_n = re[tn]; lw_n = rl[tn]; }
-				if (x < qmin4 + 3) break;          // even q = x-3 is outside the first 4096 entries / the window
+				if (x < qmin4 + 3) break;          // even q = x-3 is outside the first max_chain entries / the window
 				if ((lw >> 16) != b) continue;     // a run of another byte
-				const uint32_t m = min(min(lw & 0xFFFFu, r), x - qmin4);  // run length counted down to qmin4, capped at r
+				const uint32_t m = min(min(lw & 0xFFFFu, k), x - qmin4);  // run length counted down to qmin4, capped at k
 				if (m >= 3) {
 					uint32_t q, len;
 					if (m == r) {
@@ -857,13 +903,13 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 						if (ext_ok && in[x] == c) len = (uint32_t)common_prefix(in + q, in + p, (int)r + 1, (int)max_len);
 					} else { q = x - m; len = m; }
 					if (len > best4) { best4 = len; q4 = q; }
-					// the same run seen through the 1024-entry limit
+					// the same run seen through the quarter limit
 					if (x >= qmin1 + 3) {
 						const uint32_t m1 = min(m, x - qmin1);
 						if (m1 == m) { if (len > best1) { best1 = len; q1 = q; } }
 						else if (m1 >= 3 && m1 > best1) { best1 = m1; q1 = x - m1; }
 					}
-					if (best4 >= max_len) break;
+					if (best4 >= nice_eff) break;
 				}
 				if (x - m <= qmin4) break;  // the run was cut by the limit: older runs are outside
 			}
@@ -874,21 +920,23 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 
 // ------------------------------------------------------------------ 3a. decision records + block summaries
 // rec32: bits 0..7 k (deferred literals), 8..16 match length (0 = none), 17..31 distance
-__device__ __forceinline__ void match_of(const MatchRec &r, uint32_t p, uint32_t npos, int prev_len, int &len, int &dist)
+// lazy = max_lazy_match, good = good_match of the level
+__device__ __forceinline__ void match_of(const MatchRec &r, uint32_t p, uint32_t npos, int prev_len, int lazy, int good, int &len, int &dist)
 {
 	// deflate_slow: match_length after longest_match + TOO_FAR rule, given prev_length (deflate.c:1863-1880); r = record of p
 	len = 2; dist = 0;
-	if (p >= npos || prev_len >= MAX_MATCH) return;
-	const int l = prev_len >= 32 ? r.len1024 : r.len4096;
-	const int d = prev_len >= 32 ? r.dist1024 : r.dist4096;
+	if (p >= npos || prev_len >= lazy) return;
+	const int l = prev_len >= good ? r.len_quarter : r.len_full;
+	const int d = prev_len >= good ? r.dist_quarter : r.dist_full;
 	if (l > prev_len && l >= MIN_MATCH) { len = l; dist = d; }
 	if (len == MIN_MATCH && dist > TOO_FAR) len = 2;
 }
-__device__ __forceinline__ void match_at(const MatchRec *mr, const uint16_t *rl, uint32_t gen, uint32_t p, uint32_t npos, int prev_len, int &len, int &dist)
+__device__ __forceinline__ void match_at(const MatchRec *mr, const uint16_t *rl, uint32_t gen, uint32_t p, uint32_t npos, int prev_len,
+                                         int lazy, int good, int &len, int &dist)
 {
 	len = 2; dist = 0;
-	if (p >= npos || prev_len >= MAX_MATCH) return;
-	match_of(checked_match(mr[p], gen, rl[p], p, npos + 2), p, npos, prev_len, len, dist);
+	if (p >= npos || prev_len >= lazy) return;
+	match_of(checked_match(mr[p], gen, rl[p], p, npos + 2), p, npos, prev_len, lazy, good, len, dist);
 }
 
 __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
@@ -902,6 +950,7 @@ __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
 	const uint32_t nblk64 = (L + 63) / 64;
 	const int lane = threadIdx.x & 63;
 	const uint32_t gen = *a.gen;
+	const int lazy = (int)a.max_lazy, good = (int)a.good;
 	// the lane's own record and its right neighbour's (what the first deferral test reads) are requested together and without a
 	// branch (a load inside a conditional is waited for on the spot, which made them two round trips in a row), one turn ahead
 	const uint32_t lastp = npos ? npos - 1 : 0;
@@ -923,14 +972,14 @@ __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
 		const MatchRec r0 = checked_match(cq.m0, gen, cq.w0, pa, L), r1 = checked_match(cq.m1, gen, cq.w1, pb, L);
 		if (p < L) {
 			int len, dist;
-			match_of(r0, p, npos, 2, len, dist);
+			match_of(r0, p, npos, 2, lazy, good, len, dist);
 			if (len < MIN_MATCH) { rec = 0; nxt = p + 1; cnt = 1; }  // literal in[p]
 			else {
 				uint32_t k = 0;
 				for (;;) {  // lazy evaluation: defer while the next position has a longer match
 					int l2, d2;
-					if (k == 0) match_of(r1, p + 1, npos, len, l2, d2);
-					else match_at(mr, rl, gen, p + k + 1, npos, len, l2, d2);
+					if (k == 0) match_of(r1, p + 1, npos, len, lazy, good, l2, d2);
+					else match_at(mr, rl, gen, p + k + 1, npos, len, lazy, good, l2, d2);
 					if (l2 > len) { len = l2; dist = d2; k++; } else break;
 				}
 				rec = k | ((uint32_t)len << 8) | ((uint32_t)dist << 17);
@@ -1751,7 +1800,7 @@ __global__ void dfl_layout_kernel(DeflateArgs a, int n)
 	if (s >= n) return;
 	uint8_t *out = a.out + (size_t)s * a.out_stride;
 	for (int i = 0; i < 13; i++) out[i] = a.header13[i];
-	out[13] = 0x78; out[14] = 0xDA;  // CMF/FLG for wbits 15, level 9 (deflate.c:819-836)
+	out[13] = 0x78; out[14] = (uint8_t)a.zlib_flg;  // CMF/FLG for wbits 15 and the level (deflate.c:819-836)
 	uint64_t bit = 8ull * 15;
 	BlockMeta *meta = a.block_meta + (size_t)s * a.max_blocks;
 	const uint32_t nb = a.n_blocks[s];
@@ -1962,6 +2011,19 @@ __global__ void dfl_offsets_kernel(DeflateArgs a, int n)
 
 }  // namespace
 
+// deflate.c configuration_table (the deflate_slow levels) and the zlib header's level_flags
+bool deflate_level_args(int level, DeflateArgs &a)
+{
+	static const uint32_t T[6][5] = {
+		{4, 4, 16, 16, 0x5E}, {8, 16, 32, 32, 0x5E}, {8, 16, 128, 128, 0x9C},
+		{8, 32, 128, 256, 0xDA}, {32, 128, 258, 1024, 0xDA}, {32, 258, 258, 4096, 0xDA},
+	};
+	if (level < 4 || level > 9) return false;
+	const uint32_t *t = T[level - 4];
+	a.good = t[0]; a.max_lazy = t[1]; a.nice = t[2]; a.max_chain = t[3]; a.zlib_flg = t[4];
+	return true;
+}
+
 // host: trees.c tr_static_init tables -> constant memory
 hipError_t deflate_init_tables()
 {
@@ -2046,9 +2108,15 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 	// (486 us against 499 / 510 with 128 / 512, profiles/r03_match_grid.log)
 	const int gm_cap = a.pos_mask == COMPACT_POS_MASK ? 256 : 2048;
 	const int gm = (int)std::min<size_t>(gm_cap, (a.in_stride + 255) / 256), n8 = (n + 7) & ~7;  // see xcd_slice()
-	if (a.pos_mask == COMPACT_POS_MASK) hipLaunchKernelGGL(dfl_match_kernel<true>, dim3(gm, n8), dim3(256), 0, st, a, n);
-	else if (a.pos_mask == 0xFFFFFFFFu) hipLaunchKernelGGL(dfl_match_kernel<false>, dim3(gm, n8), dim3(256), 0, st, a, n);
-	else return hipErrorInvalidValue;
+	if (a.max_chain < 16 || a.max_chain > 4096 || a.nice < 16 || a.nice > (uint32_t)MAX_MATCH) return hipErrorInvalidValue;  // levels 4 .. 9
+	const bool ql = (a.max_chain >> 2) <= (uint32_t)LIGHT_STEPS;  // the quarter chain ends inside the light walk
+	if (a.pos_mask == COMPACT_POS_MASK) {
+		if (ql) hipLaunchKernelGGL((dfl_match_kernel<true, true>), dim3(gm, n8), dim3(256), 0, st, a, n);
+		else hipLaunchKernelGGL((dfl_match_kernel<true, false>), dim3(gm, n8), dim3(256), 0, st, a, n);
+	} else if (a.pos_mask == 0xFFFFFFFFu) {
+		if (ql) hipLaunchKernelGGL((dfl_match_kernel<false, true>), dim3(gm, n8), dim3(256), 0, st, a, n);
+		else hipLaunchKernelGGL((dfl_match_kernel<false, false>), dim3(gm, n8), dim3(256), 0, st, a, n);
+	} else return hipErrorInvalidValue;
 	if (fork) {  // both have what the other produced: the run matcher the run lists, the heavy matcher the queue of long chains
 		if ((e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
 		if ((e = hipEventRecord(ev[2], s2)) != hipSuccess) return e;

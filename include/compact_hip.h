@@ -68,6 +68,12 @@ extern "C" {
 #define CCT_FLAG_DEFLATE 4u       /* deflate_compression     (core.py:337) */
 #define CCT_FLAG_SIGNED_SEG 8u    /* caller's array dtype is int16: segmentation sees signed
                                      values (core.py:254 image.flatten().tolist()) */
+/* zlib level of the DEFLATE stage (config['encoder']['deflate_level'], an extension of the reference):
+ * field 0 = level 9 (what the reference writes, and every caller that leaves the field clear),
+ * 4 .. 9 = that level; 1 .. 3 and 10 .. 15 are refused with CCT_E_ARG.  The level shows only in the
+ * second zlib header byte; the 13-byte .cct header is the same and zlib.decompress reads any level. */
+#define CCT_FLAG_LEVEL_MASK 0xF00u
+#define CCT_FLAG_DEFLATE_LEVEL(l) ((((uint32_t)(l)) & 15u) << 8)
 
 /* per-slice status bits written by the device kernels (0 = clean) */
 #define CCT_ST_Q7 1u         /* encode: a traversal delta outside [-2047,2048] was emitted; the
@@ -173,6 +179,12 @@ int cct_encode_batch_packed(const uint16_t *images, int images_on_device, int n,
 int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n,
                             uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 
+/* cct_zlib_compress_batch at zlib level 4 .. 9 (compress2(level)), or -1 for 6 (Z_DEFAULT_COMPRESSION,
+ * what zlib.compress(data) uses).  Levels 0 to 3 (deflate_stored / deflate_fast) are not on the device:
+ * any level outside -1, 4 .. 9 returns CCT_E_ARG before the device is touched. */
+int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level,
+                                  uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+
 /* INFLATE stage alone, on the device: n zlib streams (h_in[h_offsets[i] .. h_offsets[i+1])) -> the bytes
  * zlib.decompress returns for each (what the reference calls at core.py:421).  Output i lands at
  * h_out + i*out_stride (out_stride a multiple of 16); h_status[i] = CCT_OK, CCT_E_ZLIB (anything libz
@@ -232,7 +244,8 @@ int cct_packbits_decode_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per
  * thread: an encode and a decode driven from two threads do not overwrite each other; takes no lock):
  * [0] encode kernel (HIP events on the library stream), [1] packed files device -> host, [2] DEFLATE (HIP events
- * on the device path, host wall on the libz path), [3] INFLATE (likewise), [4] decode kernel (HIP events),
+ * on the device path, also after cct_zlib_compress_batch / _level; host wall on the libz path), [3] INFLATE
+ * (likewise), [4] decode kernel (HIP events),
  * [5] reserved. */
 int cct_last_timings(float *out6);
 /* Options: "encode_slots" / "decode_slots" (1 or 2 batches on the device at a time), "device_deflate" / "device_inflate"

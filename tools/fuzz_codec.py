@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Fuzz run (not part of the product): random byte strings with many different statistics through the device
-DEFLATE (must equal zlib.compress(x, 9) byte for byte) and through the device INFLATE (streams written by zlib
-with random level / strategy / window / flush points must inflate to the input).
-Usage: python tools/fuzz_codec.py [rounds] [seed]"""
+DEFLATE (must equal zlib.compress(x, level) byte for byte, level 9 unless --levels names others) and through the
+device INFLATE (streams written by zlib with random level / strategy / window / flush points must inflate to the input).
+Usage: python tools/fuzz_codec.py [rounds] [seed] [--levels 4,5,6,7,8,9]"""
+import argparse
 import os
 import sys
 import time
@@ -75,18 +76,24 @@ def stream(rng, b):
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    ap = argparse.ArgumentParser()
+    ap.add_argument("rounds", nargs="?", type=int, default=20)
+    ap.add_argument("seed", nargs="?", type=int, default=1)
+    ap.add_argument("--levels", default="9", help="comma-separated zlib levels of the device DEFLATE (-1, 4 to 9)")
+    args = ap.parse_args()
+    rounds, seed = args.rounds, args.seed
+    levels = [int(x) for x in args.levels.split(",")]
     rng = np.random.default_rng(seed)
     t0, nbad = time.time(), 0
     for r in range(rounds):
         blobs = [blob(rng) for _ in range(int(rng.integers(1, 48)))]
-        got = cct_hip.zlib_compress_batch(blobs)
-        for i, (b, g) in enumerate(zip(blobs, got)):
-            if g != zlib.compress(b, 9):
-                nbad += 1
-                open(f"/tmp/fuzz_deflate_{seed}_{r}_{i}.bin", "wb").write(b)
-                print(f"DEFLATE MISMATCH round {r} blob {i} len {len(b)}", flush=True)
+        for level in levels:
+            got = cct_hip.zlib_compress_batch(blobs, level=level)
+            for i, (b, g) in enumerate(zip(blobs, got)):
+                if g != zlib.compress(b, level):
+                    nbad += 1
+                    open(f"/tmp/fuzz_deflate_{seed}_{r}_{i}_l{level}.bin", "wb").write(b)
+                    print(f"DEFLATE MISMATCH round {r} blob {i} len {len(b)} level {level}", flush=True)
         streams = [stream(rng, b) for b in blobs]
         outs = cct_hip.zlib_decompress_batch(streams, max_out=max(16, max(len(b) for b in blobs)))
         for i, (b, o) in enumerate(zip(blobs, outs)):
