@@ -19,6 +19,14 @@ FLAG_LEVEL_MASK = 0xF00
 def flag_deflate_level(level):
     """CCT_FLAG_DEFLATE_LEVEL(level): the zlib level field of the encoder flags (0 = level 9)."""
     return (int(level) & 15) << 8
+
+
+FLAG_STRATEGY_MASK = 0x7000
+
+
+def flag_deflate_strategy(strategy):
+    """CCT_FLAG_DEFLATE_STRATEGY(strategy): the zlib strategy field of the encoder flags (0 = Z_DEFAULT_STRATEGY)."""
+    return (int(strategy) & 7) << 12
 ST_Q7, ST_CAP, ST_OVERFLOW, ST_STREAM = 1, 2, 4, 8
 ROLE_PARTNER = 0xFF
 
@@ -74,6 +82,8 @@ _SIGS = {
     "cct_zlib_compress_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cct_zlib_compress_batch_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                 C.c_void_p]),
+    "cct_zlib_compress_batch_strategy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p]),
     "cct_zlib_decompress_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "cct_read_header": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.POINTER(Header)]),
     "cct_decode_payload_dev": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

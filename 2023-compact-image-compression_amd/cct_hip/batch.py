@@ -25,27 +25,60 @@ def magic_bytes(config):
     return b[-4:].rjust(4, b"\0")
 
 
-def deflate_level(config):
-    """config['encoder']['deflate_level'] -> zlib level of the DEFLATE stage: absent -> 9 (what the reference writes),
-    -1 -> 6 (Z_DEFAULT_COMPRESSION), 4 .. 9 as given.  Levels 0 to 3 run deflate_stored / deflate_fast, which the
-    device does not implement: ValueError, as for anything else."""
-    level = config["encoder"].get("deflate_level")
-    if level is None:
-        return 9
+Z_HUFFMAN_ONLY, Z_RLE = 2, 3  # zlib strategies that run deflate_huff / deflate_rle, which read no level table
+
+
+def _check_strategy(strategy):
+    """zlib strategy 0 .. 4 (Z_DEFAULT_STRATEGY, Z_FILTERED, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED) or ValueError"""
+    if isinstance(strategy, bool) or not isinstance(strategy, (int, np.integer)):
+        raise ValueError(f"deflate strategy must be an integer (zlib's Z_* constants), got {strategy!r}")
+    strategy = int(strategy)
+    if not 0 <= strategy <= 4:
+        raise ValueError(f"deflate strategy {strategy}: zlib strategies are 0 to 4 (Z_DEFAULT_STRATEGY to Z_FIXED)")
+    return strategy
+
+
+def _check_level(level, strategy):
+    """zlib level of (level, strategy) on the device: -1 -> 6; 4 .. 9; also 1 .. 3 under Z_HUFFMAN_ONLY / Z_RLE"""
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
         raise ValueError(f"deflate_level must be an integer, got {level!r}")
     level = int(level)
     if level == -1:
         return 6
-    if not 4 <= level <= 9:
-        raise ValueError(f"deflate_level {level}: supported levels are -1 and 4 to 9 "
+    if strategy in (Z_HUFFMAN_ONLY, Z_RLE):
+        if not 1 <= level <= 9:
+            raise ValueError(f"deflate level {level} with strategy {strategy}: supported levels are -1 and 1 to 9 "
+                             "(0 is deflate_stored, not on the device)")
+    elif not 4 <= level <= 9:
+        raise ValueError(f"deflate level {level} with strategy {strategy}: supported levels are -1 and 4 to 9 "
                          "(0 to 3 are deflate_stored / deflate_fast, not on the device)")
     return level
 
 
+def deflate_strategy(config):
+    """config['encoder']['deflate_strategy'] -> zlib strategy of the DEFLATE stage, zlib's integer constants: absent -> 0
+    (Z_DEFAULT_STRATEGY, what the reference writes), 1 Z_FILTERED, 2 Z_HUFFMAN_ONLY, 3 Z_RLE, 4 Z_FIXED.  Anything else
+    (bool, str and float included): ValueError."""
+    strategy = config["encoder"].get("deflate_strategy")
+    return 0 if strategy is None else _check_strategy(strategy)
+
+
+def deflate_level(config):
+    """config['encoder']['deflate_level'] -> zlib level of the DEFLATE stage: absent -> 9 (what the reference writes),
+    -1 -> 6 (Z_DEFAULT_COMPRESSION), 4 .. 9 as given.  Levels 0 to 3 run deflate_stored / deflate_fast, which the
+    device does not implement: ValueError, as for anything else -- except levels 1 to 3 under deflate_strategy 2 or 3
+    (deflate_huff / deflate_rle ignore the level)."""
+    strategy = deflate_strategy(config)
+    level = config["encoder"].get("deflate_level")
+    if level is None:
+        return 9
+    return _check_level(level, strategy)
+
+
 def codec_params(config, dtype=None):
     """config dict -> (flags, block_size, eof, magic, channels, bytes_per_channel).  An optional
-    config['encoder']['deflate_level'] sets the CCT_FLAG_DEFLATE_LEVEL field (absent: field 0 = level 9)."""
+    config['encoder']['deflate_level'] sets the CCT_FLAG_DEFLATE_LEVEL field (absent: field 0 = level 9), an optional
+    config['encoder']['deflate_strategy'] the CCT_FLAG_DEFLATE_STRATEGY field (absent: field 0 = Z_DEFAULT_STRATEGY)."""
     enc = config["encoder"]
     tr = enc["transforms"]
     flags = 0
@@ -59,6 +92,8 @@ def codec_params(config, dtype=None):
         flags |= _ffi.FLAG_SIGNED_SEG
     if enc.get("deflate_level") is not None:
         flags |= _ffi.flag_deflate_level(deflate_level(config))
+    if enc.get("deflate_strategy") is not None:
+        flags |= _ffi.flag_deflate_strategy(deflate_strategy(config))
     eof = enc.get("end_of_file")
     return (flags, int(config["block_size"]), -1 if eof is None else int(eof) % 256, magic_bytes(config),
             int(enc["channels"]), int(enc["bytes_per_channel"]))
@@ -286,15 +321,15 @@ def decode_batch(files, config=None, out_dev=None):
     return out
 
 
-def zlib_compress_batch(blobs, level=9):
+def zlib_compress_batch(blobs, level=9, strategy=0):
     """DEFLATE stage alone on the device: [bytes] -> [zlib streams], each byte-identical to
     zlib.compress(blob, level) -- level 9 by default (what the reference calls at core.py:340), 4 to 8, or
-    -1 for zlib's default 6.  Levels 0 to 3 are not on the device (ValueError)."""
+    -1 for zlib's default 6.  Levels 0 to 3 are not on the device (ValueError).  strategy (zlib's Z_* constant, 0 to 4):
+    the stream of zlib.compressobj(level, zlib.DEFLATED, 15, 8, strategy); Z_HUFFMAN_ONLY (2) and Z_RLE (3) also take
+    levels 1 to 3."""
     import zlib
-    level = int(level)
-    if level != -1 and not 4 <= level <= 9:
-        raise ValueError(f"zlib level {level}: supported levels are -1 and 4 to 9 "
-                         "(0 to 3 are deflate_stored / deflate_fast, not on the device)")
+    strategy = _check_strategy(strategy)
+    level = _check_level(int(level), strategy)
     L = _ffi.lib()
     n = len(blobs)
     if n == 0:
@@ -307,8 +342,8 @@ def zlib_compress_batch(blobs, level=9):
     out_stride = (len(zlib.compress(b"", 0)) + in_stride + (in_stride >> 12) + (in_stride >> 14) + (in_stride >> 25) + 13 + 128 + 63) & ~63
     out = np.empty((n, out_stride), dtype=np.uint8)
     sizes = np.zeros(n, dtype=np.uint32)
-    _ffi.check(L.cct_zlib_compress_batch_level(data, offs.ctypes.data, n, level, out.ctypes.data, out_stride,
-                                               sizes.ctypes.data))
+    _ffi.check(L.cct_zlib_compress_batch_strategy(data, offs.ctypes.data, n, level, strategy, out.ctypes.data,
+                                                  out_stride, sizes.ctypes.data))
     return [out[i, : sizes[i]].tobytes() for i in range(n)]
 
 

@@ -725,28 +725,36 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 // passes, the run list, the block walk) left half of the 256 CUs idle.
 constexpr size_t DEFLATE_PASS_BYTES = (size_t)1 << 30;
 
-// DEFLATE (zlib stream of `level`, 4 .. 9) of n device-resident byte strings on the device; output slice i =
-// 13 header bytes + zlib stream at d_out + i*out_stride (E.z_out), sizes in E.z_outsizes.
+// DEFLATE (zlib stream of `level` and `strategy`: 4 .. 9 with strategies 0, 1, 4, 1 .. 9 with 2, 3) of n device-resident byte
+// strings on the device; output slice i = 13 header bytes + zlib stream at d_out + i*out_stride (E.z_out), sizes in E.z_outsizes.
 int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint32_t *d_in_sizes, int n, const uint8_t header13[13],
-                   size_t out_stride, int level)
+                   size_t out_stride, int level, int strategy)
 {
 	if (in_stride % 256 != 0 || out_stride % 4 != 0) return fail(CCT_E_ARG, "deflate strides must be multiples of 256 / 4");
 	DeflateArgs a{};
-	if (!deflate_level_args(level, a)) return fail(CCT_E_ARG, "zlib level %d is not on the device", level);
+	if (!deflate_strategy_args(level, strategy, a))
+		return fail(CCT_E_ARG, "zlib level %d with strategy %d is not on the device", level, strategy);
+	// Z_HUFFMAN_ONLY / Z_RLE: the short pass (launch_deflate) uses no sort records, match records, run lists or queues, and
+	// Z_HUFFMAN_ONLY no decision records or walk either: those workspaces are neither grown nor cleared for it
+	const bool chains = strategy != 2 && strategy != 3, walk = strategy != 2;
 	const size_t EB = (size_t)n * in_stride;
 	if (EB >= ((size_t)1 << 32)) return fail(CCT_E_ARG, "deflate batch of %zu bytes exceeds the 4 GiB sort limit; split the batch", EB);
 	const int max_blocks = (int)(in_stride / 16383 + 2);
 	int rc;
-	if ((rc = E.z_vals_in.ensure(EB * 8))) return rc;   // records between the two sort passes, then run_ends + run_len
-	if ((rc = E.z_vals_out.ensure(EB * 8))) return rc;  // sorted records
-	if ((rc = E.z_mr.ensure(EB * 8))) return rc;
-	if ((rc = E.z_runs.ensure(EB * 4))) return rc;
-	if ((rc = E.z_rec.ensure(EB * 4))) return rc;
+	if (chains) {
+		if ((rc = E.z_vals_in.ensure(EB * 8))) return rc;   // records between the two sort passes, then run_ends + run_len
+		if ((rc = E.z_vals_out.ensure(EB * 8))) return rc;  // sorted records
+		if ((rc = E.z_mr.ensure(EB * 8))) return rc;
+		if ((rc = E.z_runs.ensure(EB * 4))) return rc;
+		if ((rc = E.z_rec.ensure(EB * 4))) return rc;
+	}
 	if ((rc = E.z_sym.ensure(EB * 4))) return rc;
-	if ((rc = E.z_exitp.ensure(EB * 4))) return rc;
-	if ((rc = E.z_exitc.ensure(EB * 4))) return rc;
-	if ((rc = E.z_bentry.ensure(EB / 64 * 4))) return rc;
-	if ((rc = E.z_bsym.ensure(EB / 64 * 4))) return rc;
+	if (walk) {
+		if ((rc = E.z_exitp.ensure(EB * 4))) return rc;
+		if ((rc = E.z_exitc.ensure(EB * 4))) return rc;
+		if ((rc = E.z_bentry.ensure(EB / 64 * 4))) return rc;
+		if ((rc = E.z_bsym.ensure(EB / 64 * 4))) return rc;
+	}
 	const int run_chunks = (int)(in_stride / 1784 + 1);  // chunks of dfl_run_len_kernel (RUNLEN_OUT positions) per slice
 	if ((rc = E.z_small.ensure((size_t)n * (9 + 384 + 2 * (size_t)run_chunks) * 4))) return rc;
 	if ((rc = E.z_bend.ensure((size_t)n * max_blocks * 4))) return rc;
@@ -773,13 +781,14 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 	a.run_counts = small + (9 + 384) * (size_t)n; a.run_chunks = run_chunks;
 	// the tag of a pass must not meet a record of 16383 passes ago: clear records and counter well before it comes round (and
 	// whenever the buffer is new); a pass that failed on the way may have left the two counts a few apart, hence the margin
+	// (a short pass neither reads match records nor advances the tag: it does not count)
 	if ((rc = E.z_gen.ensure(256))) return rc;
-	if (E.z_mr_cleared != E.z_mr.p || E.z_mr_cleared_cap != E.z_mr.cap || E.z_gen_passes >= 16000u) {
+	if (chains && (E.z_mr_cleared != E.z_mr.p || E.z_mr_cleared_cap != E.z_mr.cap || E.z_gen_passes >= 16000u)) {
 		HIP_TRY(hipMemsetAsync(E.z_mr.p, 0, E.z_mr.cap, E.stream));
 		HIP_TRY(hipMemsetAsync(E.z_gen.p, 0, 256, E.stream));
 		E.z_mr_cleared = E.z_mr.p; E.z_mr_cleared_cap = E.z_mr.cap; E.z_gen_passes = 0;
 	}
-	E.z_gen_passes++;
+	if (chains) E.z_gen_passes++;
 	a.gen = (uint32_t *)E.z_gen.p;
 	a.mr = E.z_mr.p; a.heavy_list = (uint32_t *)E.z_rec.p; a.sym = (uint32_t *)E.z_sym.p;
 	a.run_ends = (uint32_t *)E.z_runs.p;  // 4 EB of their own: the lists are built while the sort runs (launch_deflate)
@@ -1111,7 +1120,8 @@ int cct_encode_payload_dev(const uint16_t *d_images, int n, int width, int heigh
 	int rc = check_shape(n, width, height, block_size);
 	if (rc) return rc;
 	if ((rc = ensure_ctx())) return rc;
-	return encode_payload_locked(g_enc[0], g_ctx.stream, d_images, n, width, height, block_size, flags & ~CCT_FLAG_LEVEL_MASK, eof_byte, d_payload, payload_stride,
+	return encode_payload_locked(g_enc[0], g_ctx.stream, d_images, n, width, height, block_size,
+	                             flags & ~(CCT_FLAG_LEVEL_MASK | CCT_FLAG_STRATEGY_MASK), eof_byte, d_payload, payload_stride,
 	                             d_payload_sizes, d_status, d_stats, d_roles);
 }
 
@@ -1131,11 +1141,20 @@ static EncSlot &acquire_encode_slot(std::unique_lock<std::mutex> &lk)
 	}
 }
 
-// CCT_FLAG_DEFLATE_LEVEL field -> zlib level (a clear field is level 9, what the reference writes); -1 for a refused field
-static int flags_deflate_level(uint32_t flags)
+// CCT_FLAG_DEFLATE_STRATEGY field -> zlib strategy 0 .. 4 (a clear field is Z_DEFAULT_STRATEGY); -1 for a refused field
+static int flags_deflate_strategy(uint32_t flags)
+{
+	const int f = (int)((flags & CCT_FLAG_STRATEGY_MASK) >> 12);
+	return f <= 4 ? f : -1;
+}
+
+// CCT_FLAG_DEFLATE_LEVEL field -> zlib level (a clear field is level 9, what the reference writes); -1 for a refused field.
+// Levels 1 .. 3 are deflate_fast, except under Z_HUFFMAN_ONLY / Z_RLE, which ignore the level's function
+static int flags_deflate_level(uint32_t flags, int strategy)
 {
 	const int f = (int)((flags & CCT_FLAG_LEVEL_MASK) >> 8);
-	return f == 0 ? 9 : (f >= 4 && f <= 9) ? f : -1;
+	const int lo = (strategy == 2 || strategy == 3) ? 1 : 4;
+	return f == 0 ? 9 : (f >= lo && f <= 9) ? f : -1;
 }
 
 // core.py:193-210 (big-endian fields, values masked to a byte / 16 bits)
@@ -1266,7 +1285,7 @@ static int files_to_strided(FilesOut &f, uint8_t *h_first, size_t out_stride)
 
 // DEFLATE (or none) on the host thread team: payloads come back, libz at `level` per slice (9: core.py:340), header in front
 static int files_on_host(EncSlot &E, int n, size_t stride, const std::vector<uint32_t> &psz, const uint8_t hdr13[13], bool defl,
-                         int level, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, const uint32_t *h_status)
+                         int level, int strategy, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, const uint32_t *h_status)
 {
 	const double t_copy0 = now_ms();
 	uint8_t *stage = (uint8_t *)E.h_stage.p;
@@ -1283,7 +1302,18 @@ static int files_on_host(EncSlot &E, int n, size_t stride, const std::vector<uin
 		uint8_t *o = h_out + (size_t)i * out_stride;
 		memcpy(o, hdr13, 13);
 		const uint8_t *pl = stage + (size_t)i * stride;
-		if (defl) {  // zlib.compress(data, level), core.py:340 with level 9
+		if (defl && strategy != Z_DEFAULT_STRATEGY) {  // zlib.compressobj(level, DEFLATED, 15, 8, strategy)
+			z_stream zs{};
+			int zr = deflateInit2(&zs, level, Z_DEFLATED, 15, 8, strategy);
+			if (zr != Z_OK) { zerr.store(zr); h_out_sizes[i] = 0; return; }
+			zs.next_in = const_cast<Bytef *>(pl); zs.avail_in = psz[i];
+			zs.next_out = o + 13; zs.avail_out = (uInt)(out_stride - 13);
+			zr = deflate(&zs, Z_FINISH);
+			const uLong dl = zs.total_out;
+			(void)deflateEnd(&zs);
+			if (zr != Z_STREAM_END) { zerr.store(zr == Z_OK ? Z_BUF_ERROR : zr); h_out_sizes[i] = 0; return; }
+			h_out_sizes[i] = 13 + (uint32_t)dl;
+		} else if (defl) {  // zlib.compress(data, level), core.py:340 with level 9
 			uLongf dl = (uLongf)(out_stride - 13);
 			const int zr = compress2(o + 13, &dl, pl, psz[i], level);
 			if (zr != Z_OK) { zerr.store(zr); h_out_sizes[i] = 0; return; }
@@ -1308,11 +1338,18 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 	const bool packed = h_packed_offsets != nullptr;
 	const double t_call0 = now_ms();
 	EncodeInFlight in_flight;  // decode calls that start meanwhile pick the INFLATE geometry that shares the device best
-	const int level = flags_deflate_level(flags);
-	if (level < 0)
-		return fail(CCT_E_ARG, "deflate level field %u: levels 4 .. 9 only (1 .. 3 are deflate_fast: not on the device)",
-		            (flags & CCT_FLAG_LEVEL_MASK) >> 8);
-	flags &= ~CCT_FLAG_LEVEL_MASK;  // the payload stage and the .cct header do not depend on it
+	const int strategy = flags_deflate_strategy(flags);
+	if (strategy < 0)
+		return fail(CCT_E_ARG, "deflate strategy field %u: zlib strategies are 0 .. 4", (flags & CCT_FLAG_STRATEGY_MASK) >> 12);
+	const int level = flags_deflate_level(flags, strategy);
+	if (level < 0) {
+		if (strategy == 2 || strategy == 3)
+			return fail(CCT_E_ARG, "deflate level field %u with strategy %d: levels 1 .. 9 only",
+			            (flags & CCT_FLAG_LEVEL_MASK) >> 8, strategy);
+		return fail(CCT_E_ARG, "deflate level field %u with strategy %d: levels 4 .. 9 only (1 .. 3 are deflate_fast: not on the device)",
+		            (flags & CCT_FLAG_LEVEL_MASK) >> 8, strategy);
+	}
+	flags &= ~(CCT_FLAG_LEVEL_MASK | CCT_FLAG_STRATEGY_MASK);  // the payload stage and the .cct header do not depend on them
 	int rc = check_shape(n, width, height, block_size);
 	if (rc) return rc;
 	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device
@@ -1403,7 +1440,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 			const int nc = std::min(chunk, n - c0);
 			HIP_TRY(hipEventRecord(ev_z0, E.stream));
 			rc = deflate_locked(E, (const uint8_t *)E.e_payload.p + (size_t)c0 * stride, stride,
-			                    (const uint32_t *)E.e_sizes.p + c0, nc, hdr13, zstride, level);
+			                    (const uint32_t *)E.e_sizes.p + c0, nc, hdr13, zstride, level, strategy);
 			if (rc) return rc;
 			HIP_TRY(hipEventRecord(ev_z1, E.stream));
 			g_gate_passes_issued.fetch_add(1, std::memory_order_relaxed);
@@ -1489,7 +1526,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 		if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
 		return CCT_OK;
 	}
-	rc = files_on_host(E, n, stride, psz, hdr13, defl, level, h_out, out_stride, h_out_sizes, h_status);
+	rc = files_on_host(E, n, stride, psz, hdr13, defl, level, strategy, h_out, out_stride, h_out_sizes, h_status);
 	if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
 	return rc;
 }
@@ -1513,7 +1550,7 @@ int cct_encode_batch_packed(const uint16_t *images, int images_on_device, int n,
 	                         bytes_per_channel, h_archive, archive_cap, h_out_sizes, h_status, h_payload_sizes, h_stats, h_offsets);
 }
 
-static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, uint8_t *h_out,
+static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy, uint8_t *h_out,
                                     size_t out_stride, uint32_t *h_out_sizes)
 {
 	std::lock_guard<std::mutex> lk(g_mu);
@@ -1548,7 +1585,7 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 	HIP_TRY(hipEventCreate(&ev.e[0]));
 	HIP_TRY(hipEventCreate(&ev.e[1]));
 	HIP_TRY(hipEventRecord(ev.e[0], E.stream));
-	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride, level);
+	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride, level, strategy);
 	if (rc) return rc;
 	HIP_TRY(hipEventRecord(ev.e[1], E.stream));
 	HIP_TRY(hipMemcpyAsync(osz.data(), E.z_outsizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
@@ -1566,7 +1603,7 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, uint8_t *h_out, size_t out_stride,
                             uint32_t *h_out_sizes)
 {
-	return zlib_compress_batch_impl(h_in, h_offsets, n, 9, h_out, out_stride, h_out_sizes);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, 9, Z_DEFAULT_STRATEGY, h_out, out_stride, h_out_sizes);
 }
 
 int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, uint8_t *h_out,
@@ -1575,7 +1612,20 @@ int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets
 	if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION
 	if (level >= 0 && level <= 3) return fail(CCT_E_ARG, "zlib level %d: deflate_stored / deflate_fast: not on the device", level);
 	if (level < 4 || level > 9) return fail(CCT_E_ARG, "zlib level %d: levels are -1 and 4 .. 9", level);
-	return zlib_compress_batch_impl(h_in, h_offsets, n, level, h_out, out_stride, h_out_sizes);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, level, Z_DEFAULT_STRATEGY, h_out, out_stride, h_out_sizes);
+}
+
+int cct_zlib_compress_batch_strategy(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy,
+                                     uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
+{
+	if (strategy < Z_DEFAULT_STRATEGY || strategy > Z_FIXED)
+		return fail(CCT_E_ARG, "zlib strategy %d: strategies are 0 .. 4 (Z_DEFAULT_STRATEGY .. Z_FIXED)", strategy);
+	if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION
+	if (level == 0) return fail(CCT_E_ARG, "zlib level 0 with strategy %d: deflate_stored: not on the device", strategy);
+	if (level < 0 || level > 9) return fail(CCT_E_ARG, "zlib level %d with strategy %d: levels are -1 and 1 .. 9", level, strategy);
+	if (strategy != Z_HUFFMAN_ONLY && strategy != Z_RLE && level <= 3)
+		return fail(CCT_E_ARG, "zlib level %d with strategy %d: deflate_fast: not on the device (levels -1 and 4 .. 9)", level, strategy);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, level, strategy, h_out, out_stride, h_out_sizes);
 }
 
 // take a free decode slot (see DecSlot)

@@ -176,9 +176,15 @@ struct DeflateArgs {
 	uint8_t header13[16];
 	// the zlib level (4 .. 9, all deflate_slow): deflate.c configuration_table entries and the second header byte
 	uint32_t good, max_lazy, nice, max_chain, zlib_flg;
+	// the zlib strategy (0 .. 4, deflate_kernels.hip "zlib strategies") and the shortest match deflate_slow keeps:
+	// MIN_MATCH, or 6 under Z_FILTERED (matches of <= 5 bytes dropped)
+	uint32_t strategy, min_len;
 };
 // a level's fields of DeflateArgs (deflate_kernels.hip); false for levels outside 4 .. 9
 bool deflate_level_args(int level, DeflateArgs &a);
+// the fields of a (level, strategy) pair: levels 4 .. 9 with strategies 0, 1 and 4 (deflate_slow), levels 1 .. 9 with 2
+// and 3 (deflate_huff / deflate_rle, which read no level table); false for anything else
+bool deflate_strategy_args(int level, int strategy, DeflateArgs &a);
 hipError_t deflate_init_tables();
 size_t deflate_sort_temp_bytes(size_t total, int n);
 hipError_t launch_pack(const uint8_t *src, size_t stride, const uint32_t *sizes, int n, uint64_t *offsets, uint8_t *dst,

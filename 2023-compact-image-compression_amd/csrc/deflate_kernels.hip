@@ -1,11 +1,16 @@
-// Device DEFLATE, byte-identical to zlib 1.2.11 `deflate(level L, wbits 15, memLevel 8, default
-// strategy, one-shot Z_FINISH)` for L = 4 .. 9 -- level 9 is the stream CPython's zlib.compress(data,
-// level=9) produces for the reference (src/codec/core.py:340).  zlib is a third-party dependency of the
+// Device DEFLATE, byte-identical to zlib 1.2.11 `deflateInit2(level L, Z_DEFLATED, wbits 15, memLevel 8,
+// strategy S)` + one-shot Z_FINISH for L = 4 .. 9 -- level 9 with the default strategy is the stream CPython's
+// zlib.compress(data, level=9) produces for the reference (src/codec/core.py:340).  zlib is a third-party dependency of the
 // reference and is not vendored there; the algorithm is restated here in data-parallel form (CPU model
 // of the same restatement, pinned against libz: oracle/deflate_model.c for level 9,
 // tools/deflate_level_model.c for every level).  All six levels run deflate_slow, which inserts every
 // string into the hash chains; the level enters only through good / max_lazy / nice / max_chain
 // (DeflateArgs) in the match and decision kernels, and the second zlib header byte.
+//
+// zlib strategies (DeflateArgs::strategy): Z_DEFAULT_STRATEGY and Z_FIXED (static trees unless a stored block is
+// smaller: dfl_tree_kernel) and Z_FILTERED (matches of <= 5 bytes dropped: match_of) run deflate_slow, levels 4 .. 9.
+// Z_RLE (deflate_rle: greedy matches at distance 1 only) and Z_HUFFMAN_ONLY (deflate_huff: literals only) run at any
+// level 1 .. 9 with the same bytes, as a short pass without the sort and match kernels (launch_deflate).
 //
 //   sort      stable two-pass LSD radix sort of (hash, position) per slice, the 15-bit rolling hash of 3 bytes
 //             (deflate.c UPDATE_HASH) computed on the fly: a bucket in position order IS zlib's hash chain
@@ -44,6 +49,9 @@ constexpr int TOO_FAR = 4096;
 constexpr int BLOCK_SYMS = 16383;                // lit_bufsize - 1 (memLevel 8)
 constexpr int L_CODES = 286, D_CODES = 30, BL_CODES = 19, HEAP_SIZE = 2 * L_CODES + 1;
 constexpr int END_BLOCK = 256, MAX_BITS = 15, MAX_BL_BITS = 7;
+constexpr uint32_t Z_FILTERED = 1, Z_HUFFMAN_ONLY = 2, Z_RLE = 3, Z_FIXED = 4;  // zlib.h strategies
+// deflate_huff / deflate_rle instead of deflate_slow: the short pass (launch_deflate)
+__host__ __device__ __forceinline__ bool short_pass(uint32_t strategy) { return strategy == Z_HUFFMAN_ONLY || strategy == Z_RLE; }
 
 __constant__ uint8_t c_extra_lbits[29] = {0,0,0,0,0,0,0,0,1,1,1,1,2,2,2,2,3,3,3,3,4,4,4,4,5,5,5,5,0};
 __constant__ uint8_t c_extra_dbits[30] = {0,0,0,0,1,1,2,2,3,3,4,4,5,5,6,6,7,7,8,8,9,9,10,10,11,11,12,12,13,13};
@@ -315,11 +323,13 @@ __device__ __forceinline__ uint32_t nil_candidate(uint32_t p, uint32_t lookahead
 // scanned tail (>= 264 bytes) decides every length below the cap.
 constexpr int RUNLEN_OUT = 2048 - 264;
 
+// SORT = false (the Z_RLE pass): run-length words only, without the sort histograms and run-list counts nobody reads there
+template <bool SORT>
 __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 {
 	__shared__ uint32_t wtot[4];  // per wave: has_change << 31 | distance from the wave's first position to its first change
-	__shared__ uint32_t hist[384];  // digits of the sort: hash & 255 of every string of this workgroup's positions, then hash >> 8
-	for (int t = threadIdx.x; t < 384; t += 256) hist[t] = 0;
+	__shared__ uint32_t hist[SORT ? 384 : 1];  // digits of the sort: hash & 255 of every string of this workgroup's positions, then hash >> 8
+	if (SORT) for (int t = threadIdx.x; t < 384; t += 256) hist[t] = 0;
 	__syncthreads();
 	const int s = blockIdx.y;
 	const uint32_t L = a.in_sizes[s];
@@ -346,7 +356,7 @@ __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 		// the sort's digit histograms (UPDATE_HASH of the three bytes from every published position that starts a string).
 		// A quarter of a CT payload is runs of one byte: a lane whose strings all hash alike adds them in one go, and so does
 		// a wave (every lane adding 1 to the same two counters made this kernel 0.31 instead of 0.09 ms)
-		{
+		if (SORT) {
 			uint32_t hk[8], cnt = 0, h0 = 0;
 			bool same = true;
 #pragma unroll
@@ -407,7 +417,7 @@ __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 		// entries this chunk contributes to the lists of run ends and run starts (dfl_run_lists_kernel): position p ends a run of
 		// >= 3 three bytes on (exactly three equal bytes from p, the fourth inside the input) and starts one when >= 3 equal bytes
 		// follow and the byte before differs
-		{
+		if (SORT) {
 			// from the "changes after this byte" bits of in[g-1 .. g+9] (bit i: in[g-1+i] != in[g+i], or the right byte is past the
 			// end, or -- bit 0 -- there is no byte before position 0): position p = g+k, pair p <-> bit k+1
 			uint32_t cx = g == 0 ? 1u : 0u;
@@ -429,6 +439,7 @@ __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 			}
 		}
 	}
+	if (!SORT) return;
 	__syncthreads();
 	for (int t = threadIdx.x; t < 384; t += 256)
 		if (hist[t]) atomicAdd(&a.sort_hist[(size_t)s * 384 + t], hist[t]);
@@ -920,23 +931,26 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 
 // ------------------------------------------------------------------ 3a. decision records + block summaries
 // rec32: bits 0..7 k (deferred literals), 8..16 match length (0 = none), 17..31 distance
-// lazy = max_lazy_match, good = good_match of the level
-__device__ __forceinline__ void match_of(const MatchRec &r, uint32_t p, uint32_t npos, int prev_len, int lazy, int good, int &len, int &dist)
+// lazy = max_lazy_match, good = good_match of the level, minl = DeflateArgs::min_len (3, or 6 under Z_FILTERED)
+__device__ __forceinline__ void match_of(const MatchRec &r, uint32_t p, uint32_t npos, int prev_len, int lazy, int good, int minl,
+                                         int &len, int &dist)
 {
-	// deflate_slow: match_length after longest_match + TOO_FAR rule, given prev_length (deflate.c:1863-1880); r = record of p
+	// deflate_slow: match_length after longest_match + filter / TOO_FAR rule, given prev_length (deflate.c:1863-1880); r = record
+	// of p.  zlib drops a match of <= 5 bytes under Z_FILTERED: the same as requiring minl = 6 bytes here (a length longest_match
+	// returns without beating prev_length is "no match" either way), and a 3-byte match never survives it for the TOO_FAR test
 	len = 2; dist = 0;
 	if (p >= npos || prev_len >= lazy) return;
 	const int l = prev_len >= good ? r.len_quarter : r.len_full;
 	const int d = prev_len >= good ? r.dist_quarter : r.dist_full;
-	if (l > prev_len && l >= MIN_MATCH) { len = l; dist = d; }
+	if (l > prev_len && l >= minl) { len = l; dist = d; }
 	if (len == MIN_MATCH && dist > TOO_FAR) len = 2;
 }
 __device__ __forceinline__ void match_at(const MatchRec *mr, const uint16_t *rl, uint32_t gen, uint32_t p, uint32_t npos, int prev_len,
-                                         int lazy, int good, int &len, int &dist)
+                                         int lazy, int good, int minl, int &len, int &dist)
 {
 	len = 2; dist = 0;
 	if (p >= npos || prev_len >= lazy) return;
-	match_of(checked_match(mr[p], gen, rl[p], p, npos + 2), p, npos, prev_len, lazy, good, len, dist);
+	match_of(checked_match(mr[p], gen, rl[p], p, npos + 2), p, npos, prev_len, lazy, good, minl, len, dist);
 }
 
 __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
@@ -950,7 +964,7 @@ __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
 	const uint32_t nblk64 = (L + 63) / 64;
 	const int lane = threadIdx.x & 63;
 	const uint32_t gen = *a.gen;
-	const int lazy = (int)a.max_lazy, good = (int)a.good;
+	const int lazy = (int)a.max_lazy, good = (int)a.good, minl = (int)a.min_len;
 	// the lane's own record and its right neighbour's (what the first deferral test reads) are requested together and without a
 	// branch (a load inside a conditional is waited for on the spot, which made them two round trips in a row), one turn ahead
 	const uint32_t lastp = npos ? npos - 1 : 0;
@@ -972,14 +986,14 @@ __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
 		const MatchRec r0 = checked_match(cq.m0, gen, cq.w0, pa, L), r1 = checked_match(cq.m1, gen, cq.w1, pb, L);
 		if (p < L) {
 			int len, dist;
-			match_of(r0, p, npos, 2, lazy, good, len, dist);
+			match_of(r0, p, npos, 2, lazy, good, minl, len, dist);
 			if (len < MIN_MATCH) { rec = 0; nxt = p + 1; cnt = 1; }  // literal in[p]
 			else {
 				uint32_t k = 0;
 				for (;;) {  // lazy evaluation: defer while the next position has a longer match
 					int l2, d2;
-					if (k == 0) match_of(r1, p + 1, npos, len, lazy, good, l2, d2);
-					else match_at(mr, rl, gen, p + k + 1, npos, len, lazy, good, l2, d2);
+					if (k == 0) match_of(r1, p + 1, npos, len, lazy, good, minl, l2, d2);
+					else match_at(mr, rl, gen, p + k + 1, npos, len, lazy, good, minl, l2, d2);
 					if (l2 > len) { len = l2; dist = d2; k++; } else break;
 				}
 				rec = k | ((uint32_t)len << 8) | ((uint32_t)dist << 17);
@@ -997,6 +1011,78 @@ __global__ void __launch_bounds__(256) dfl_rec_kernel(DeflateArgs a)
 			if (inside) { nxt = n2; cnt += c2; }
 		}
 		a.exit_pos[base + p] = (nxt - blk_end) | (cnt << 16);  // both < 1024: one word per position (entry -> exit offset past the block, symbols)
+	}
+}
+
+// ------------------------------------------------------------------ 3a'. the parse of the short passes
+// deflate_rle: at position p > 0 with >= 3 bytes of lookahead and in[p-1] == in[p] == in[p+1] == in[p+2], the match (distance 1)
+// runs over every byte equal to in[p-1] from p, capped at MAX_MATCH and at the end of the input; otherwise in[p] is a literal.
+// The parse is greedy (no lazy step), so a position's record needs only its run-length word: the length is the word's low
+// bits, and in[p-1] == in[p] is its bit 15 -- except at p = 1, where bit 15 is clear (the hash chains never match position 0,
+// the run matcher's rule) but deflate_rle compares in[0] and in[1]: in[0] == in[1] is run_len[0] >= 2.  Same rec32 / exit_pos
+// format as dfl_rec_kernel (k = 0 deferred literals, one symbol per decision position), so the walk and the symbols kernel
+// follow it unchanged.
+__global__ void __launch_bounds__(256) dfl_rle_rec_kernel(DeflateArgs a)
+{
+	const int s = blockIdx.y;
+	const uint32_t L = a.in_sizes[s];
+	const size_t base = (size_t)s * a.in_stride;
+	const uint16_t *rl = a.run_len + base;
+	const uint32_t nblk64 = (L + 63) / 64;
+	const int lane = threadIdx.x & 63;
+	const uint32_t lastp = L ? L - 1 : 0;
+	const uint32_t wb_step = gridDim.x * (blockDim.x >> 6);
+	const uint32_t wb0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	uint32_t nx = rl[min(wb0 * 64 + lane, lastp)];  // one turn ahead, index clamped instead of tested
+	for (uint32_t wb = wb0; wb < nblk64; wb += wb_step) {
+		const uint32_t p = wb * 64 + lane;
+		const uint32_t blk_end = wb * 64 + 64;
+		const uint32_t rw = nx;
+		nx = rl[min((wb + wb_step) * 64 + lane, lastp)];
+		const uint32_t rw0 = (uint32_t)__shfl((int)rw, 0);  // run_len[0] in the wave of block 0
+		const bool prev_eq = p >= 2 ? (rw >> 15) != 0 : (p == 1 && (rw0 & 0x7FFFu) >= 2u);
+		const uint32_t run = rw & 0x7FFFu;
+		uint32_t rec = 0, nxt = blk_end, cnt = 0;
+		if (p < L) {
+			const bool m = prev_eq && run >= (uint32_t)MIN_MATCH;  // (run >= 3 implies the lookahead >= 3)
+			rec = m ? (run << 8) | (1u << 17) : 0u;
+			nxt = p + (m ? run : 1u);
+			cnt = 1;
+		}
+		a.rec32[base + p] = rec;
+#pragma unroll
+		for (int r = 0; r < 6; r++) {
+			const bool inside = nxt < blk_end;
+			const int j = inside ? (int)(nxt - wb * 64) : lane;
+			const uint32_t n2 = __shfl(nxt, j), c2 = __shfl(cnt, j);
+			if (inside) { nxt = n2; cnt += c2; }
+		}
+		a.exit_pos[base + p] = (nxt - blk_end) | (cnt << 16);
+	}
+}
+
+// deflate_huff: every byte is a literal, so symbol p is in[p] and block m ends at input position 16383 (m + 1): no parse, no
+// walk.  Four positions per lane (in_stride is a multiple of 256: the dword and the four symbols stay inside the slice)
+__global__ void __launch_bounds__(256) dfl_huff_symbols_kernel(DeflateArgs a)
+{
+	const int s = blockIdx.y;
+	const uint32_t L = a.in_sizes[s];
+	const size_t base = (size_t)s * a.in_stride;
+	const uint32_t *in4 = reinterpret_cast<const uint32_t *>(a.in + base);
+	uint4 *sym4 = reinterpret_cast<uint4 *>(a.sym + base);
+	uint32_t *bend = a.blk_end + (size_t)s * a.max_blocks;
+	if (blockIdx.x == 0 && threadIdx.x == 0) a.total_syms[s] = L;
+	const uint32_t nq = (L + 3) / 4;
+	for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += gridDim.x * blockDim.x) {
+		const uint32_t w = in4[q], p0 = 4 * q;
+		uint32_t v[4];
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const uint32_t p = p0 + (uint32_t)k;
+			v[k] = p < L ? (w >> (8 * k)) & 255u : 0u;
+			if (p < L && p % BLOCK_SYMS == BLOCK_SYMS - 1) bend[p / BLOCK_SYMS] = p + 1;
+		}
+		sym4[q] = make_uint4(v[0], v[1], v[2], v[3]);
 	}
 }
 
@@ -1571,7 +1657,9 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 	const uint32_t L = a.in_sizes[s];
 	// number of blocks: one flush per 16383 tallied symbols inside the loop, plus the final flush
 	uint32_t nfull = T / BLOCK_SYMS;
-	if (T % BLOCK_SYMS == 0 && nfull > 0 && a.postloop_lit[s]) nfull--;  // the post-loop literal never flushes
+	// the post-loop literal never flushes (deflate_slow only: deflate_huff and deflate_rle have none, and there a symbol count that
+	// is a multiple of 16383 ends the stream with an empty final block)
+	if (T % BLOCK_SYMS == 0 && nfull > 0 && !short_pass(a.strategy) && a.postloop_lit[s]) nfull--;
 	const uint32_t nblocks = nfull + 1;
 	BlockMeta *meta = a.block_meta + (size_t)s * a.max_blocks;
 	if ((uint32_t)m0 >= nblocks) return;
@@ -1712,7 +1800,7 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		bm.in_begin = in_begin; bm.stored_len = stored_len; bm.first_sym = first; bm.nsym = nsym; bm.last = last ? 1u : 0u;
 		if (stored_len + 4 <= opt_lenb) {
 			bm.type = 0; bm.hdr_nbits = 0; bm.body_bits = 0;
-		} else if (static_lenb == opt_lenb) {
+		} else if (a.strategy == Z_FIXED || static_lenb == opt_lenb) {  // trees.c _tr_flush_block
 			bm.type = 1; bm.hdr_nbits = 0; bm.body_bits = S.static_len;
 		} else {
 			bm.type = 2; bm.hdr_nbits = 0;  // hdr_nbits follows below, once the wave has written the header
@@ -2024,6 +2112,24 @@ bool deflate_level_args(int level, DeflateArgs &a)
 	return true;
 }
 
+// (level, strategy) -> DeflateArgs.  deflate.c: level_flags is 0 for strategy >= Z_HUFFMAN_ONLY (Z_FIXED included) or level < 2;
+// deflate_huff and deflate_rle read no configuration_table entry, so every level 1 .. 9 gives the same stream (and graph)
+bool deflate_strategy_args(int level, int strategy, DeflateArgs &a)
+{
+	if (strategy < 0 || strategy > (int)Z_FIXED) return false;
+	a.strategy = (uint32_t)strategy;
+	a.min_len = strategy == (int)Z_FILTERED ? 6u : (uint32_t)MIN_MATCH;
+	if (short_pass((uint32_t)strategy)) {
+		if (level < 1 || level > 9) return false;
+		a.good = a.max_lazy = a.nice = a.max_chain = 0;
+		a.zlib_flg = 0x01;
+		return true;
+	}
+	if (!deflate_level_args(level, a)) return false;
+	if (strategy == (int)Z_FIXED) a.zlib_flg = 0x01;
+	return true;
+}
+
 // host: trees.c tr_static_init tables -> constant memory
 hipError_t deflate_init_tables()
 {
@@ -2083,16 +2189,42 @@ size_t deflate_sort_temp_bytes(size_t total, int n)
 //     side:                               └─ run lists ─┴─ heavy matcher, Adler ─┘
 // Under stream capture this becomes the same fork / join in the graph.  Next to the SORT passes nothing may run: pass B took
 // 0.60 instead of 0.34 ms beside the run-list kernels (profiles/r03_deflate_fork.log).
+//
+// The short pass of Z_RLE / Z_HUFFMAN_ONLY has no hash chains: no sort, no match kernels, no run lists.  Z_RLE keeps the run-length
+// words (without the sort's histograms), its own greedy parse, the walk and the symbols kernel; Z_HUFFMAN_ONLY writes its symbols
+// directly.  Both then share the trees, layout and emit of the long pass.  It has no side branch: everything but the Adler-32 sums
+// depends on the kernel before it, and the sums are a small fraction of the pass, so it runs on `st` alone whether or not a side
+// stream is given.
+static hipError_t launch_deflate_short(const DeflateArgs &a, int n, hipStream_t st)
+{
+	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
+	if (a.strategy == Z_RLE) {
+		hipLaunchKernelGGL(dfl_run_len_kernel<false>, dim3(gx, n), dim3(256), 0, st, a);  // run-length words
+		hipLaunchKernelGGL(dfl_rle_rec_kernel, dim3(gx, n), dim3(256), 0, st, a);
+		hipLaunchKernelGGL(dfl_offsets2_kernel, dim3(256), dim3(256), 0, st, a, n);
+		hipLaunchKernelGGL(dfl_walk_kernel, dim3(n), dim3(WALK_T), 0, st, a, n);
+		hipLaunchKernelGGL(dfl_symbols_kernel, dim3(gx, n), dim3(256), 0, st, a);
+	} else {
+		hipLaunchKernelGGL(dfl_huff_symbols_kernel, dim3(gx, n), dim3(256), 0, st, a);
+	}
+	hipLaunchKernelGGL(dfl_adler_kernel, dim3(n), dim3(256), 0, st, a);
+	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
+	hipLaunchKernelGGL(dfl_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a, n);
+	hipLaunchKernelGGL(dfl_emit_kernel, dim3(a.max_blocks, n), dim3(256), 0, st, a);
+	return hipGetLastError();
+}
+
 hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t sort_temp_bytes, hipStream_t st, hipStream_t side,
                           const hipEvent_t *ev)
 {
 	hipError_t e;
 	if ((e = hipMemsetAsync(a.out, 0, (size_t)n * a.out_stride, st)) != hipSuccess) return e;
+	if (short_pass(a.strategy)) return launch_deflate_short(a, n, st);
 	if ((e = hipMemsetAsync(a.sort_hist, 0, (size_t)n * 384 * 4, st)) != hipSuccess) return e;
 	hipLaunchKernelGGL(dfl_offsets_kernel, dim3(64), dim3(256), 0, st, a, n);  // (also zeroes run_counts)
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
 	(void)sort_temp; (void)sort_temp_bytes;
-	hipLaunchKernelGGL(dfl_run_len_kernel, dim3(gx, n), dim3(256), 0, st, a);       // run-length words, sort histograms, run-list counts
+	hipLaunchKernelGGL(dfl_run_len_kernel<true>, dim3(gx, n), dim3(256), 0, st, a);       // run-length words, sort histograms, run-list counts
 	hipLaunchKernelGGL(dfl_sort_pass_kernel<true>, dim3(n), dim3(1024), 0, st, a);   // in -> rec_in by hash & 255
 	hipLaunchKernelGGL(dfl_sort_pass_kernel<false>, dim3(n), dim3(1024), 0, st, a);  // -> rec_out by hash >> 8
 	const bool fork = side != nullptr && ev != nullptr;

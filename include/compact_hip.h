@@ -71,9 +71,18 @@ extern "C" {
 /* zlib level of the DEFLATE stage (config['encoder']['deflate_level'], an extension of the reference):
  * field 0 = level 9 (what the reference writes, and every caller that leaves the field clear),
  * 4 .. 9 = that level; 1 .. 3 and 10 .. 15 are refused with CCT_E_ARG.  The level shows only in the
- * second zlib header byte; the 13-byte .cct header is the same and zlib.decompress reads any level. */
+ * second zlib header byte; the 13-byte .cct header is the same and zlib.decompress reads any level.
+ * (Under strategies 2 and 3 below, levels 1 .. 3 are accepted too.) */
 #define CCT_FLAG_LEVEL_MASK 0xF00u
 #define CCT_FLAG_DEFLATE_LEVEL(l) ((((uint32_t)(l)) & 15u) << 8)
+/* zlib strategy of the DEFLATE stage (config['encoder']['deflate_strategy'], an extension of the reference), zlib.h's
+ * constants: field 0 = Z_DEFAULT_STRATEGY (every caller that leaves the field clear), 1 = Z_FILTERED,
+ * 2 = Z_HUFFMAN_ONLY, 3 = Z_RLE, 4 = Z_FIXED; 5 .. 7 are refused with CCT_E_ARG.  Strategies 0, 1 and 4 take
+ * the level field's levels 4 .. 9; 2 and 3 take levels 1 .. 9 (field 0 is still level 9) and write the same
+ * bytes at each.  The stream is deflateInit2(level, Z_DEFLATED, 15, 8, strategy)'s; the 13-byte .cct header
+ * does not change. */
+#define CCT_FLAG_STRATEGY_MASK 0x7000u
+#define CCT_FLAG_DEFLATE_STRATEGY(s) ((((uint32_t)(s)) & 7u) << 12)
 
 /* per-slice status bits written by the device kernels (0 = clean) */
 #define CCT_ST_Q7 1u         /* encode: a traversal delta outside [-2047,2048] was emitted; the
@@ -185,6 +194,15 @@ int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int 
 int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level,
                                   uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 
+/* cct_zlib_compress_batch at a zlib level and strategy: each stream is byte-identical to
+ * deflateInit2(level, Z_DEFLATED, 15, 8, strategy) + deflate(Z_FINISH) (zlib.compressobj(level, zlib.DEFLATED,
+ * 15, 8, strategy) in Python).  Strategies 0 (Z_DEFAULT_STRATEGY), 1 (Z_FILTERED) and 4 (Z_FIXED) take levels
+ * -1 and 4 .. 9; 2 (Z_HUFFMAN_ONLY) and 3 (Z_RLE) take -1 and 1 .. 9 and need no hash chains (a shorter device
+ * pass).  Level 0, levels 1 .. 3 with strategies 0, 1 and 4, and strategies outside 0 .. 4 return CCT_E_ARG
+ * before the device is touched.  Strategy 0 returns what cct_zlib_compress_batch_level returns. */
+int cct_zlib_compress_batch_strategy(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy,
+                                     uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+
 /* INFLATE stage alone, on the device: n zlib streams (h_in[h_offsets[i] .. h_offsets[i+1])) -> the bytes
  * zlib.decompress returns for each (what the reference calls at core.py:421).  Output i lands at
  * h_out + i*out_stride (out_stride a multiple of 16); h_status[i] = CCT_OK, CCT_E_ZLIB (anything libz
@@ -244,7 +262,7 @@ int cct_packbits_decode_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per
  * thread: an encode and a decode driven from two threads do not overwrite each other; takes no lock):
  * [0] encode kernel (HIP events on the library stream), [1] packed files device -> host, [2] DEFLATE (HIP events
- * on the device path, also after cct_zlib_compress_batch / _level; host wall on the libz path), [3] INFLATE
+ * on the device path, also after cct_zlib_compress_batch / _level / _strategy; host wall on the libz path), [3] INFLATE
  * (likewise), [4] decode kernel (HIP events),
  * [5] reserved. */
 int cct_last_timings(float *out6);

@@ -2,7 +2,9 @@
 """Fuzz run (not part of the product): random byte strings with many different statistics through the device
 DEFLATE (must equal zlib.compress(x, level) byte for byte, level 9 unless --levels names others) and through the
 device INFLATE (streams written by zlib with random level / strategy / window / flush points must inflate to the input).
-Usage: python tools/fuzz_codec.py [rounds] [seed] [--levels 4,5,6,7,8,9]"""
+--strategies also runs the device DEFLATE at zlib strategies 1 to 4 (each must equal
+zlib.compressobj(level, DEFLATED, 15, 8, strategy); levels 1 to 3 as well for Z_HUFFMAN_ONLY and Z_RLE).
+Usage: python tools/fuzz_codec.py [rounds] [seed] [--levels 4,5,6,7,8,9] [--strategies [1,2,3,4]]"""
 import argparse
 import os
 import sys
@@ -80,20 +82,31 @@ def main():
     ap.add_argument("rounds", nargs="?", type=int, default=20)
     ap.add_argument("seed", nargs="?", type=int, default=1)
     ap.add_argument("--levels", default="9", help="comma-separated zlib levels of the device DEFLATE (-1, 4 to 9)")
+    ap.add_argument("--strategies", nargs="?", const="1,2,3,4", default="",
+                    help="comma-separated zlib strategies besides the default (1 to 4), at the --levels they accept")
     args = ap.parse_args()
     rounds, seed = args.rounds, args.seed
     levels = [int(x) for x in args.levels.split(",")]
+    runs = [(lv, 0) for lv in levels]
+    for s in (int(x) for x in args.strategies.split(",") if x):
+        runs += [(lv, s) for lv in levels] + ([(lv, s) for lv in (1, 2, 3)] if s in (2, 3) else [])
+
+    def libz(b, level, strategy):
+        if strategy == 0:
+            return zlib.compress(b, level)
+        c = zlib.compressobj(level, zlib.DEFLATED, 15, 8, strategy)
+        return c.compress(b) + c.flush()
     rng = np.random.default_rng(seed)
     t0, nbad = time.time(), 0
     for r in range(rounds):
         blobs = [blob(rng) for _ in range(int(rng.integers(1, 48)))]
-        for level in levels:
-            got = cct_hip.zlib_compress_batch(blobs, level=level)
+        for level, strategy in runs:
+            got = cct_hip.zlib_compress_batch(blobs, level=level, strategy=strategy)
             for i, (b, g) in enumerate(zip(blobs, got)):
-                if g != zlib.compress(b, level):
+                if g != libz(b, level, strategy):
                     nbad += 1
-                    open(f"/tmp/fuzz_deflate_{seed}_{r}_{i}_l{level}.bin", "wb").write(b)
-                    print(f"DEFLATE MISMATCH round {r} blob {i} len {len(b)} level {level}", flush=True)
+                    open(f"/tmp/fuzz_deflate_{seed}_{r}_{i}_l{level}_s{strategy}.bin", "wb").write(b)
+                    print(f"DEFLATE MISMATCH round {r} blob {i} len {len(b)} level {level} strategy {strategy}", flush=True)
         streams = [stream(rng, b) for b in blobs]
         outs = cct_hip.zlib_decompress_batch(streams, max_out=max(16, max(len(b) for b in blobs)))
         for i, (b, o) in enumerate(zip(blobs, outs)):
