@@ -321,15 +321,22 @@ def decode_batch(files, config=None, out_dev=None):
     return out
 
 
-def zlib_compress_batch(blobs, level=9, strategy=0):
+def _check_mem_level(mem_level):
+    """zlib memLevel on the device: 8 (zlib's default) or 9 (Pillow's PNG writer), or ValueError"""
+    if isinstance(mem_level, bool) or not isinstance(mem_level, (int, np.integer)) or int(mem_level) not in (8, 9):
+        raise ValueError(f"zlib mem_level {mem_level!r}: the device runs memLevel 8 and 9")
+    return int(mem_level)
+
+
+def zlib_compress_batch(blobs, level=9, strategy=0, mem_level=8):
     """DEFLATE stage alone on the device: [bytes] -> [zlib streams], each byte-identical to
     zlib.compress(blob, level) -- level 9 by default (what the reference calls at core.py:340), 4 to 8, or
-    -1 for zlib's default 6.  Levels 0 to 3 are not on the device (ValueError).  strategy (zlib's Z_* constant, 0 to 4):
-    the stream of zlib.compressobj(level, zlib.DEFLATED, 15, 8, strategy); Z_HUFFMAN_ONLY (2) and Z_RLE (3) also take
-    levels 1 to 3."""
-    import zlib
+    -1 for zlib's default 6.  Levels 0 to 3 are not on the device (ValueError).  strategy (zlib's Z_* constant, 0 to 4)
+    and mem_level (8 or 9): the stream of zlib.compressobj(level, zlib.DEFLATED, 15, mem_level, strategy);
+    Z_HUFFMAN_ONLY (2) and Z_RLE (3) also take levels 1 to 3."""
     strategy = _check_strategy(strategy)
     level = _check_level(int(level), strategy)
+    mem_level = _check_mem_level(mem_level)
     L = _ffi.lib()
     n = len(blobs)
     if n == 0:
@@ -339,12 +346,105 @@ def zlib_compress_batch(blobs, level=9, strategy=0):
     data = b"".join(blobs) or b"\0"
     longest = max(len(b) for b in blobs)
     in_stride = (longest + 16 + 255) & ~255
-    out_stride = (len(zlib.compress(b"", 0)) + in_stride + (in_stride >> 12) + (in_stride >> 14) + (in_stride >> 25) + 13 + 128 + 63) & ~63
+    # compressBound at memLevel 8, deflateBound's general bound at 9 (api.cpp zlib_bound), + slack
+    if mem_level == 8:
+        bound = in_stride + (in_stride >> 12) + (in_stride >> 14) + (in_stride >> 25) + 13
+    else:
+        bound = in_stride + ((in_stride + 7) >> 3) + ((in_stride + 63) >> 6) + 11
+    out_stride = (bound + 11 + 128 + 63) & ~63
     out = np.empty((n, out_stride), dtype=np.uint8)
     sizes = np.zeros(n, dtype=np.uint32)
-    _ffi.check(L.cct_zlib_compress_batch_strategy(data, offs.ctypes.data, n, level, strategy, out.ctypes.data,
-                                                  out_stride, sizes.ctypes.data))
+    _ffi.check(L.cct_zlib_compress_batch_params(data, offs.ctypes.data, n, level, strategy, mem_level, out.ctypes.data,
+                                                out_stride, sizes.ctypes.data))
     return [out[i, : sizes[i]].tobytes() for i in range(n)]
+
+
+def _png_args(images, level, shift, shape):
+    """Validated (ptr, on_device, n, rows, cols, level, shift, keep) of png_encode_batch; raises before any device call."""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError(f"PNG compress_level must be an integer, got {level!r}")
+    level = int(level)
+    if level == -1:
+        level = 6
+    if not 4 <= level <= 9:
+        raise ValueError(f"PNG compress_level {level}: supported levels are -1 and 4 to 9 "
+                         "(0 to 3 are deflate_stored / deflate_fast, not on the device)")
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)):
+        raise TypeError(f"PNG sample shift must be an integer, got {shift!r}")
+    shift = int(shift)
+    if not 0 <= shift <= 15:
+        raise ValueError(f"PNG sample shift {shift}: 0 to 15")
+    if isinstance(images, DeviceBuffer):
+        if shape is None:
+            raise ValueError("png_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)")
+        shape = tuple(int(x) for x in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise ValueError(f"PNG batch shape {shape}: (n, rows, cols) or (rows, cols)")
+        n, rows, cols = shape
+        if n < 0 or n * rows * cols * 2 > images.nbytes:
+            raise ValueError(f"PNG batch shape {shape} does not fit the {images.nbytes}-byte DeviceBuffer")
+        ptr, on_device, keep = images.ptr, 1, images
+    else:
+        arr = np.asarray(images)
+        if arr.dtype != np.uint16:
+            raise TypeError(f"16-bit PNGs take uint16 samples, got {arr.dtype}")
+        if arr.ndim == 2:
+            arr = arr[None]
+        if arr.ndim != 3:
+            raise ValueError(f"PNG batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
+        n, rows, cols = arr.shape
+        _check_png_shape(rows, cols)  # before the copy below
+        arr = np.ascontiguousarray(arr)
+        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    _check_png_shape(rows, cols)
+    return ptr, on_device, n, rows, cols, level, shift, keep
+
+
+def _check_png_shape(rows, cols):
+    if rows < 1 or cols < 1:
+        raise ValueError(f"PNG of {rows} x {cols} samples: rows and cols must be >= 1")
+    if rows * (1 + 2 * cols) > (1 << 30) - 512:
+        raise ValueError(f"PNG of {rows} x {cols} samples: more filtered bytes than one device DEFLATE pass takes")
+
+
+def png_encode_batch(images, level=6, shift=0, shape=None):
+    """16-bit grayscale PNGs on the device: a uint16 array of shape (n, rows, cols) or (rows, cols), or a DeviceBuffer
+    with shape= given, -> a list of n `bytes`.  File i is byte-identical to what Pillow writes for
+    Image.fromarray(((img.astype(uint32) << shift) & 0xFFFF).astype(uint16)).save(f, "PNG", compress_level=level):
+    level -1 (= 6, Pillow's default) or 4 to 9.  The row filters are chosen and applied on the device, the zlib stream
+    is the device DEFLATE at memLevel 9 / Z_FILTERED (host libz under the device_deflate 0 option), and the chunks and
+    CRC-32s are written on the device.  Arguments are checked (TypeError / ValueError) before any device call."""
+    ptr, on_device, n, rows, cols, level, shift, keep = _png_args(images, level, shift, shape)
+    if n == 0:
+        return []
+    L = _ffi.lib()
+    out_stride = L.cct_png_bound(rows, cols)
+    out = np.empty((n, out_stride), dtype=np.uint8)
+    sizes = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_png_encode_batch(ptr, on_device, n, rows, cols, shift, level, out.ctypes.data, out_stride,
+                                      sizes.ctypes.data))
+    del keep
+    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+
+
+def decode_png_batch(files, config=None, level=9):
+    """The 16-bit previews of .cct files, the batch form of Decoder(config, bytes, out_path).decode() as the reference
+    writes them (imageio -> Pillow at compress_level 9, value << 4: core.py:522-538): files are decoded into HBM and
+    turned into PNGs there, without the rasters coming back to the host.  Returns a list of PNG `bytes`."""
+    config = config or default_config()
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError(f"PNG compress_level must be an integer, got {level!r}")
+    if not (int(level) == -1 or 4 <= int(level) <= 9):
+        raise ValueError(f"PNG compress_level {level}: supported levels are -1 and 4 to 9")
+    if not files:
+        return []
+    hdr = _ffi.Header()
+    _ffi.check(_ffi.lib().cct_read_header(files[0], len(files[0]), magic_bytes(config), C.byref(hdr)))
+    d_img = DeviceBuffer(max(2 * len(files) * hdr.width * hdr.height, 2))
+    n, w, h = decode_batch(files, config, out_dev=d_img)
+    return png_encode_batch(d_img, level=level, shift=4, shape=(n, w, h))
 
 
 def zlib_decompress_batch(streams, max_out, raise_errors=True):

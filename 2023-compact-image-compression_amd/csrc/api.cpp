@@ -84,6 +84,7 @@ struct EncSlot {
 	// device DEFLATE workspaces
 	DevBuf z_vals_in, z_vals_out, z_mr, z_rec, z_exitp, z_exitc, z_sym, z_bentry, z_bsym,
 	    z_small, z_bend, z_meta, z_tables, z_sorttmp, z_out, z_outsizes, z_in, z_insizes, z_packed, z_packoffs, z_gen, z_runs;
+	DevBuf png_img, png_out, png_sizes;  // PNG writer: rasters from the host, files, their sizes (cct_png_encode_batch)
 	// match records are valid by tag (deflate_kernels.hip MatchRec): the device counter z_gen has run z_gen_passes times since
 	// the buffer z_mr_cleared (z_mr at that time) was last zeroed together with it
 	const void *z_mr_cleared = nullptr;
@@ -104,7 +105,8 @@ struct EncSlot {
 		DevBuf *b[] = {&e_role, &e_lidx, &e_lmask, &e_lcur, &e_images, &e_payload, &e_sizes, &e_status, &e_stats, &e_pairrec,
 		               &e_hand, &h_stage, &z_vals_in, &z_vals_out, &z_mr, &z_rec, &z_exitp, &z_exitc,
 		               &z_sym, &z_bentry, &z_bsym, &z_small, &z_bend, &z_meta, &z_tables, &z_sorttmp, &z_out, &z_outsizes, &z_in,
-		               &z_insizes, &z_packed, &z_packoffs, &z_packed2[0], &z_packed2[1], &z_gen, &z_runs, &h_small[0], &h_small[1]};
+		               &z_insizes, &z_packed, &z_packoffs, &z_packed2[0], &z_packed2[1], &z_gen, &z_runs, &h_small[0], &h_small[1],
+		               &png_img, &png_out, &png_sizes};
 		for (DevBuf *p : b) all_bufs[n_bufs++] = p;
 		h_stage.pinned_host = true;
 		h_small[0].pinned_host = h_small[1].pinned_host = true;
@@ -725,21 +727,23 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 // passes, the run list, the block walk) left half of the 256 CUs idle.
 constexpr size_t DEFLATE_PASS_BYTES = (size_t)1 << 30;
 
-// DEFLATE (zlib stream of `level` and `strategy`: 4 .. 9 with strategies 0, 1, 4, 1 .. 9 with 2, 3) of n device-resident byte
-// strings on the device; output slice i = 13 header bytes + zlib stream at d_out + i*out_stride (E.z_out), sizes in E.z_outsizes.
+// DEFLATE (zlib stream of `level`, `strategy` and `mem_level`: 4 .. 9 with strategies 0, 1, 4, 1 .. 9 with 2, 3; memLevel 8 or 9)
+// of n device-resident byte strings on the device; output slice i = 13 header bytes + zlib stream at d_out + i*out_stride
+// (E.z_out), sizes in E.z_outsizes.
 int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint32_t *d_in_sizes, int n, const uint8_t header13[13],
-                   size_t out_stride, int level, int strategy)
+                   size_t out_stride, int level, int strategy, int mem_level = 8)
 {
 	if (in_stride % 256 != 0 || out_stride % 4 != 0) return fail(CCT_E_ARG, "deflate strides must be multiples of 256 / 4");
 	DeflateArgs a{};
 	if (!deflate_strategy_args(level, strategy, a))
 		return fail(CCT_E_ARG, "zlib level %d with strategy %d is not on the device", level, strategy);
+	if (!deflate_mem_level_args(mem_level, a)) return fail(CCT_E_ARG, "zlib memLevel %d: 8 and 9 are on the device", mem_level);
 	// Z_HUFFMAN_ONLY / Z_RLE: the short pass (launch_deflate) uses no sort records, match records, run lists or queues, and
 	// Z_HUFFMAN_ONLY no decision records or walk either: those workspaces are neither grown nor cleared for it
 	const bool chains = strategy != 2 && strategy != 3, walk = strategy != 2;
 	const size_t EB = (size_t)n * in_stride;
 	if (EB >= ((size_t)1 << 32)) return fail(CCT_E_ARG, "deflate batch of %zu bytes exceeds the 4 GiB sort limit; split the batch", EB);
-	const int max_blocks = (int)(in_stride / 16383 + 2);
+	const int max_blocks = (int)(in_stride / a.block_syms + 2);
 	int rc;
 	if (chains) {
 		if ((rc = E.z_vals_in.ensure(EB * 8))) return rc;   // records between the two sort passes, then run_ends + run_len
@@ -756,8 +760,8 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 		if ((rc = E.z_bsym.ensure(EB / 64 * 4))) return rc;
 	}
 	const int run_chunks = (int)(in_stride / 1784 + 1);  // chunks of dfl_run_len_kernel (RUNLEN_OUT positions) per slice
-	if ((rc = E.z_small.ensure((size_t)n * (9 + 384 + 2 * (size_t)run_chunks) * 4))) return rc;
-	if ((rc = E.z_bend.ensure((size_t)n * max_blocks * 4))) return rc;
+	if ((rc = E.z_small.ensure((size_t)n * (9 + SORT_HIST + 2 * (size_t)run_chunks) * 4))) return rc;
+	if ((rc = E.z_bend.ensure((size_t)n * max_blocks * 8))) return rc;  // block ends, then the loop tops of their flushes
 	if ((rc = E.z_meta.ensure((size_t)n * max_blocks * sizeof(BlockMeta)))) return rc;
 	if ((rc = E.z_tables.ensure((size_t)n * max_blocks * sizeof(BlockTables)))) return rc;
 	if ((rc = E.z_out.ensure((size_t)n * out_stride))) return rc;
@@ -774,11 +778,14 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 	}
 	a.in = d_in; a.in_stride = in_stride; a.in_sizes = d_in_sizes;
 	a.rec_in = (uint64_t *)E.z_vals_in.p; a.rec_out = (uint64_t *)E.z_vals_out.p;
-	a.pos_mask = (g_ctx.compact_recs && in_stride < ((size_t)1 << 22)) ? (1u << 22) - 1u : 0xFFFFFFFFu;
+	// compact sort records hold a 15-bit hash: memLevel 8 only (deflate_kernels.hip "Sort records").  A compact record for the
+	// 16-bit hash would need a 20-bit position field.  memLevel 9 serves the PNG writer, and on filtered PNG rows compact records
+	// do not pay even at memLevel 8 (61.7 against 61.0 ms per 256 slices at level 6)
+	a.pos_mask = (g_ctx.compact_recs && mem_level == 8 && in_stride < ((size_t)1 << 22)) ? (1u << 22) - 1u : 0xFFFFFFFFu;
 	uint32_t *small = (uint32_t *)E.z_small.p;
 	a.seg_begin = small; a.seg_end = small + n; a.total_syms = small + 2 * n; a.postloop_lit = small + 3 * n;
 	a.n_blocks = small + 4 * n; a.adler = small + 5 * n; a.heavy_count = small + 6 * n; a.deep_count = small + 7 * n; a.run_end_count = small + 8 * n; a.sort_hist = small + 9 * n;
-	a.run_counts = small + (9 + 384) * (size_t)n; a.run_chunks = run_chunks;
+	a.run_counts = small + (9 + SORT_HIST) * (size_t)n; a.run_chunks = run_chunks;
 	// the tag of a pass must not meet a record of 16383 passes ago: clear records and counter well before it comes round (and
 	// whenever the buffer is new); a pass that failed on the way may have left the two counts a few apart, hence the margin
 	// (a short pass neither reads match records nor advances the tag: it does not count)
@@ -795,7 +802,7 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 	a.run_len = (uint16_t *)E.z_sym.p;  // 2 EB, written before the sort and dead before the symbols are
 	a.rec32 = (uint32_t *)E.z_exitp.p; a.exit_pos = (uint32_t *)E.z_exitc.p; a.exit_cnt = (uint32_t *)E.z_rec.p;  // the heavy/deep queues are dead once dfl_rec_kernel runs
 	a.blk_entry = (uint32_t *)E.z_bentry.p; a.blk_symbase = (uint32_t *)E.z_bsym.p;
-	a.blk_end = (uint32_t *)E.z_bend.p;
+	a.blk_end = (uint32_t *)E.z_bend.p; a.blk_top = a.blk_end + (size_t)n * max_blocks;
 	a.block_meta = (BlockMeta *)E.z_meta.p; a.block_tables = (BlockTables *)E.z_tables.p;
 	a.max_blocks = max_blocks;
 	a.out = (uint8_t *)E.z_out.p; a.out_stride = out_stride; a.out_sizes = (uint32_t *)E.z_outsizes.p;
@@ -1550,8 +1557,17 @@ int cct_encode_batch_packed(const uint16_t *images, int images_on_device, int n,
 	                         bytes_per_channel, h_archive, archive_cap, h_out_sizes, h_status, h_payload_sizes, h_stats, h_offsets);
 }
 
-static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy, uint8_t *h_out,
-                                    size_t out_stride, uint32_t *h_out_sizes)
+// Bytes a zlib stream of n input bytes can take: compressBound at memLevel 8 (deflateBound's tight bound for the default
+// parameters), deflateBound's general bound otherwise.  memLevel 9's 32767-symbol blocks can straddle a slide of the window,
+// where zlib may not store them: random bytes under Z_FILTERED come out 0.09 % above compressBound.
+static size_t zlib_bound(size_t n, int mem_level)
+{
+	if (mem_level == 8) return compressBound((uLong)n);
+	return n + ((n + 7) >> 3) + ((n + 63) >> 6) + 5 + 6;
+}
+
+static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy, int mem_level,
+                                    uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
 {
 	std::lock_guard<std::mutex> lk(g_mu);
 	ApiCall in_call;
@@ -1563,7 +1579,7 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 	size_t longest = 0;
 	for (int i = 0; i < n; i++) longest = std::max(longest, (size_t)(h_offsets[i + 1] - h_offsets[i]));
 	const size_t in_stride = (longest + 16 + 255) & ~(size_t)255;
-	const size_t zstride = (13 + compressBound((uLong)in_stride) + 63) & ~(size_t)63;
+	const size_t zstride = (13 + zlib_bound(in_stride, mem_level) + 63) & ~(size_t)63;
 	if (out_stride < zstride - 13) return fail(CCT_E_CAP, "out_stride %zu too small (need %zu)", out_stride, zstride - 13);
 	if ((rc = E.z_in.ensure((size_t)n * in_stride))) return rc;
 	if ((rc = E.z_insizes.ensure((size_t)n * 4))) return rc;
@@ -1585,7 +1601,8 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 	HIP_TRY(hipEventCreate(&ev.e[0]));
 	HIP_TRY(hipEventCreate(&ev.e[1]));
 	HIP_TRY(hipEventRecord(ev.e[0], E.stream));
-	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride, level, strategy);
+	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride, level, strategy,
+	                    mem_level);
 	if (rc) return rc;
 	HIP_TRY(hipEventRecord(ev.e[1], E.stream));
 	HIP_TRY(hipMemcpyAsync(osz.data(), E.z_outsizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
@@ -1603,7 +1620,7 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, uint8_t *h_out, size_t out_stride,
                             uint32_t *h_out_sizes)
 {
-	return zlib_compress_batch_impl(h_in, h_offsets, n, 9, Z_DEFAULT_STRATEGY, h_out, out_stride, h_out_sizes);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, 9, Z_DEFAULT_STRATEGY, 8, h_out, out_stride, h_out_sizes);
 }
 
 int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, uint8_t *h_out,
@@ -1612,12 +1629,19 @@ int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets
 	if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION
 	if (level >= 0 && level <= 3) return fail(CCT_E_ARG, "zlib level %d: deflate_stored / deflate_fast: not on the device", level);
 	if (level < 4 || level > 9) return fail(CCT_E_ARG, "zlib level %d: levels are -1 and 4 .. 9", level);
-	return zlib_compress_batch_impl(h_in, h_offsets, n, level, Z_DEFAULT_STRATEGY, h_out, out_stride, h_out_sizes);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, level, Z_DEFAULT_STRATEGY, 8, h_out, out_stride, h_out_sizes);
 }
 
 int cct_zlib_compress_batch_strategy(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy,
                                      uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
 {
+	return cct_zlib_compress_batch_params(h_in, h_offsets, n, level, strategy, 8, h_out, out_stride, h_out_sizes);
+}
+
+int cct_zlib_compress_batch_params(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy, int mem_level,
+                                   uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
+{
+	if (mem_level != 8 && mem_level != 9) return fail(CCT_E_ARG, "zlib memLevel %d: 8 and 9 are on the device", mem_level);
 	if (strategy < Z_DEFAULT_STRATEGY || strategy > Z_FIXED)
 		return fail(CCT_E_ARG, "zlib strategy %d: strategies are 0 .. 4 (Z_DEFAULT_STRATEGY .. Z_FIXED)", strategy);
 	if (level == -1) level = 6;  // Z_DEFAULT_COMPRESSION
@@ -1625,7 +1649,127 @@ int cct_zlib_compress_batch_strategy(const uint8_t *h_in, const uint64_t *h_offs
 	if (level < 0 || level > 9) return fail(CCT_E_ARG, "zlib level %d with strategy %d: levels are -1 and 1 .. 9", level, strategy);
 	if (strategy != Z_HUFFMAN_ONLY && strategy != Z_RLE && level <= 3)
 		return fail(CCT_E_ARG, "zlib level %d with strategy %d: deflate_fast: not on the device (levels -1 and 4 .. 9)", level, strategy);
-	return zlib_compress_batch_impl(h_in, h_offsets, n, level, strategy, h_out, out_stride, h_out_sizes);
+	return zlib_compress_batch_impl(h_in, h_offsets, n, level, strategy, mem_level, h_out, out_stride, h_out_sizes);
+}
+
+// ---- PNG writer (png_kernels.hip) ---------------------------------------------------------------
+// Pillow's PNG stream: zlib.compressobj(level, DEFLATED, 15, memLevel 9, Z_FILTERED) (ZipEncode.c); IDAT chunks of the
+// bufsize of ImageFile._save, max(65536, 4 * cols) bytes.  One DEFLATE pass takes at most DEFLATE_PASS_BYTES of filtered rows.
+constexpr int PNG_MEM_LEVEL = 9;
+constexpr size_t PNG_MAX_FILTERED = DEFLATE_PASS_BYTES - 512;
+static size_t png_filtered_bytes(int rows, int cols) { return (size_t)rows * (1 + 2 * (size_t)cols); }
+static size_t png_in_stride(size_t filtered) { return (filtered + 16 + 255) & ~(size_t)255; }
+static size_t png_zstride(size_t in_stride) { return (13 + zlib_bound(in_stride, PNG_MEM_LEVEL) + 63) & ~(size_t)63; }
+static uint32_t png_chunk(int cols) { return (uint32_t)std::max<size_t>(65536, 4 * (size_t)cols); }
+// signature + IHDR (33), the stream, 12 bytes per IDAT chunk, IEND (12)
+static size_t png_file_bytes(size_t zlen, uint32_t chunk) { return 33 + zlen + 12 * ((zlen + chunk - 1) / chunk) + 12; }
+
+size_t cct_png_bound(int rows, int cols)
+{
+	if (rows < 1 || cols < 1 || png_filtered_bytes(rows, cols) > PNG_MAX_FILTERED) return 0;
+	return (png_file_bytes(png_zstride(png_in_stride(png_filtered_bytes(rows, cols))) - 13, png_chunk(cols)) + 63) & ~(size_t)63;
+}
+
+int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, int rows, int cols, int shift, int level,
+                         uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
+{
+	if (level == -1) level = 6;  // Pillow's compress_level default (Z_DEFAULT_COMPRESSION)
+	if (level >= 0 && level <= 3) return fail(CCT_E_ARG, "PNG compress_level %d: deflate_stored / deflate_fast: not on the device", level);
+	if (level < 4 || level > 9) return fail(CCT_E_ARG, "PNG compress_level %d: levels are -1 and 4 .. 9", level);
+	if (shift < 0 || shift > 15) return fail(CCT_E_ARG, "PNG sample shift %d: 0 .. 15", shift);
+	if (rows < 1 || cols < 1) return fail(CCT_E_ARG, "PNG shape %d x %d: rows and cols must be >= 1", rows, cols);
+	if (png_filtered_bytes(rows, cols) > PNG_MAX_FILTERED)
+		return fail(CCT_E_ARG, "PNG shape %d x %d: %zu filtered bytes exceed one DEFLATE pass (%zu)", rows, cols,
+		            png_filtered_bytes(rows, cols), PNG_MAX_FILTERED);
+	if (n < 0) return fail(CCT_E_ARG, "negative batch size");
+	if (!images && n > 0) return fail(CCT_E_ARG, "images is required");
+	const size_t bound = cct_png_bound(rows, cols);
+	if (out_stride < bound) return fail(CCT_E_CAP, "out_stride %zu too small (need cct_png_bound = %zu)", out_stride, bound);
+	std::lock_guard<std::mutex> lk(g_mu);
+	ApiCall in_call;
+	int rc = ensure_ctx();
+	if (rc) return rc;
+	if (n == 0) return CCT_OK;
+	EncSlot &E = g_enc[0];
+	const size_t F = png_filtered_bytes(rows, cols), in_stride = png_in_stride(F), zstride = png_zstride(in_stride);
+	const size_t img_bytes = (size_t)rows * cols * 2;
+	const uint32_t chunk = png_chunk(cols);
+	const size_t pstride = png_file_bytes(zstride - 13, chunk);
+	const uint32_t max_chunks = (uint32_t)((zstride - 13 + chunk - 1) / chunk);
+	const int per_pass = (int)std::max<size_t>(1, DEFLATE_PASS_BYTES / in_stride);
+	const bool host_img = !images_on_device;
+	PngPackArgs pk{};
+	pk.chunk = chunk;
+	{  // IHDR: width, height, depth 16, color type 0 (grayscale), compression 0, filter 0, interlace 0
+		uint8_t *h = pk.ihdr;
+		const uint8_t fixed[8] = {0, 0, 0, 13, 'I', 'H', 'D', 'R'};
+		memcpy(h, fixed, 8);
+		const uint32_t w = (uint32_t)cols, ht = (uint32_t)rows;
+		const uint8_t data[13] = {(uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w,
+		                          (uint8_t)(ht >> 24), (uint8_t)(ht >> 16), (uint8_t)(ht >> 8), (uint8_t)ht, 16, 0, 0, 0, 0};
+		memcpy(h + 8, data, 13);
+		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), h + 4, 17);
+		h[21] = (uint8_t)(crc >> 24); h[22] = (uint8_t)(crc >> 16); h[23] = (uint8_t)(crc >> 8); h[24] = (uint8_t)crc;
+	}
+	DrainOnExit drain(E.stream);
+	std::vector<uint32_t> sizes;
+	std::vector<uint8_t> host_rows, host_z;
+	for (int c0 = 0; c0 < n; c0 += per_pass) {
+		const int nc = std::min(per_pass, n - c0);
+		if ((rc = E.z_in.ensure((size_t)nc * in_stride))) return rc;
+		if ((rc = E.z_insizes.ensure((size_t)nc * 4))) return rc;
+		if ((rc = E.png_out.ensure((size_t)nc * pstride))) return rc;
+		if ((rc = E.png_sizes.ensure((size_t)nc * 4))) return rc;
+		const uint16_t *d_img = images + (size_t)c0 * rows * cols;
+		if (host_img) {
+			if ((rc = E.png_img.ensure((size_t)nc * img_bytes))) return rc;
+			HIP_TRY(hipMemcpyAsync(E.png_img.p, d_img, (size_t)nc * img_bytes, hipMemcpyHostToDevice, E.stream));
+			d_img = (const uint16_t *)E.png_img.p;
+		}
+		sizes.assign((size_t)nc, (uint32_t)F);
+		HIP_TRY(hipMemcpyAsync(E.z_insizes.p, sizes.data(), (size_t)nc * 4, hipMemcpyHostToDevice, E.stream));
+		HIP_TRY(launch_png_filter(d_img, nc, rows, cols, shift, (uint8_t *)E.z_in.p, in_stride, E.stream));
+		if (g_ctx.device_deflate) {
+			const uint8_t hdr13[13] = {0};
+			rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, nc, hdr13, zstride, level,
+			                    Z_FILTERED, PNG_MEM_LEVEL);
+			if (rc) return rc;
+		} else {  // host libz: the filtered rows come back, the streams go out to the pack kernel in the device pass's layout
+			if ((rc = E.z_out.ensure((size_t)nc * zstride))) return rc;
+			if ((rc = E.z_outsizes.ensure((size_t)nc * 4))) return rc;
+			host_rows.resize((size_t)nc * in_stride);
+			host_z.resize((size_t)nc * zstride);
+			HIP_TRY(hipMemcpyAsync(host_rows.data(), E.z_in.p, (size_t)nc * in_stride, hipMemcpyDeviceToHost, E.stream));
+			HIP_TRY(hipStreamSynchronize(E.stream));
+			std::atomic<int> zerr(0);
+			parallel_for(nc, g_ctx.zlib_threads, [&](int i) {
+				z_stream zs{};
+				int zr = deflateInit2(&zs, level, Z_DEFLATED, 15, PNG_MEM_LEVEL, Z_FILTERED);
+				if (zr != Z_OK) { zerr.store(zr); sizes[i] = 13; return; }
+				zs.next_in = host_rows.data() + (size_t)i * in_stride; zs.avail_in = (uInt)F;
+				zs.next_out = host_z.data() + (size_t)i * zstride + 13; zs.avail_out = (uInt)(zstride - 13);
+				zr = deflate(&zs, Z_FINISH);
+				sizes[i] = 13 + (uint32_t)zs.total_out;
+				(void)deflateEnd(&zs);
+				if (zr != Z_STREAM_END) { zerr.store(zr == Z_OK ? Z_BUF_ERROR : zr); sizes[i] = 13; }
+			});
+			if (zerr.load()) return fail(CCT_E_ZLIB, "deflate failed (%d)", zerr.load());
+			HIP_TRY(hipMemcpyAsync(E.z_out.p, host_z.data(), (size_t)nc * zstride, hipMemcpyHostToDevice, E.stream));
+			HIP_TRY(hipMemcpyAsync(E.z_outsizes.p, sizes.data(), (size_t)nc * 4, hipMemcpyHostToDevice, E.stream));
+		}
+		pk.src = (const uint8_t *)E.z_out.p; pk.src_stride = zstride; pk.src_skip = 13; pk.src_sizes = (const uint32_t *)E.z_outsizes.p;
+		pk.out = (uint8_t *)E.png_out.p; pk.out_stride = pstride; pk.out_sizes = (uint32_t *)E.png_sizes.p;
+		HIP_TRY(launch_png_pack(pk, nc, max_chunks, E.stream));
+		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, E.png_sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, E.stream));
+		HIP_TRY(hipStreamSynchronize(E.stream));
+		for (int i = 0; i < nc; i++) {
+			if (h_out_sizes[c0 + i] > pstride) return fail(CCT_E_DEVICE, "PNG %d: size %u beyond its stride", c0 + i, h_out_sizes[c0 + i]);
+			HIP_TRY(hipMemcpyAsync(h_out + (size_t)(c0 + i) * out_stride, (uint8_t *)E.png_out.p + (size_t)i * pstride,
+			                       h_out_sizes[c0 + i], hipMemcpyDeviceToHost, E.stream));
+		}
+		HIP_TRY(hipStreamSynchronize(E.stream));
+	}
+	return CCT_OK;
 }
 
 // take a free decode slot (see DecSlot)

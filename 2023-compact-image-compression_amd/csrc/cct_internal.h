@@ -164,12 +164,13 @@ struct DeflateArgs {
 	uint32_t *gen;                                                   // device counter of the passes run on this mr buffer, 1 .. 16383 (deflate_kernels.hip MatchRec)
 	uint32_t *heavy_list, *sym, *run_ends;                           // n * in_stride each
 	uint32_t *run_counts; int run_chunks;                            // n * 2 * run_chunks right behind sort_hist: run ends / starts per chunk of 1784 positions (run_chunks = chunks per slice)
-	uint32_t *sort_hist;                                             // n * 384: per slice the histograms of hash & 255 and of hash >> 8 (dfl_run_len_kernel -> sort passes)
+	uint32_t *sort_hist;                                             // n * SORT_HIST: per slice the histograms of hash & 255 and of hash >> 8 (dfl_run_len_kernel -> sort passes)
 	uint16_t *run_len;                                               // n * in_stride: equal bytes ahead (<= 258) | has_prev << 15
 	uint32_t *rec32, *exit_pos, *exit_cnt;                           // n * in_stride each
 	uint32_t *blk_entry, *blk_symbase;                               // n * in_stride / 64
 	uint32_t *total_syms, *postloop_lit, *n_blocks, *adler, *heavy_count, *deep_count, *run_end_count;  // n
 	uint32_t *blk_end;                                               // n * max_blocks
+	uint32_t *blk_top;                                               // n * max_blocks: position at the top of the loop iteration that flushed the block (dfl_tree_kernel, window_base)
 	BlockMeta *block_meta; BlockTables *block_tables;                // n * max_blocks
 	int max_blocks;
 	uint8_t *out; size_t out_stride; uint32_t *out_sizes;            // whole .cct files (header + zlib stream)
@@ -179,9 +180,15 @@ struct DeflateArgs {
 	// the zlib strategy (0 .. 4, deflate_kernels.hip "zlib strategies") and the shortest match deflate_slow keeps:
 	// MIN_MATCH, or 6 under Z_FILTERED (matches of <= 5 bytes dropped)
 	uint32_t strategy, min_len;
+	// the zlib memLevel (8 or 9): hash bits (memLevel + 7) and symbols per block (lit_bufsize - 1)
+	uint32_t hash_bits, block_syms;
 };
+// sort histogram words per slice: 256 digits of hash & 255, then up to 256 of hash >> 8 (16-bit hash, memLevel 9)
+constexpr int SORT_HIST = 512;
 // a level's fields of DeflateArgs (deflate_kernels.hip); false for levels outside 4 .. 9
 bool deflate_level_args(int level, DeflateArgs &a);
+// a memLevel's fields of DeflateArgs; false for anything but 8 and 9
+bool deflate_mem_level_args(int mem_level, DeflateArgs &a);
 // the fields of a (level, strategy) pair: levels 4 .. 9 with strategies 0, 1 and 4 (deflate_slow), levels 1 .. 9 with 2
 // and 3 (deflate_huff / deflate_rle, which read no level table); false for anything else
 bool deflate_strategy_args(int level, int strategy, DeflateArgs &a);
@@ -191,6 +198,20 @@ hipError_t launch_pack(const uint8_t *src, size_t stride, const uint32_t *sizes,
                        int exact, hipStream_t st);
 hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t sort_temp_bytes, hipStream_t st, hipStream_t side = nullptr,
                           const hipEvent_t *fork_join_events = nullptr);  // side + four events (no timing): independent kernels side by side
+
+// ---- PNG writer (png_kernels.hip) -----------------------------------------------------------------
+// n rasters (rows x cols uint16, C order) -> filter byte + filtered big-endian row, rows * (1 + 2 cols) bytes at d_out + i*out_stride
+hipError_t launch_png_filter(const uint16_t *d_img, int n, int rows, int cols, int shift, uint8_t *d_out, size_t out_stride,
+                             hipStream_t st);
+struct PngPackArgs {
+	const uint8_t *src; size_t src_stride; uint32_t src_skip;  // zlib stream i = src + i*src_stride + src_skip ..
+	const uint32_t *src_sizes;                                 // .. of src_sizes[i] - src_skip bytes (device)
+	uint32_t chunk;                                            // IDAT data bytes per chunk: max(65536, 4 cols)
+	uint8_t ihdr[25];                                          // IHDR chunk: length, type, data, CRC
+	uint8_t *out; size_t out_stride; uint32_t *out_sizes;      // PNG files (device)
+};
+// grid: max_chunks >= the IDAT chunks of the longest stream
+hipError_t launch_png_pack(const PngPackArgs &a, int n, uint32_t max_chunks, hipStream_t st);
 
 // ---- gate between the decode and the encode stream (sched_kernels.hip) ---------------------------
 hipError_t launch_gate_bump(uint32_t *word, hipStream_t st);

@@ -1,5 +1,5 @@
-// Device DEFLATE, byte-identical to zlib 1.2.11 `deflateInit2(level L, Z_DEFLATED, wbits 15, memLevel 8,
-// strategy S)` + one-shot Z_FINISH for L = 4 .. 9 -- level 9 with the default strategy is the stream CPython's
+// Device DEFLATE, byte-identical to zlib 1.2.11 `deflateInit2(level L, Z_DEFLATED, wbits 15, memLevel M,
+// strategy S)` + one-shot Z_FINISH for L = 4 .. 9 and M = 8 or 9 -- level 9 with the default strategy is the stream CPython's
 // zlib.compress(data, level=9) produces for the reference (src/codec/core.py:340).  zlib is a third-party dependency of the
 // reference and is not vendored there; the algorithm is restated here in data-parallel form (CPU model
 // of the same restatement, pinned against libz: oracle/deflate_model.c for level 9,
@@ -12,7 +12,12 @@
 // Z_RLE (deflate_rle: greedy matches at distance 1 only) and Z_HUFFMAN_ONLY (deflate_huff: literals only) run at any
 // level 1 .. 9 with the same bytes, as a short pass without the sort and match kernels (launch_deflate).
 //
-//   sort      stable two-pass LSD radix sort of (hash, position) per slice, the 15-bit rolling hash of 3 bytes
+// zlib memLevel (DeflateArgs::hash_bits, block_syms): memLevel 8 hashes 3 bytes into 15 bits (hash_shift 5) and ends a block
+// after 16383 tallied symbols; memLevel 9 into 16 bits (hash_shift 6), blocks of 32767 symbols.  Nothing else of deflate_slow,
+// deflate_rle or deflate_huff depends on it.  The kernels that need the widths at compile time take them as template arguments
+// (HB = hash bits, BS = block symbols); memLevel 9 runs on wide sort records only (api.cpp deflate_locked, "Sort records").
+//
+//   sort      stable two-pass LSD radix sort of (hash, position) per slice, the 15- or 16-bit rolling hash of 3 bytes
 //             (deflate.c UPDATE_HASH) computed on the fly: a bucket in position order IS zlib's hash chain
 //             (head/prev), walked backwards
 //   runs      ordered list of the runs of >= 3 equal bytes and, per position, the equal bytes ahead
@@ -27,7 +32,7 @@
 //             doubling (entry -> exit, symbol count), the block-to-block hop chain is walked
 //             speculatively by 256 lanes per slice
 //   symbols   visited positions emit literals / (length, distance) pairs in stream order
-//   trees     per 16383-symbol block: histograms, then build_tree / gen_bitlen / gen_codes /
+//   trees     per 16383- (32767-) symbol block: histograms, then build_tree / gen_bitlen / gen_codes /
 //             scan_tree / build_bl_tree exactly as trees.c (the heap is replayed: ties are decided by heap
 //             position), stored / static / dynamic choice
 //   emit      code bits of every symbol at its prefix-summed bit offset; zlib header, Adler-32
@@ -46,7 +51,8 @@ constexpr int MIN_MATCH = 3, MAX_MATCH = 258, WSIZE = 32768;
 constexpr int MIN_LOOKAHEAD = MAX_MATCH + MIN_MATCH + 1;
 constexpr int MAX_DIST = WSIZE - MIN_LOOKAHEAD;  // 32506
 constexpr int TOO_FAR = 4096;
-constexpr int BLOCK_SYMS = 16383;                // lit_bufsize - 1 (memLevel 8)
+constexpr int BLOCK_SYMS = 16383;                // lit_bufsize - 1 (memLevel 8; DeflateArgs::block_syms at run time)
+constexpr int BLOCK_SYMS_ML9 = 32767;            // lit_bufsize - 1 (memLevel 9)
 constexpr int L_CODES = 286, D_CODES = 30, BL_CODES = 19, HEAP_SIZE = 2 * L_CODES + 1;
 constexpr int END_BLOCK = 256, MAX_BITS = 15, MAX_BL_BITS = 7;
 constexpr uint32_t Z_FILTERED = 1, Z_HUFFMAN_ONLY = 2, Z_RLE = 3, Z_FIXED = 4;  // zlib.h strategies
@@ -65,6 +71,15 @@ __constant__ uint16_t c_base_dist[30];
 __constant__ uint16_t c_static_lcode[288];
 __constant__ uint8_t c_static_llen[288];
 __constant__ uint16_t c_static_dcode[30];
+
+// deflate.c UPDATE_HASH over the three bytes of a string: hash_bits HB = memLevel + 7, hash_shift = (HB + 2) / 3.  The shift
+// is at least HB / 3, so the hash of any earlier byte has left the mask: the three bytes alone decide it
+template <int HB>
+__device__ __forceinline__ uint32_t hash3(uint32_t b0, uint32_t b1, uint32_t b2)
+{
+	constexpr int SH = (HB + 2) / 3;
+	return ((b0 << (2 * SH)) ^ (b1 << SH) ^ b2) & ((1u << HB) - 1u);
+}
 
 __device__ __forceinline__ int d_code(uint32_t dist) { return dist < 256 ? c_dist_code[dist] : c_dist_code[256 + (dist >> 7)]; }
 
@@ -98,7 +113,7 @@ __device__ __forceinline__ MatchRec checked_match(MatchRec r, uint32_t gen, uint
 }
 
 // ------------------------------------------------------------------ 1. hash + sort by (hash, position)
-// The chain of a string = the earlier strings with the same 15-bit hash, most recent first (deflate.c
+// The chain of a string = the earlier strings with the same 15-bit (16-bit) hash, most recent first (deflate.c
 // INSERT_STRING / prev[]).  Sorting the positions of a slice by (hash, position) lays every chain out as a
 // contiguous run.  Stable LSD radix sort in two passes (hash & 255, then hash >> 8); ONE workgroup of 1024 lanes
 // per slice walks its slice tile by tile with running digit offsets in LDS, so there is no cross-workgroup
@@ -120,10 +135,11 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 	return v;
 }
 
-template <bool FIRST>
+template <bool FIRST, int HB>
 __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 {
-	constexpr int BITS = FIRST ? 8 : 7, NB = 1 << BITS;
+	constexpr int BITS = FIRST ? 8 : HB - 8, NB = 1 << BITS;
+	constexpr uint32_t HMASK = (1u << HB) - 1u;
 	__shared__ uint32_t offs[256];
 	__shared__ uint32_t wcnt[16][NB];
 	const int s = blockIdx.x;
@@ -142,7 +158,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 	__syncthreads();
 	// digit histogram of this pass: counted by dfl_run_len_kernel, which reads the input in position order with the whole chip
 	// (here one workgroup per slice would wait for its loads, and pass A paid an LDS atomic per element for pass B's histogram)
-	if (tid < NB) offs[tid] = a.sort_hist[(size_t)s * 384 + (FIRST ? 0 : 256) + tid];
+	if (tid < NB) offs[tid] = a.sort_hist[(size_t)s * SORT_HIST + (FIRST ? 0 : 256) + tid];
 	__syncthreads();
 	if (wave == 0) {  // exclusive scan of up to 256 bins: 4 per lane
 		uint32_t v[4], sum = 0;
@@ -182,7 +198,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 #ifdef CCT_SORT_PROBE  // tuning builds only (results invalid)
 	const bool compact = false;
 #else
-	const bool compact = a.pos_mask != 0xFFFFFFFFu;
+	const bool compact = HB == 15 && a.pos_mask != 0xFFFFFFFFu;  // (memLevel 8 only)
 #endif
 	const uint32_t dmax = (uint32_t)a.in_stride - 4u;
 	// tile_base = first element of this wave's 256; ra/rb = the values as loaded: anything computed here is computed (and waited for) early
@@ -201,7 +217,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 			}
 		}
 	};
-	// h = upper record word (hash in bits 0..14), p = lower record word (position in the bits of a.pos_mask): see "Sort records"
+	// h = upper record word (hash in bits 0 .. HB-1), p = lower record word (position in the bits of a.pos_mask): see "Sort records"
 	auto finish = [&](uint32_t tile_base, const uint32_t (&ra)[E], const uint32_t (&rb)[E], uint32_t (&h)[E], uint32_t (&p)[E]) {
 #pragma unroll
 		for (int e = 0; e < E; e++) {
@@ -217,7 +233,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 				const uint32_t sh = (uint32_t)lane & 3u;
 				const uint32_t w = __builtin_amdgcn_alignbyte(db, da, sh);  // bytes idx .. idx + 3
 				const uint32_t b0 = w & 255u, b1 = (w >> 8) & 255u, b2 = (w >> 16) & 255u;
-				h[e] = ((b0 << 10) ^ (b1 << 5) ^ b2) & 0x7FFFu; p[e] = idx;
+				h[e] = hash3<HB>(b0, b1, b2); p[e] = idx;
 				if (compact) {
 					// bytes 3 and 4 -- or, for a string that starts with three equal bytes (those go to the run matcher, nobody
 					// compares their bytes 3 and 4), the run-length word of the position, which saves the match kernel a scattered load
@@ -247,7 +263,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 #pragma unroll
 		for (int e = 0; e < E; e++) {
 			const bool valid = idx0 + e * 64 < npos;
-			const uint32_t d = FIRST ? (h[e] & 255u) : ((h[e] & 0x7FFFu) >> 8);
+			const uint32_t d = FIRST ? (h[e] & 255u) : ((h[e] & HMASK) >> 8);
 			uint64_t same = __ballot(valid);  // lanes of this round with the same digit
 #pragma unroll
 			for (int b = 0; b < BITS; b++) {
@@ -279,7 +295,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 #pragma unroll
 		for (int e = 0; e < E; e++) {
 			if (idx0 + e * 64 < npos) {
-				const uint32_t d = FIRST ? (h[e] & 255u) : ((h[e] & 0x7FFFu) >> 8);
+				const uint32_t d = FIRST ? (h[e] & 255u) : ((h[e] & HMASK) >> 8);
 				const uint32_t dst = wcnt[wave][d] + rk[e];
 				rec_dst[dst] = (uint64_t)p[e] | ((uint64_t)h[e] << 32);
 			}
@@ -323,13 +339,15 @@ __device__ __forceinline__ uint32_t nil_candidate(uint32_t p, uint32_t lookahead
 // scanned tail (>= 264 bytes) decides every length below the cap.
 constexpr int RUNLEN_OUT = 2048 - 264;
 
-// SORT = false (the Z_RLE pass): run-length words only, without the sort histograms and run-list counts nobody reads there
-template <bool SORT>
+// SORT = false (the Z_RLE pass): run-length words only, without the sort histograms and run-list counts nobody reads there.
+// HB: hash bits (15 or 16, memLevel 8 or 9)
+template <bool SORT, int HB>
 __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 {
+	constexpr int NH = 256 + (1 << (HB - 8));  // hash & 255, then hash >> 8
 	__shared__ uint32_t wtot[4];  // per wave: has_change << 31 | distance from the wave's first position to its first change
-	__shared__ uint32_t hist[SORT ? 384 : 1];  // digits of the sort: hash & 255 of every string of this workgroup's positions, then hash >> 8
-	if (SORT) for (int t = threadIdx.x; t < 384; t += 256) hist[t] = 0;
+	__shared__ uint32_t hist[SORT ? NH : 1];  // digits of the sort: hash & 255 of every string of this workgroup's positions, then hash >> 8
+	if (SORT) for (int t = threadIdx.x; t < NH; t += 256) hist[t] = 0;
 	__syncthreads();
 	const int s = blockIdx.y;
 	const uint32_t L = a.in_sizes[s];
@@ -362,7 +380,7 @@ __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 #pragma unroll
 			for (int k = 0; k < 8; k++) {
 				const bool v = threadIdx.x * 8 + k < (uint32_t)RUNLEN_OUT && g + k + 2 < L;
-				hk[k] = v ? (((uint32_t)b[k + 1] << 10) ^ ((uint32_t)b[k + 2] << 5) ^ (uint32_t)b[k + 3]) & 0x7FFFu : 0xFFFFFFFFu;
+				hk[k] = v ? hash3<HB>(b[k + 1], b[k + 2], b[k + 3]) : 0xFFFFFFFFu;
 				if (v) { if (!cnt) h0 = hk[k]; else same &= hk[k] == h0; cnt++; }
 			}
 			const bool wave_same = __all(same && cnt == 8 && h0 == (uint32_t)__builtin_amdgcn_readfirstlane((int)h0));
@@ -441,8 +459,8 @@ __global__ void __launch_bounds__(256) dfl_run_len_kernel(DeflateArgs a)
 	}
 	if (!SORT) return;
 	__syncthreads();
-	for (int t = threadIdx.x; t < 384; t += 256)
-		if (hist[t]) atomicAdd(&a.sort_hist[(size_t)s * 384 + t], hist[t]);
+	for (int t = threadIdx.x; t < NH; t += 256)
+		if (hist[t]) atomicAdd(&a.sort_hist[(size_t)s * SORT_HIST + t], hist[t]);
 }
 
 // length of the common prefix of x and y, continuing from len, capped at cap; 8 bytes per step
@@ -466,8 +484,13 @@ __device__ __forceinline__ int common_prefix(const uint8_t *x, const uint8_t *y,
 // Two strings of one bucket start with the same three bytes exactly when b1 and the top three bits of b0 agree (the hash then
 // pins b2 and the rest of b0), so the match kernel decides every candidate whose match is shorter than five bytes -- nearly all
 // of them on token payloads -- from the records alone, which are read in sorted order (coalesced); before, every position paid
-// a scattered load for its own string and one per candidate.
-__device__ __forceinline__ uint32_t rec_hash(uint64_t r) { return (uint32_t)(r >> 32) & 0x7FFFu; }
+// a scattered load for its own string and one per candidate.  Compact records exist at memLevel 8 only: the 16-bit hash of
+// memLevel 9 would leave four top bits of b0 unpinned, and the record has no bit to spare.  A wide record's upper word is the
+// hash alone (15 or 16 bits).
+__device__ __forceinline__ uint32_t rec_hash(uint64_t r, uint32_t pos_mask)
+{
+	return (uint32_t)(r >> 32) & (pos_mask == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0x7FFFu);
+}
 __device__ __forceinline__ uint32_t rec_pos(uint64_t r, uint32_t pos_mask) { return (uint32_t)r & pos_mask; }
 constexpr uint32_t COMPACT_POS_BITS = 22, COMPACT_POS_MASK = (1u << COMPACT_POS_BITS) - 1u;
 
@@ -503,7 +526,7 @@ __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const
 	}
 	for (int64_t j = (int64_t)i - 1; j >= 0; j--) {
 		const uint64_t rj = recs[j];
-		if (rec_hash(rj) != h) break;
+		if (rec_hash(rj, pos_mask) != h) break;
 		if (count == LIGHT_STEPS) { kind = 1; break; }           // heavy: finish cooperatively
 		const uint32_t q = rec_pos(rj, pos_mask);
 		const uint32_t dist = p - q;
@@ -563,7 +586,7 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 		uint32_t best_q = 0, best_q1 = 0, run_r = 0;
 		const uint64_t ri = recs[min(i, npos - 1)];
 		const uint32_t p = rec_pos(ri, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu);
-		const uint32_t h = rec_hash(ri);
+		const uint32_t h = rec_hash(ri, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu);
 		bool from_memory = valid;
 		bool found = false;  // something to store (see MatchRec)
 		if (CMP) {
@@ -655,7 +678,7 @@ __device__ __forceinline__ void coop_longest_match(const uint8_t *in, const uint
                                                    uint32_t i, uint32_t p, uint32_t pos_mask, int lane, uint32_t nice, uint32_t max_chain,
                                                    uint32_t &lo, uint32_t &hi)
 {
-	const uint32_t h = rec_hash(recs[i]);
+	const uint32_t h = rec_hash(recs[i], pos_mask);
 	const uint32_t lookahead = L - p;
 	const int max_len = lookahead < (uint32_t)MAX_MATCH ? (int)lookahead : MAX_MATCH;
 	const int nice_eff = (int)min(lookahead, nice);  // nice_match clamped to the lookahead (<= max_len)
@@ -683,7 +706,7 @@ __device__ __forceinline__ void coop_longest_match(const uint8_t *in, const uint
 		const int64_t j = (int64_t)i - 1 - (int64_t)(r * 64 + lane);
 		const uint64_t rj = j >= 0 ? rj_next : ~0ull;
 		rj_next = rec_of_round(r + 1);  // (requested before this round's strings are compared)
-		const bool in_chain = j >= 0 && rec_hash(rj) == h && (uint32_t)(r * 64 + lane) < max_chain;
+		const bool in_chain = j >= 0 && rec_hash(rj, pos_mask) == h && (uint32_t)(r * 64 + lane) < max_chain;
 		const uint32_t q = in_chain ? rec_pos(rj, pos_mask) : 0u;
 		const uint32_t dist = p - q;
 		const bool term = !in_chain || q == 0 || q == nil_q ||
@@ -862,7 +885,7 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 		const uint64_t ri = recs[i];
 		const uint64_t r_head = recs[i >= 1 ? i - 1 : 0], r_quarter = recs[i >= quarter ? i - quarter : 0], r_full = recs[i >= a.max_chain ? i - a.max_chain : 0];
 		const uint32_t p = rec_pos(ri, a.pos_mask);
-		const uint32_t h = rec_hash(ri);
+		const uint32_t h = rec_hash(ri, a.pos_mask);
 		const uint32_t lookahead = L - p;
 		const uint32_t max_len = lookahead < (uint32_t)MAX_MATCH ? lookahead : (uint32_t)MAX_MATCH;
 		const uint32_t nice_eff = min(lookahead, a.nice);  // nice_match clamped to the lookahead (<= max_len)
@@ -874,7 +897,7 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 		bool scan = true;
 		if (!has_prev) {  // chain head rules of deflate_slow / longest_match
 			const uint64_t rh = i >= 1 ? r_head : ~0ull;
-			const bool have_head = i >= 1 && rec_hash(rh) == h;
+			const bool have_head = i >= 1 && rec_hash(rh, a.pos_mask) == h;
 			const uint32_t hq = have_head ? rec_pos(rh, a.pos_mask) : 0u;
 			if (!have_head || hq == 0 || hq == nil_candidate(p, lookahead) || p - hq > (uint32_t)MAX_DIST) scan = false;
 			else if (p - hq == (uint32_t)MAX_DIST) {  // only the head itself may sit at distance MAX_DIST
@@ -889,8 +912,8 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 			const uint8_t c = ext_ok ? in[p + r] : 0;
 			const uint32_t qw = p >= (uint32_t)MAX_DIST ? p - (uint32_t)MAX_DIST + 1 : 1u;  // dist < MAX_DIST, q != NIL
 			uint32_t qmin4 = qw, qmin1 = qw;
-			if (i >= a.max_chain && rec_hash(r_full) == h) qmin4 = max(qmin4, rec_pos(r_full, a.pos_mask));
-			if (i >= quarter && rec_hash(r_quarter) == h) qmin1 = max(qmin1, rec_pos(r_quarter, a.pos_mask));
+			if (i >= a.max_chain && rec_hash(r_full, a.pos_mask) == h) qmin4 = max(qmin4, rec_pos(r_full, a.pos_mask));
+			if (i >= quarter && rec_hash(r_quarter, a.pos_mask) == h) qmin1 = max(qmin1, rec_pos(r_quarter, a.pos_mask));
 			// number of run ends <= p (none lies strictly inside p's own run): an end x comes from position x - 3, so these are the
 			// entries of the positions below p - 2 -- the rank table gives those below the 8-aligned part, the rest is a step or two
 			uint32_t lo = 0;
@@ -1061,8 +1084,10 @@ __global__ void __launch_bounds__(256) dfl_rle_rec_kernel(DeflateArgs a)
 	}
 }
 
-// deflate_huff: every byte is a literal, so symbol p is in[p] and block m ends at input position 16383 (m + 1): no parse, no
-// walk.  Four positions per lane (in_stride is a multiple of 256: the dword and the four symbols stay inside the slice)
+// deflate_huff: every byte is a literal, so symbol p is in[p] and block m ends at input position BS (m + 1) (BS = 16383 or
+// 32767, memLevel 8 or 9), flushed in the loop iteration of its last literal: no parse, no walk.  Four positions per lane
+// (in_stride is a multiple of 256: the dword and the four symbols stay inside the slice)
+template <uint32_t BS>
 __global__ void __launch_bounds__(256) dfl_huff_symbols_kernel(DeflateArgs a)
 {
 	const int s = blockIdx.y;
@@ -1070,7 +1095,7 @@ __global__ void __launch_bounds__(256) dfl_huff_symbols_kernel(DeflateArgs a)
 	const size_t base = (size_t)s * a.in_stride;
 	const uint32_t *in4 = reinterpret_cast<const uint32_t *>(a.in + base);
 	uint4 *sym4 = reinterpret_cast<uint4 *>(a.sym + base);
-	uint32_t *bend = a.blk_end + (size_t)s * a.max_blocks;
+	uint32_t *bend = a.blk_end + (size_t)s * a.max_blocks, *btop = a.blk_top + (size_t)s * a.max_blocks;
 	if (blockIdx.x == 0 && threadIdx.x == 0) a.total_syms[s] = L;
 	const uint32_t nq = (L + 3) / 4;
 	for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += gridDim.x * blockDim.x) {
@@ -1080,7 +1105,7 @@ __global__ void __launch_bounds__(256) dfl_huff_symbols_kernel(DeflateArgs a)
 		for (int k = 0; k < 4; k++) {
 			const uint32_t p = p0 + (uint32_t)k;
 			v[k] = p < L ? (w >> (8 * k)) & 255u : 0u;
-			if (p < L && p % BLOCK_SYMS == BLOCK_SYMS - 1) bend[p / BLOCK_SYMS] = p + 1;
+			if (p < L && p % BS == BS - 1) { bend[p / BS] = p + 1; btop[p / BS] = p; }
 		}
 		sym4[q] = make_uint4(v[0], v[1], v[2], v[3]);
 	}
@@ -1147,7 +1172,11 @@ __global__ void __launch_bounds__(WALK_T) dfl_walk_kernel(DeflateArgs a, int n)
 }
 
 // ------------------------------------------------------------------ 3c. symbols in stream order
-// sym32: bits 0..7 lc (literal or length-3), bits 16..31 distance (0 = literal)
+// sym32: bits 0..7 lc (literal or length-3), bits 16..31 distance (0 = literal); BS = symbols per block (memLevel 8 or 9).
+// A block ends where its last symbol's input ends (blk_end) and is flushed in the loop iteration that tallied that symbol: its
+// top is the symbol's position under deflate_rle, one more under deflate_slow, which tallies a string once it has looked at the
+// next one (blk_top, dfl_tree_kernel)
+template <uint32_t BS>
 __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 {
 	const int s = blockIdx.y;
@@ -1158,7 +1187,8 @@ __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 	const uint32_t nblk64 = (L + 63) / 64;
 	const int lane = threadIdx.x & 63;
 	uint32_t *sym = a.sym + base;
-	uint32_t *bend = a.blk_end + (size_t)s * a.max_blocks;
+	uint32_t *bend = a.blk_end + (size_t)s * a.max_blocks, *btop = a.blk_top + (size_t)s * a.max_blocks;
+	const uint32_t lazy = short_pass(a.strategy) ? 0u : 1u;
 	// everything a block needs is requested without a branch (a load inside a conditional is waited for on the spot: entry,
 	// record, symbol base and the literal byte used to be four round trips in a row) -- and one turn ahead
 	const uint32_t wb_step = gridDim.x * (blockDim.x >> 6), wb_last = nblk64 ? nblk64 - 1 : 0;
@@ -1209,11 +1239,11 @@ __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 			if (p == L - 1) a.postloop_lit[s] = 1;  // the literal tallied after deflate_slow's main loop
 			for (uint32_t t = 0; t < (len ? k : 1u); t++, off++) {  // literals
 				sym[off] = t ? in[p + t] : lit0;
-				if (off % BLOCK_SYMS == BLOCK_SYMS - 1) bend[off / BLOCK_SYMS] = p + t + 1;
+				if (off % BS == BS - 1) { bend[off / BS] = p + t + 1; btop[off / BS] = p + t + lazy; }
 			}
 			if (len) {
 				sym[off] = (len - MIN_MATCH) | (dist << 16);
-				if (off % BLOCK_SYMS == BLOCK_SYMS - 1) bend[off / BLOCK_SYMS] = p + k + len;
+				if (off % BS == BS - 1) { bend[off / BS] = p + k + len; btop[off / BS] = p + k + lazy; }
 			}
 		}
 	}
@@ -1234,8 +1264,8 @@ struct TreeScratch {  // one block's working set, in LDS
 	uint16_t dfreq[2 * D_CODES + 1], ddad[2 * D_CODES + 1], dlen[2 * D_CODES + 1], dcode[D_CODES + 2];
 	uint16_t bfreq[2 * BL_CODES + 1], bdad[2 * BL_CODES + 1], blen[2 * BL_CODES + 1], bcode[BL_CODES + 1];
 	// heap entries carry their own sort key: freq << 15 | depth << 10 | node, so that trees.c's smaller(n, m)
-	// is (e_n >> 10) <= (e_m >> 10) and one 64-bit LDS read fetches both children (freq <= 16384: 15 bits;
-	// depth <= 21 for that total weight: 5 bits; node < 573: 10 bits)
+	// is (e_n >> 10) <= (e_m >> 10) and one 64-bit LDS read fetches both children (freq <= 32768: 16 bits at memLevel 9;
+	// depth <= 22 for that total weight: 5 bits; node < 573: 10 bits)
 	alignas(16) uint32_t heap[HEAP_SIZE + 11];  // + a sink slot for each lane of the heap replay (tree_heap)
 	uint32_t bl_count[MAX_BITS + 1];
 	uint16_t next_code[MAX_BITS + 1];
@@ -1649,17 +1679,33 @@ __device__ void send_header(TreeScratch &S)
 // parts of a block (overflow repair, block type) run on lane q for block m0 + q; the heap replay and the parallel parts
 // take the blocks in turn.
 constexpr int TREE_BLOCKS = 1;
+
+// Absolute position of window[0] at the top of the loop iteration at position `top` (deflate.c fill_window).  The window
+// holds 64 KiB; fill_window runs once the lookahead is <= lam (deflate_slow: < MIN_LOOKAHEAD, deflate_rle: <= MAX_MATCH,
+// deflate_huff: 0) and slides it by 32 KiB when strstart >= 32768 + MAX_DIST.  While input is left the window is full after
+// every fill, so slide k happens at top 32768 (k - 1) + 65536 - lam; once the input is all in, at most one more follows, at
+// the first top >= max(base + 65274, L - lam).
+__device__ __forceinline__ uint32_t window_base(uint32_t top, uint32_t L, uint32_t strategy)
+{
+	const uint32_t lam = strategy == Z_HUFFMAN_ONLY ? 0u : strategy == Z_RLE ? (uint32_t)MAX_MATCH : (uint32_t)MIN_LOOKAHEAD - 1u;
+	const uint32_t kf = L >= 65536u ? (L - 65536u) / 32768u + 1u : 0u;  // slides with a full window
+	uint32_t k = 0;
+	if (top >= 65536u - lam) k = min((top - (65536u - lam)) / 32768u + 1u, kf);
+	if (k == kf && 32768u * k + (uint32_t)(WSIZE + MAX_DIST) <= top && L <= top + lam) k++;
+	return 32768u * k;
+}
 __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 {
 	__shared__ TreeScratch S4[TREE_BLOCKS];
 	const int s = blockIdx.y, m0 = blockIdx.x * TREE_BLOCKS, lane = threadIdx.x;
 	const uint32_t T = a.total_syms[s];
 	const uint32_t L = a.in_sizes[s];
-	// number of blocks: one flush per 16383 tallied symbols inside the loop, plus the final flush
-	uint32_t nfull = T / BLOCK_SYMS;
+	// number of blocks: one flush per 16383 (32767) tallied symbols inside the loop, plus the final flush
+	const uint32_t BS = a.block_syms;
+	uint32_t nfull = T / BS;
 	// the post-loop literal never flushes (deflate_slow only: deflate_huff and deflate_rle have none, and there a symbol count that
-	// is a multiple of 16383 ends the stream with an empty final block)
-	if (T % BLOCK_SYMS == 0 && nfull > 0 && !short_pass(a.strategy) && a.postloop_lit[s]) nfull--;
+	// is a multiple of the block size ends the stream with an empty final block)
+	if (T % BS == 0 && nfull > 0 && !short_pass(a.strategy) && a.postloop_lit[s]) nfull--;
 	const uint32_t nblocks = nfull + 1;
 	BlockMeta *meta = a.block_meta + (size_t)s * a.max_blocks;
 	if ((uint32_t)m0 >= nblocks) return;
@@ -1678,8 +1724,8 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		TreeScratch &S = S4[q];
 		const int m = m0 + q;
 		const bool last = (uint32_t)m == nblocks - 1;
-		const uint32_t first = (uint32_t)m * BLOCK_SYMS;
-		const uint32_t nsym = last ? T - first : (uint32_t)BLOCK_SYMS;
+		const uint32_t first = (uint32_t)m * BS;
+		const uint32_t nsym = last ? T - first : BS;
 		const uint32_t *sym = a.sym + (size_t)s * a.in_stride + first;
 		for (int i = lane; i < HEAP_SIZE; i += 64) { S.freq[i] = 0; S.len[i] = 0; }
 		for (int i = lane; i < L_CODES + 2; i += 64) S.code[i] = 0;
@@ -1782,8 +1828,8 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		TreeScratch &S = S4[lane];
 		const int m = m0 + lane;
 		const bool last = (uint32_t)m == nblocks - 1;
-		const uint32_t first = (uint32_t)m * BLOCK_SYMS;
-		const uint32_t nsym = last ? T - first : (uint32_t)BLOCK_SYMS;
+		const uint32_t first = (uint32_t)m * BS;
+		const uint32_t nsym = last ? T - first : BS;
 		const uint32_t in_begin = m == 0 ? 0u : bend[m - 1];
 		const uint32_t in_end = last ? L : bend[m];
 		int max_blindex;
@@ -1794,11 +1840,13 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		const uint32_t static_lenb = (S.static_len + 3 + 7) >> 3;
 		if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
 		const uint32_t stored_len = in_end - in_begin;
-		// stored blocks need block_start >= 0 in window coordinates; a block that an incompressible
-		// verdict could apply to spans < 32 KiB of input, so its start is always inside the window
+		// stored blocks need block_start >= 0 in window coordinates (trees.c: buf != NULL).  At memLevel 8 a block that an
+		// incompressible verdict could apply to spans < 32 KiB of input, so its start is always inside the window; 32767
+		// literals can span a slide of the window
+		const bool in_window = in_begin >= window_base(last ? L : a.blk_top[(size_t)s * a.max_blocks + m], L, a.strategy);
 		BlockMeta bm;
 		bm.in_begin = in_begin; bm.stored_len = stored_len; bm.first_sym = first; bm.nsym = nsym; bm.last = last ? 1u : 0u;
-		if (stored_len + 4 <= opt_lenb) {
+		if (in_window && stored_len + 4 <= opt_lenb) {
 			bm.type = 0; bm.hdr_nbits = 0; bm.body_bits = 0;
 		} else if (a.strategy == Z_FIXED || static_lenb == opt_lenb) {  // trees.c _tr_flush_block
 			bm.type = 1; bm.hdr_nbits = 0; bm.body_bits = S.static_len;
@@ -2130,6 +2178,15 @@ bool deflate_strategy_args(int level, int strategy, DeflateArgs &a)
 	return true;
 }
 
+// deflate.c deflateInit2: hash_bits = memLevel + 7, lit_bufsize = 1 << (memLevel + 6) (a block ends after lit_bufsize - 1 symbols)
+bool deflate_mem_level_args(int mem_level, DeflateArgs &a)
+{
+	if (mem_level != 8 && mem_level != 9) return false;
+	a.hash_bits = (uint32_t)mem_level + 7u;
+	a.block_syms = (1u << (mem_level + 6)) - 1u;
+	return true;
+}
+
 // host: trees.c tr_static_init tables -> constant memory
 hipError_t deflate_init_tables()
 {
@@ -2197,15 +2254,18 @@ size_t deflate_sort_temp_bytes(size_t total, int n)
 // stream is given.
 static hipError_t launch_deflate_short(const DeflateArgs &a, int n, hipStream_t st)
 {
+	const bool ml9 = a.block_syms == (uint32_t)BLOCK_SYMS_ML9;
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
 	if (a.strategy == Z_RLE) {
-		hipLaunchKernelGGL(dfl_run_len_kernel<false>, dim3(gx, n), dim3(256), 0, st, a);  // run-length words
+		hipLaunchKernelGGL((dfl_run_len_kernel<false, 15>), dim3(gx, n), dim3(256), 0, st, a);  // run-length words
 		hipLaunchKernelGGL(dfl_rle_rec_kernel, dim3(gx, n), dim3(256), 0, st, a);
 		hipLaunchKernelGGL(dfl_offsets2_kernel, dim3(256), dim3(256), 0, st, a, n);
 		hipLaunchKernelGGL(dfl_walk_kernel, dim3(n), dim3(WALK_T), 0, st, a, n);
-		hipLaunchKernelGGL(dfl_symbols_kernel, dim3(gx, n), dim3(256), 0, st, a);
+		if (ml9) hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS_ML9>, dim3(gx, n), dim3(256), 0, st, a);
+		else hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS>, dim3(gx, n), dim3(256), 0, st, a);
 	} else {
-		hipLaunchKernelGGL(dfl_huff_symbols_kernel, dim3(gx, n), dim3(256), 0, st, a);
+		if (ml9) hipLaunchKernelGGL(dfl_huff_symbols_kernel<BLOCK_SYMS_ML9>, dim3(gx, n), dim3(256), 0, st, a);
+		else hipLaunchKernelGGL(dfl_huff_symbols_kernel<BLOCK_SYMS>, dim3(gx, n), dim3(256), 0, st, a);
 	}
 	hipLaunchKernelGGL(dfl_adler_kernel, dim3(n), dim3(256), 0, st, a);
 	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
@@ -2218,15 +2278,24 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
                           const hipEvent_t *ev)
 {
 	hipError_t e;
+	const bool ml9 = a.hash_bits == 16;
+	if ((a.hash_bits != 15 && !ml9) || a.block_syms != (uint32_t)(ml9 ? BLOCK_SYMS_ML9 : BLOCK_SYMS)) return hipErrorInvalidValue;
+	if (ml9 && a.pos_mask != 0xFFFFFFFFu) return hipErrorInvalidValue;  // memLevel 9: wide records only ("Sort records")
 	if ((e = hipMemsetAsync(a.out, 0, (size_t)n * a.out_stride, st)) != hipSuccess) return e;
 	if (short_pass(a.strategy)) return launch_deflate_short(a, n, st);
-	if ((e = hipMemsetAsync(a.sort_hist, 0, (size_t)n * 384 * 4, st)) != hipSuccess) return e;
+	if ((e = hipMemsetAsync(a.sort_hist, 0, (size_t)n * SORT_HIST * 4, st)) != hipSuccess) return e;
 	hipLaunchKernelGGL(dfl_offsets_kernel, dim3(64), dim3(256), 0, st, a, n);  // (also zeroes run_counts)
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
 	(void)sort_temp; (void)sort_temp_bytes;
-	hipLaunchKernelGGL(dfl_run_len_kernel<true>, dim3(gx, n), dim3(256), 0, st, a);       // run-length words, sort histograms, run-list counts
-	hipLaunchKernelGGL(dfl_sort_pass_kernel<true>, dim3(n), dim3(1024), 0, st, a);   // in -> rec_in by hash & 255
-	hipLaunchKernelGGL(dfl_sort_pass_kernel<false>, dim3(n), dim3(1024), 0, st, a);  // -> rec_out by hash >> 8
+	if (ml9) {
+		hipLaunchKernelGGL((dfl_run_len_kernel<true, 16>), dim3(gx, n), dim3(256), 0, st, a);
+		hipLaunchKernelGGL((dfl_sort_pass_kernel<true, 16>), dim3(n), dim3(1024), 0, st, a);
+		hipLaunchKernelGGL((dfl_sort_pass_kernel<false, 16>), dim3(n), dim3(1024), 0, st, a);
+	} else {
+		hipLaunchKernelGGL((dfl_run_len_kernel<true, 15>), dim3(gx, n), dim3(256), 0, st, a);       // run-length words, sort histograms, run-list counts
+		hipLaunchKernelGGL((dfl_sort_pass_kernel<true, 15>), dim3(n), dim3(1024), 0, st, a);   // in -> rec_in by hash & 255
+		hipLaunchKernelGGL((dfl_sort_pass_kernel<false, 15>), dim3(n), dim3(1024), 0, st, a);  // -> rec_out by hash >> 8
+	}
 	const bool fork = side != nullptr && ev != nullptr;
 	hipStream_t s2 = fork ? side : st;
 	if (fork) {
@@ -2265,7 +2334,8 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 	hipLaunchKernelGGL(dfl_rec_kernel, dim3(gx, n), dim3(256), 0, st, a);
 	hipLaunchKernelGGL(dfl_offsets2_kernel, dim3(256), dim3(256), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_walk_kernel, dim3(n), dim3(WALK_T), 0, st, a, n);
-	hipLaunchKernelGGL(dfl_symbols_kernel, dim3(gx, n), dim3(256), 0, st, a);
+	if (ml9) hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS_ML9>, dim3(gx, n), dim3(256), 0, st, a);
+	else hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS>, dim3(gx, n), dim3(256), 0, st, a);
 	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
 	hipLaunchKernelGGL(dfl_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_emit_kernel, dim3(a.max_blocks, n), dim3(256), 0, st, a);

@@ -202,6 +202,26 @@ int cct_zlib_compress_batch_level(const uint8_t *h_in, const uint64_t *h_offsets
  * before the device is touched.  Strategy 0 returns what cct_zlib_compress_batch_level returns. */
 int cct_zlib_compress_batch_strategy(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy,
                                      uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+/* The same with zlib's memLevel: stream i is byte-identical to zlib.compressobj(level, DEFLATED, 15, mem_level,
+ * strategy).  mem_level 8 returns what cct_zlib_compress_batch_strategy returns; 9 hashes into 16 bits and ends a block
+ * after 32767 symbols (what Pillow's PNG writer uses).  Any other mem_level returns CCT_E_ARG before the device is
+ * touched; (level, strategy) are checked as above. */
+int cct_zlib_compress_batch_params(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy,
+                                   int mem_level, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+
+/* ---- PNG writer ------------------------------------------------------------------------ */
+/* Replaces the reference's 16-bit PNG previews (src/codec/core.py:522-538 through imageio, lib/png.py:25-31 through
+ * Pillow): n uint16 rasters of shape (rows, cols), C order, on the host (images_on_device 0) or the device (1).  File i,
+ * byte-identical to Pillow's Image.fromarray(((img << shift) & 0xFFFF).astype(uint16)).save(f, "PNG",
+ * compress_level=level), lands at h_out + i*out_stride, its size in h_out_sizes[i].  Rows are filtered on the device
+ * with Pillow's choice among None, Sub, Up and Paeth; the zlib stream is memLevel 9 / Z_FILTERED at `level` (-1 = 6, or
+ * 4 .. 9) on the device, or in host libz with device_deflate 0; IDAT chunks of max(65536, 4*cols) bytes with their
+ * CRC-32s are packed on the device.  CCT_E_ARG before the device is touched: levels 0 .. 3 and outside -1 .. 9, shift
+ * outside 0 .. 15, rows or cols < 1, more than 2^30 - 512 filtered bytes (rows * (1 + 2*cols)).  out_stride >=
+ * cct_png_bound(rows, cols) (CCT_E_CAP otherwise; 0 for a refused shape). */
+size_t cct_png_bound(int rows, int cols);
+int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, int rows, int cols, int shift, int level,
+                         uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 
 /* INFLATE stage alone, on the device: n zlib streams (h_in[h_offsets[i] .. h_offsets[i+1])) -> the bytes
  * zlib.decompress returns for each (what the reference calls at core.py:421).  Output i lands at

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Corpus size comparison: the counterpart of the reference's scripts/evaluate.py:52-136 without pydicom.
 
-    python tools/evaluate.py DIRECTORY [--results FILE.csv] [--batch 256] [--zip host|device]
+    python tools/evaluate.py DIRECTORY [--results FILE.csv] [--batch 256] [--zip host|device] [--png host|device]
 
 Every slice under DIRECTORY (.npy, .u16/.raw, .u16.zz, 16-bit .png) gets one CSV row `File,Raw,ZIP,PNG,RLE,JP2,CCT` as
 in results/encoder-comparisons.csv: Raw = bytes of the pixel array, ZIP = zlib.compress at the default level
@@ -11,6 +11,8 @@ of this environment: those columns hold NA.  The reference fans the slices over 
 (evaluate.py:107-119); here slices of one shape go to the GPU in batches through cct_hip.encode_batch, and the CPU
 columns are computed by a thread pool meanwhile.  --zip device computes the ZIP column on the GPU as well, a chunk at a
 time through cct_hip.zlib_compress_batch(raws, level=-1) (byte-identical to zlib.compress(raw)); host zlib is the default.
+--png device computes the PNG column the same way through cct_hip.png_encode_batch(images, level=6, shift=4), whose files
+are byte-identical to Pillow's; Pillow on the thread pool is the default.
 """
 import argparse
 import io
@@ -36,8 +38,10 @@ def png_size(image):
     return buf.tell()
 
 
-def cpu_columns(image, zip_on_host=True):
-    cols = {RAW: image.nbytes, PNG: png_size(image), RLE: "NA", JP2: "NA"}
+def cpu_columns(image, zip_on_host=True, png_on_host=True):
+    cols = {RAW: image.nbytes, RLE: "NA", JP2: "NA"}
+    if png_on_host:
+        cols[PNG] = png_size(image)
     if zip_on_host:
         cols[ZIP] = len(zlib.compress(image.tobytes()))
     return cols
@@ -50,6 +54,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--zip", choices=("host", "device"), default="host",
                     help="where the ZIP column (zlib.compress at the default level) is computed")
+    ap.add_argument("--png", choices=("host", "device"), default="host",
+                    help="where the PNG column (16-bit PNG of value << 4, Pillow's default compress_level 6) is computed")
     args = ap.parse_args(argv)
     import cct_hip
     with open(os.path.join(ROOT, "2023-compact-image-compression_amd", "config.json")) as f:
@@ -67,8 +73,8 @@ def main(argv=None):
         rows[name] = {FILE: name}
         groups.setdefault((img.shape, img.dtype.str), []).append((name, img))
     with ThreadPoolExecutor(max(1, min(8, os.cpu_count() or 1))) as pool:
-        zip_host = args.zip == "host"
-        futures = {name: pool.submit(cpu_columns, img, zip_host) for items in groups.values() for name, img in items}
+        zip_host, png_host = args.zip == "host", args.png == "host"
+        futures = {name: pool.submit(cpu_columns, img, zip_host, png_host) for items in groups.values() for name, img in items}
         for items in groups.values():
             for i in range(0, len(items), args.batch):
                 chunk = items[i:i + args.batch]
@@ -79,6 +85,10 @@ def main(argv=None):
                     zips = cct_hip.zlib_compress_batch([img.tobytes() for _, img in chunk], level=-1)
                     for (name, _), z in zip(chunk, zips):
                         rows[name][ZIP] = len(z)
+                if not png_host:  # lib/png.py:25-31: Image.fromarray(value << 4).save(..., "PNG") at compress_level 6
+                    pngs = cct_hip.png_encode_batch(np.stack([img.astype(np.uint16) for _, img in chunk]), level=6, shift=4)
+                    for (name, _), p in zip(chunk, pngs):
+                        rows[name][PNG] = len(p)
         for name, fut in futures.items():
             rows[name].update(fut.result())
     outputs = sorted(rows.values(), key=lambda r: r[FILE])  # evaluate.py:130
