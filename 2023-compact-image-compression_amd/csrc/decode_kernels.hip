@@ -330,7 +330,9 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 			for (uint32_t jm = starts & sm.J; jm; jm &= jm - 1, k++) {
 				const int i = __ffs((int)jm) - 1;
 				const uint32_t ord = p.pix_base + (uint32_t)__popc(pix & ((1u << i) - 1u));  // pixel tokens before the jump
-				if (ord < (uint32_t)N) jset(k, ord, seg_byte(w, nxt, i) & 0x3Fu);
+				// jump bytes behind pixel N - 1 are recorded too: they are counted in nj_c, and the replay stops at the first record
+				// with ord >= N -- a record left unwritten would be read as whatever the list held before
+				jset(k, ord, seg_byte(w, nxt, i) & 0x3Fu);
 			}
 		}
 	}
@@ -451,8 +453,8 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 				starts &= keep; pix &= keep; fulls &= keep;
 			}
 			DECB(0);
-			const uint32_t jm = starts & sm.J;
-			if (jm & (jm << 1)) flags |= CCT_ST_STREAM;  // two jump bytes in a row
+			// (two jump bytes in a row carry the same pixel ordinal and are refused by the replay, sslot < slots_done, across segments and
+			// steps too; a test on the masks here would also see the jump bytes behind pixel N - 1 of a lane that has no pixel left to clip)
 			if (nvalid > 0 && ((fulls >> (nvalid - 1)) & 1u) && seg_start + (uint32_t)nvalid >= Lr) flags |= CCT_ST_STREAM;  // second byte missing
 			// a wave-uniform choice for BS == 0: a lane's 16 pixels span at most two slots for every bs >= 16, for no bs < 16
 			if (BS ? BS >= 16 : bs >= 16) {

@@ -173,7 +173,8 @@ def test_odd_shapes_vs_oracle(hip, shape):
 
 def test_every_block_difficult_spills_lists(hip):
     """Noise slices: every block is difficult, so the difficult-block list overflows its LDS part
-    (ENC_LIST_CAP) into the HBM workspace, and decode's jump list does likewise."""
+    (ENC_LIST_CAP) into the HBM workspace.  Decode's jump list holds DEC_JLIST_CAP = 2048 records in LDS: the 256x256
+    slices (4096 blocks, at most 2048 pairs) cannot spill it, the 512x512 slice does."""
     from oracle import oracle
     cfg = hip.default_config()
     rng = np.random.default_rng(99)
@@ -183,6 +184,11 @@ def test_every_block_difficult_spills_lists(hip):
         assert f == oracle.encode(img)
         assert st["n_difficult"] > 3000 and st["n_jump"] > 1000
     assert np.array_equal(hip.decode_batch(files, cfg), imgs)
+    big = rng.integers(0, 2048, size=(1, 512, 512)).astype(np.uint16)
+    files, info = hip.encode_batch(big, cfg, return_info=True)
+    assert files[0] == oracle.encode(big[0])
+    assert info[0]["n_difficult"] > 3000 and info[0]["n_jump"] > 2048
+    assert np.array_equal(hip.decode_batch(files, cfg), big)
 
 
 def test_large_slice_role_table_in_hbm(hip):
