@@ -736,9 +736,12 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 		for (int k = 0; k < 8; k++) { wv[2 * k] = perm(bv[k], av[k], 0x05040100u); wv[2 * k + 1] = perm(bv[k], av[k], 0x07060302u); }
 		const uint32_t pv = prev_px_final((int)p_i);
 		deltas<16>(wv, pv, px_);
-		if (!wide) {
+		// pv is the one pixel of a pair that the regime flags may not have seen: when the previous group ends in the partner of
+		// an earlier leader, the pixel before this group in the final order (lastpx_in) is neither one of the group's own nor
+		// `before`, so the pair that follows it decides for itself
+		if (!wide && pv < 0x4000u) {
 			p_mb = two_byte_bits(px_) | (two_byte_bits(px_ + 8) << 16);
-			if (big) q7 |= any_out_of_q7<16>(px_);
+			if (big || pv >= 0x0800u) q7 |= any_out_of_q7<16>(px_);
 		} else {
 			int pu = (int)pv;
 #pragma unroll
