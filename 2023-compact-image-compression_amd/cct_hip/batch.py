@@ -447,6 +447,63 @@ def decode_png_batch(files, config=None, level=9):
     return png_encode_batch(d_img, level=level, shift=4, shape=(n, w, h))
 
 
+def png_info(file):
+    """(rows, cols, bit_depth) of one PNG file (`bytes`), from its signature and IHDR; host only.  ValueError for anything
+    png_read_batch does not take: only 8- and 16-bit grayscale without interlace is read."""
+    if not isinstance(file, (bytes, bytearray, memoryview)):
+        raise TypeError(f"a PNG file is a bytes object, got {type(file).__name__}")
+    file = bytes(file)
+    rows, cols, depth = C.c_int(0), C.c_int(0), C.c_int(0)
+    _ffi.check(_ffi.lib().cct_png_info(file, len(file), C.byref(rows), C.byref(cols), C.byref(depth)))
+    return rows.value, cols.value, depth.value
+
+
+def png_read_batch(files, shift=0, out_dev=None, raise_errors=True):
+    """8- and 16-bit grayscale PNG files (a list of `bytes`, all of the shape of the first one; the depths may mix) -> an
+    (n, rows, cols) uint16 array of sample >> shift, read on the device: chunk CRC-32s, INFLATE and the row filters.  The
+    inverse of png_encode_batch(x, shift=s) for x < 2^(16-s), and with shift=4 of the reference's previews (png_to_array).
+    With out_dev it fills that DeviceBuffer and returns the shape, like decode_batch.  With raise_errors=False it returns
+    (array or shape, status) with status[i] a CCT_E_* code (include/compact_hip.h lists the refusals); the raster of a
+    refused file is unspecified.  Arguments are checked (TypeError / ValueError) before any device call."""
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)):
+        raise TypeError(f"PNG sample shift must be an integer, got {shift!r}")
+    shift = int(shift)
+    if not 0 <= shift <= 15:
+        raise ValueError(f"PNG sample shift {shift}: 0 to 15")
+    if isinstance(files, (bytes, bytearray, memoryview, str)):
+        raise TypeError("png_read_batch takes a list of bytes objects, one per file")
+    files = list(files)
+    for f in files:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise TypeError(f"a PNG file is a bytes object, got {type(f).__name__}")
+    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
+        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+    n = len(files)
+    if n == 0:
+        res = (0, 0, 0) if out_dev is not None else np.zeros((0, 0, 0), dtype=np.uint16)
+        return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
+    rows, cols, _ = png_info(files[0])
+    _check_png_shape(rows, cols)
+    if out_dev is not None and n * rows * cols * 2 > out_dev.nbytes:
+        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
+    L = _ffi.lib()
+    blob = b"".join(files)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(f) for f in files], out=offs[1:])
+    status = np.zeros(n, dtype=np.uint32)
+    if out_dev is not None:
+        rc = L.cct_png_read_batch(blob, offs.ctypes.data, n, rows, cols, shift, out_dev.ptr, 1, out_dev.nbytes // 2,
+                                  status.ctypes.data)
+        res = (n, rows, cols)
+    else:
+        res = np.empty((n, rows, cols), dtype=np.uint16)
+        rc = L.cct_png_read_batch(blob, offs.ctypes.data, n, rows, cols, shift, res.ctypes.data, 0, res.size,
+                                  status.ctypes.data)
+    if raise_errors or rc not in (_ffi.E_PNG, _ffi.E_MIXED, _ffi.E_CRC, _ffi.E_ZLIB, _ffi.E_STREAM):
+        _ffi.check(rc)
+    return res if raise_errors else (res, status)
+
+
 def zlib_decompress_batch(streams, max_out, raise_errors=True):
     """INFLATE stage alone on the device: [zlib streams] -> [bytes], what zlib.decompress returns for each
     (the reference calls it at core.py:421).  max_out bounds the inflated size of one stream.  With

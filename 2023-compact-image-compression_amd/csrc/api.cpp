@@ -123,6 +123,7 @@ struct DecSlot {
 	hipStream_t stream = nullptr;  // slot 0: Context::stream_dec
 	DevBuf d_role, d_slot, d_jord, d_jval, d_payload, d_sizes, d_status, d_images, d_pcache;
 	DevBuf d_arch, d_archoffs, d_zstatus;
+	DevBuf d_png_z, d_png_tab, d_png_bpp;  // PNG reader: gathered zlib streams, chunk table, bytes per sample (cct_png_read_batch)
 	DevBuf dh_stage;  // pinned host staging of inflated payloads (host INFLATE path)
 	hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr, ev_k_dec0 = nullptr, ev_k_dec1 = nullptr;
 	hipEvent_t ev_ws = nullptr;  // recorded after a launch on ANOTHER stream that uses this slot's workspaces (cct_decode_payload_dev)
@@ -131,7 +132,7 @@ struct DecSlot {
 	DecSlot()
 	{
 		DevBuf *b[] = {&d_role, &d_slot, &d_jord, &d_jval, &d_payload, &d_sizes, &d_status, &d_images, &d_pcache, &d_arch, &d_archoffs,
-		               &d_zstatus, &dh_stage};
+		               &d_zstatus, &dh_stage, &d_png_z, &d_png_tab, &d_png_bpp};
 		for (DevBuf *p : b) all_bufs[n_bufs++] = p;
 		dh_stage.pinned_host = true;
 	}
@@ -174,6 +175,7 @@ struct Context {
 	int inflate_lanes = 0;  // option "inflate_lanes": 256 / 512 lanes per stream in the INFLATE kernel, 0 = 512 unless an encode call is
 	                        // in flight (next to an encode batch the narrower workgroup is the faster one, see inflate_kernels.hip)
 	int last_inflate_lanes = 0;  // read-only option "last_inflate_lanes"
+	int png_unfilter_waves = PNG_UNFILTER_WAVES;  // option "png_unfilter_waves": waves per image of png_unfilter_kernel (1, 2, 4, 8)
 };
 std::atomic<int> g_encodes_in_flight{0};
 // gate between the decode and the encode stream (sched_kernels.hip): device counters and what has been issued so far
@@ -1844,6 +1846,234 @@ int cct_zlib_decompress_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 	return first;
 }
 
+// ---- PNG reader (png_read_kernels.hip) ---------------------------------------------------------------
+static uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// signature + IHDR of one file: CCT_OK or CCT_E_PNG (no message: the callers add the file's index)
+static int png_parse_ihdr(const uint8_t *f, size_t len, int *rows, int *cols, int *depth)
+{
+	static const uint8_t head[16] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n', 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
+	if (len < 33 || memcmp(f, head, 16) != 0) return CCT_E_PNG;
+	const uint32_t w = be32(f + 16), h = be32(f + 20);
+	const int d = f[24];
+	if (w == 0 || h == 0 || w > 0x7FFFFFFFu || h > 0x7FFFFFFFu) return CCT_E_PNG;
+	if ((d != 8 && d != 16) || f[25] != 0 || f[26] != 0 || f[27] != 0 || f[28] != 0) return CCT_E_PNG;
+	*rows = (int)h; *cols = (int)w; *depth = d;
+	return CCT_OK;
+}
+
+int cct_png_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *bit_depth)
+{
+	if (!h_file || !rows || !cols || !bit_depth) return fail(CCT_E_ARG, "null argument");
+	if (png_parse_ihdr(h_file, len, rows, cols, bit_depth))
+		return fail(CCT_E_PNG, "not a PNG this reader takes (8- or 16-bit grayscale, not interlaced)");
+	return CCT_OK;
+}
+
+// The chunk heads of one file -> entries of the chunk table (cct_internal.h PngChunk has the bounds argument).  `base`: the
+// file's offset in the pass's upload; *zoff: the running size of the gathered streams.  Returns the file's status; a refused
+// file leaves no entries behind.
+static int png_walk_file(const uint8_t *f, size_t len, uint64_t base, uint32_t index, int rows, int cols, int *depth,
+                         std::vector<PngChunk> &tab, uint64_t *zoff)
+{
+	int fr, fc;
+	if (png_parse_ihdr(f, len, &fr, &fc, depth)) return CCT_E_PNG;
+	const size_t tab0 = tab.size();
+	const uint64_t z0 = *zoff;
+	auto refuse = [&](int code) { tab.resize(tab0); *zoff = z0; return code; };
+	tab.push_back(PngChunk{base + 12, 0, 13, index});
+	size_t p = 33;
+	bool idat = false, idat_over = false, iend = false;
+	while (p < len && !iend) {
+		if (len - p < 12) return refuse(CCT_E_PNG);  // no room for length, type and CRC
+		const uint32_t L = be32(f + p);
+		if (L > 0x7FFFFFFFu || (size_t)L > len - p - 12) return refuse(CCT_E_PNG);  // runs past the file
+		const uint8_t *t = f + p + 4;
+		for (int k = 0; k < 4; k++)
+			if (!((t[k] >= 'A' && t[k] <= 'Z') || (t[k] >= 'a' && t[k] <= 'z'))) return refuse(CCT_E_PNG);
+		if (!memcmp(t, "IDAT", 4)) {
+			if (idat_over) return refuse(CCT_E_PNG);  // IDAT chunks must be consecutive
+			idat = true;
+			tab.push_back(PngChunk{base + p + 4, *zoff, L, index | PNG_CHUNK_IDAT});
+			*zoff += L;
+		} else {
+			if (idat) idat_over = true;
+			if (!memcmp(t, "IEND", 4)) {
+				if (L != 0) return refuse(CCT_E_PNG);
+				iend = true;
+			} else if (!(t[0] & 0x20)) {
+				return refuse(CCT_E_PNG);  // a critical chunk this reader does not know (PLTE, a second IHDR, ...)
+			}
+			tab.push_back(PngChunk{base + p + 4, 0, L, index});
+		}
+		p += 12 + (size_t)L;
+	}
+	if (!iend || p != len || !idat) return refuse(CCT_E_PNG);
+	if (fr != rows || fc != cols) return refuse(CCT_E_MIXED);
+	return CCT_OK;
+}
+
+static const char *png_status_text(int code)
+{
+	return code == CCT_E_PNG     ? "not a PNG this reader takes"
+	       : code == CCT_E_MIXED ? "IHDR size differs from the batch shape"
+	       : code == CCT_E_CRC   ? "chunk CRC-32 mismatch"
+	       : code == CCT_E_ZLIB  ? "invalid DEFLATE stream"
+	                             : "stream is not rows * (1 + row bytes) long, or a filter type above 4";
+}
+
+// The INFLATE kernel stores no byte beyond its output stride, and when the flush that crosses the stride is the stream's last one
+// it then reports the stream as invalid (the Adler-32 of bytes it did not sum cannot match) instead of as too long.  So a file
+// the kernel calls invalid is told apart here, on the error path only: libz inflates its IDAT data into a scratch buffer, and a
+// stream that libz takes to its end with another length than `want` is CCT_E_STREAM, not CCT_E_ZLIB.  files: the pass's upload.
+static bool png_valid_stream_of_wrong_length(const uint8_t *files, const std::vector<PngChunk> &tab, uint32_t index, uint64_t want)
+{
+	z_stream zs{};
+	if (inflateInit(&zs) != Z_OK) return false;
+	std::vector<uint8_t> scratch(65536);
+	uint64_t total = 0;
+	int zr = Z_OK;
+	for (const PngChunk &c : tab) {
+		if (c.file != (index | PNG_CHUNK_IDAT) || zr != Z_OK) continue;
+		zs.next_in = const_cast<Bytef *>(files + c.src + 4);
+		zs.avail_in = c.len;
+		while (zs.avail_in && zr == Z_OK) {
+			zs.next_out = scratch.data();
+			zs.avail_out = (uInt)scratch.size();
+			zr = inflate(&zs, Z_NO_FLUSH);
+			total += scratch.size() - zs.avail_out;
+		}
+	}
+	(void)inflateEnd(&zs);
+	return zr == Z_STREAM_END && total != want;
+}
+
+// files c0 .. c0 + nc of the batch
+static int png_read_pass(DecSlot &D, const uint8_t *h_files, const uint64_t *h_offsets, int c0, int nc, int rows, int cols,
+                         int shift, uint16_t *d_img, uint32_t *h_status, float ms[3])
+{
+	int rc;
+	const uint64_t a0 = h_offsets[c0], a1 = h_offsets[c0 + nc];
+	if (a1 < a0) return fail(CCT_E_ARG, "file offsets must not decrease");
+	std::vector<PngChunk> tab;
+	std::vector<uint64_t> zoffs((size_t)nc + 1, 0);
+	std::vector<uint32_t> fst((size_t)nc, 0), zst((size_t)nc, 0), osz((size_t)nc, 0);
+	std::vector<uint8_t> bpp((size_t)nc, 2);
+	uint64_t zoff = 0;
+	int max_bpp = 0;
+	for (int i = 0; i < nc; i++) {
+		const uint64_t f0 = h_offsets[c0 + i], f1 = h_offsets[c0 + i + 1];
+		if (f1 < f0) return fail(CCT_E_ARG, "file offsets must not decrease");
+		int depth = 16;
+		h_status[i] = (uint32_t)png_walk_file(h_files + f0, (size_t)(f1 - f0), f0 - a0, (uint32_t)i, rows, cols, &depth, tab, &zoff);
+		zoffs[(size_t)i + 1] = zoff;
+		if (h_status[i] != CCT_OK) { fst[i] = PNG_ST_SKIP; continue; }
+		bpp[i] = (uint8_t)(depth / 8);
+		max_bpp = std::max(max_bpp, depth / 8);
+	}
+	if (max_bpp == 0) return CCT_OK;  // every file refused by the walk: nothing for the device
+	const size_t stride = (((size_t)rows * (1 + (size_t)cols * max_bpp) + 15) & ~(size_t)15) + 16;
+	const size_t abytes = (size_t)(a1 - a0), zpad = ((size_t)zoff + 31) & ~(size_t)15;
+	if ((rc = D.d_arch.ensure(abytes + 16))) return rc;
+	if ((rc = D.d_png_z.ensure(zpad + 16))) return rc;
+	if ((rc = D.d_png_tab.ensure(tab.size() * sizeof(PngChunk)))) return rc;
+	if ((rc = D.d_png_bpp.ensure((size_t)nc))) return rc;
+	if ((rc = D.d_archoffs.ensure(((size_t)nc + 1) * 8))) return rc;
+	if ((rc = D.d_zstatus.ensure((size_t)nc * 4))) return rc;
+	if ((rc = D.d_status.ensure((size_t)nc * 4))) return rc;
+	if ((rc = D.d_sizes.ensure((size_t)nc * 4))) return rc;
+	if ((rc = D.d_payload.ensure((size_t)nc * stride))) return rc;
+	hipStream_t st = D.stream;
+	DrainOnExit drain(st);
+	HIP_TRY(hipMemcpyAsync(D.d_arch.p, h_files + a0, abytes, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(D.d_png_tab.p, tab.data(), tab.size() * sizeof(PngChunk), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(D.d_png_bpp.p, bpp.data(), (size_t)nc, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(D.d_archoffs.p, zoffs.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(D.d_status.p, fst.data(), (size_t)nc * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemsetAsync((uint8_t *)D.d_png_z.p + (zpad > 32 ? zpad - 32 : 0), 0, zpad > 32 ? 48 : zpad + 16, st));  // the INFLATE kernel reads ahead
+	PngUnpackArgs ua{};
+	ua.files = (const uint8_t *)D.d_arch.p; ua.chunks = (const PngChunk *)D.d_png_tab.p;
+	ua.streams = (uint8_t *)D.d_png_z.p; ua.status = (uint32_t *)D.d_status.p;
+	HIP_TRY(hipEventRecord(D.ev_d0, st));
+	HIP_TRY(launch_png_unpack(ua, (uint32_t)tab.size(), st));
+	HIP_TRY(hipEventRecord(D.ev_d1, st));
+	InflateArgs ia{};
+	ia.in = (const uint8_t *)D.d_png_z.p; ia.in_total = zpad;
+	ia.offsets = (const uint64_t *)D.d_archoffs.p; ia.skip = 0;
+	ia.out = (uint8_t *)D.d_payload.p; ia.out_stride = stride;
+	ia.out_sizes = (uint32_t *)D.d_sizes.p; ia.status = (uint32_t *)D.d_zstatus.p;
+	HIP_TRY(launch_inflate(ia, nc, st, inflate_lanes_now()));
+	HIP_TRY(hipEventRecord(D.ev_k_dec0, st));
+	PngUnfilterArgs fa{};
+	fa.rows = (uint8_t *)D.d_payload.p; fa.rows_stride = stride;
+	fa.row_sizes = (const uint32_t *)D.d_sizes.p; fa.zstatus = (const uint32_t *)D.d_zstatus.p;
+	fa.status = (uint32_t *)D.d_status.p; fa.bpp = (const uint8_t *)D.d_png_bpp.p;
+	fa.nrows = rows; fa.cols = cols; fa.shift = shift;
+	fa.images = d_img;
+	HIP_TRY(launch_png_unfilter(fa, nc, g_ctx.png_unfilter_waves, st));
+	HIP_TRY(hipEventRecord(D.ev_k_dec1, st));
+	HIP_TRY(hipMemcpyAsync(fst.data(), D.d_status.p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(zst.data(), D.d_zstatus.p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(osz.data(), D.d_sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	float t[3] = {0, 0, 0};
+	HIP_TRY(hipEventElapsedTime(&t[0], D.ev_d0, D.ev_d1));
+	HIP_TRY(hipEventElapsedTime(&t[1], D.ev_d1, D.ev_k_dec0));
+	HIP_TRY(hipEventElapsedTime(&t[2], D.ev_k_dec0, D.ev_k_dec1));
+	for (int k = 0; k < 3; k++) ms[k] += t[k];
+	for (int i = 0; i < nc; i++) {
+		if (h_status[i] != CCT_OK) continue;
+		const uint32_t want = (uint32_t)((size_t)rows * (1 + (size_t)cols * bpp[i]));
+		if (fst[i] & PNG_ST_CRC) h_status[i] = CCT_E_CRC;
+		else if (zst[i] & CCT_ST_ZLIB) h_status[i] = png_valid_stream_of_wrong_length(h_files + a0, tab, (uint32_t)i, want) ? CCT_E_STREAM : CCT_E_ZLIB;
+		else if ((zst[i] & CCT_ST_STREAM) || osz[i] != want || (fst[i] & PNG_ST_FILTER)) h_status[i] = CCT_E_STREAM;
+	}
+	return CCT_OK;
+}
+
+int cct_png_read_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int shift,
+                       uint16_t *images, int images_on_device, size_t images_cap_px, uint32_t *h_status)
+{
+	if (n < 0) return fail(CCT_E_ARG, "negative batch size");
+	if (shift < 0 || shift > 15) return fail(CCT_E_ARG, "PNG sample shift %d: 0 .. 15", shift);
+	if (rows < 1 || cols < 1) return fail(CCT_E_ARG, "PNG shape %d x %d: rows and cols must be >= 1", rows, cols);
+	if (png_filtered_bytes(rows, cols) > PNG_MAX_FILTERED)
+		return fail(CCT_E_ARG, "PNG shape %d x %d: %zu filtered bytes exceed the reader's limit (%zu)", rows, cols,
+		            png_filtered_bytes(rows, cols), PNG_MAX_FILTERED);
+	if (n > 0 && (!h_files || !h_offsets || !images || !h_status)) return fail(CCT_E_ARG, "null argument");
+	const size_t N = (size_t)rows * cols;
+	if (images_cap_px / N < (size_t)n) return fail(CCT_E_CAP, "output holds %zu pixels, need %zu", images_cap_px, (size_t)n * N);
+	if (n == 0) return CCT_OK;
+	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device before slot and shared lock (cct_zlib_decompress_batch)
+		std::lock_guard<std::mutex> lk(g_mu);
+		int rc0 = ensure_ctx();
+		if (rc0) return rc0;
+	}
+	std::unique_lock<std::mutex> lkd;
+	DecSlot &D = acquire_decode_slot(lkd);
+	ApiCall in_call;
+	int rc;
+	HIP_TRY(hipSetDevice(g_ctx.device));
+	// a pass holds the inflated rows of its files: at most DEFLATE_PASS_BYTES of them, as the writer's passes do
+	const size_t stride16 = ((png_filtered_bytes(rows, cols) + 15) & ~(size_t)15) + 16;
+	const int per_pass = (int)std::max<size_t>(1, DEFLATE_PASS_BYTES / stride16);
+	if (!images_on_device && (rc = D.d_images.ensure((size_t)std::min(n, per_pass) * N * 2))) return rc;
+	float ms[3] = {0, 0, 0};
+	for (int c0 = 0; c0 < n; c0 += per_pass) {
+		const int nc = std::min(per_pass, n - c0);
+		uint16_t *d_img = images_on_device ? images + (size_t)c0 * N : (uint16_t *)D.d_images.p;
+		if ((rc = png_read_pass(D, h_files, h_offsets, c0, nc, rows, cols, shift, d_img, h_status + c0, ms))) return rc;
+		if (!images_on_device) {
+			HIP_TRY(hipMemcpyAsync(images + (size_t)c0 * N, d_img, (size_t)nc * N * 2, hipMemcpyDeviceToHost, D.stream));
+			HIP_TRY(hipStreamSynchronize(D.stream));
+		}
+	}
+	tl_h2d_ms = ms[0]; tl_inflate_ms = ms[1]; tl_dec_kernel_ms = ms[2];
+	for (int i = 0; i < n; i++)
+		if (h_status[i] != CCT_OK) return fail((int)h_status[i], "file %d: %s", i, png_status_text((int)h_status[i]));
+	return CCT_OK;
+}
+
 int cct_read_header(const uint8_t *h_file, size_t len, const char magic[4], cct_header *out)
 {
 	if (!h_file || !out) return fail(CCT_E_ARG, "null argument");
@@ -2059,6 +2289,10 @@ int cct_set_option(const char *key, int value)
 		if (value != 0 && value != 256 && value != 512) return fail(CCT_E_ARG, "inflate_lanes must be 0 (automatic), 256 or 512");
 		g_ctx.inflate_lanes = value; return CCT_OK;
 	}
+	if (!strcmp(key, "png_unfilter_waves")) {
+		if (value != 1 && value != 2 && value != 4 && value != 8) return fail(CCT_E_ARG, "png_unfilter_waves must be 1, 2, 4 or 8");
+		g_ctx.png_unfilter_waves = value; return CCT_OK;
+	}
 	if (!strcmp(key, "wg_threads")) {
 		if (value != 256 && value != 512 && value != 1024) return fail(CCT_E_ARG, "wg_threads must be 256, 512 or 1024");
 		g_ctx.wg_threads = value; return CCT_OK;
@@ -2085,6 +2319,7 @@ int cct_get_option(const char *key, int *value)
 	if (!strcmp(key, "decode_slots")) { *value = g_ctx.dec_slots; return CCT_OK; }
 	if (!strcmp(key, "inflate_lanes")) { *value = g_ctx.inflate_lanes; return CCT_OK; }
 	if (!strcmp(key, "last_inflate_lanes")) { *value = g_ctx.last_inflate_lanes; return CCT_OK; }
+	if (!strcmp(key, "png_unfilter_waves")) { *value = g_ctx.png_unfilter_waves; return CCT_OK; }
 	if (!strcmp(key, "wg_threads")) { *value = g_ctx.wg_threads; return CCT_OK; }
 	return fail(CCT_E_ARG, "unknown option %s", key);
 }

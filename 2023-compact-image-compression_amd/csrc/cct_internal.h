@@ -213,6 +213,46 @@ struct PngPackArgs {
 // grid: max_chunks >= the IDAT chunks of the longest stream
 hipError_t launch_png_pack(const PngPackArgs &a, int n, uint32_t max_chunks, hipStream_t st);
 
+// ---- PNG reader (png_read_kernels.hip) ------------------------------------------------------------
+// One chunk of one file, as the host's walk over the chunk heads found it (api.cpp png_walk_file).  The bounds argument: the
+// device kernels derive every address they touch from this table and from the caller's (rows, cols), never from file content.
+// The walk reads a chunk's length only after it has checked that the 8-byte head lies inside the file, and enters the chunk
+// only after it has checked length <= file size - position - 12, so [src, src + 4 + len + 4) -- type, data, CRC -- lies inside
+// the file and with it inside the uploaded archive.  dst is the running sum of the IDAT lengths entered before it, for the
+// batch, so [dst, dst + len) lies inside the gathered buffer, which is allocated for the final sum (plus the INFLATE kernel's
+// read-ahead padding), and inside [offsets[file], offsets[file + 1]), the stream the INFLATE kernel is given for that file.
+// png_unpack_kernel reads and writes nothing else.  The INFLATE kernel bounds its output by its stride.
+// png_unfilter_kernel touches the file's rows_stride bytes of inflated rows and its rows * cols samples of the output, both
+// indexed by (row < rows, column < cols) alone; a file is unfiltered only if its stream inflated to exactly
+// rows * (1 + cols * bpp) bytes, so every byte it reads was written by this call.  A filter byte selects one of five
+// formulas; a value above 4 sets a status bit.
+struct PngChunk {
+	uint64_t src;   // offset of the chunk's type field in the uploaded files
+	uint64_t dst;   // IDAT: offset of its data in the gathered zlib streams
+	uint32_t len;   // data bytes (<= 2^31 - 1)
+	uint32_t file;  // index of the file in the pass | PNG_CHUNK_IDAT
+};
+constexpr uint32_t PNG_CHUNK_IDAT = 1u << 31;
+// per-file status word of a pass (device): CRC and FILTER are set by the kernels, SKIP by the host for a file its walk refused
+constexpr uint32_t PNG_ST_CRC = 1u, PNG_ST_FILTER = 2u, PNG_ST_SKIP = 4u;
+struct PngUnpackArgs {
+	const uint8_t *files;     // the pass's files as uploaded
+	const PngChunk *chunks;
+	uint8_t *streams;         // gathered zlib streams
+	uint32_t *status;
+};
+hipError_t launch_png_unpack(const PngUnpackArgs &a, uint32_t n_chunks, hipStream_t st);
+struct PngUnfilterArgs {
+	uint8_t *rows; size_t rows_stride;              // inflated rows of file i at rows + i * rows_stride; the kernel writes the last row of a band back
+	const uint32_t *row_sizes, *zstatus;            // the INFLATE kernel's out_sizes and status
+	uint32_t *status;
+	const uint8_t *bpp;                             // bytes per sample of every file: 1 or 2
+	int nrows, cols, shift;
+	uint16_t *images;                               // n * nrows * cols
+};
+constexpr int PNG_UNFILTER_WAVES = 8;  // waves per image (option "png_unfilter_waves": 1, 2, 4, 8)
+hipError_t launch_png_unfilter(const PngUnfilterArgs &a, int n, int waves, hipStream_t st);
+
 // ---- gate between the decode and the encode stream (sched_kernels.hip) ---------------------------
 hipError_t launch_gate_bump(uint32_t *word, hipStream_t st);
 hipError_t launch_gate_wait(const uint32_t *gate, uint32_t want_pass, uint32_t grace_us, uint32_t timeout_us, hipStream_t st);

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cct_internal.h"
+#include "png_device.h"
 
 namespace cct {
 namespace {
@@ -31,14 +32,6 @@ __device__ __forceinline__ uint32_t png_cost(uint32_t v)
 {
 	v &= 255u;
 	return v < 128u ? v : 256u - v;
-}
-
-// PNG spec 9.4: ties go to a, then b, then c
-__device__ __forceinline__ uint32_t paeth(uint32_t a, uint32_t b, uint32_t c)
-{
-	const int p = (int)a + (int)b - (int)c;
-	const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
-	return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
 // filter type f (0 None, 1 Sub, 2 Up, 4 Paeth) of byte x with left a, up b, up-left c
@@ -98,33 +91,6 @@ __global__ void __launch_bounds__(256) png_filter_kernel(const uint16_t *img, in
 	}
 }
 
-// zlib crc32.c multmodp: a * b modulo the CRC-32 polynomial, bit-reflected (bit 31 = x^0).  a must not be 0.
-__device__ uint32_t multmodp(uint32_t a, uint32_t b)
-{
-	uint32_t m = 1u << 31, p = 0;
-	for (;;) {
-		if (a & m) {
-			p ^= b;
-			if ((a & (m - 1u)) == 0) break;
-		}
-		m >>= 1;
-		b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-	}
-	return p;
-}
-
-// x^(8 n) modulo the polynomial: the operator that appends n zero bytes to a raw CRC register
-__device__ uint32_t x8n_mod(uint32_t n)
-{
-	uint32_t p = 1u << 31, sq = 1u << 23;  // x^0, x^8
-	while (n) {
-		if (n & 1u) p = multmodp(sq, p);
-		sq = multmodp(sq, sq);
-		n >>= 1;
-	}
-	return p;
-}
-
 __constant__ uint8_t c_png_sig[8] = {0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A};
 __constant__ uint8_t c_png_iend[12] = {0, 0, 0, 0, 0x49, 0x45, 0x4E, 0x44, 0xAE, 0x42, 0x60, 0x82};
 __constant__ uint8_t c_idat[4] = {0x49, 0x44, 0x41, 0x54};
@@ -133,7 +99,8 @@ __constant__ uint8_t c_idat[4] = {0x49, 0x44, 0x41, 0x54};
 // the CRC-32 of type + data.  The CRC: the 4 + len bytes are cut into 256 segments of equal length `seg`, aligned to the end
 // (the first segment starts with up to 255 virtual zero bytes, which leave a raw CRC register at 0), so every lane's raw
 // table CRC moves to its place by a power of two of the one-segment operator x^(8 seg): a tree of 8 levels, each level one
-// squaring of the operator (crc32_combine for equal lengths).  Chunk 0 also writes the signature and IHDR; the last chunk
+// squaring of the operator (crc32_combine for equal lengths); crc32_workgroup (png_device.h) is the same scheme as a function,
+// which the reader uses (calling it here moved this kernel's instructions about).  Chunk 0 also writes the signature and IHDR; the last chunk
 // IEND and the file size.
 __global__ void __launch_bounds__(256) png_pack_kernel(PngPackArgs a)
 {

@@ -61,6 +61,8 @@ extern "C" {
 #define CCT_E_DEVICE 8    /* no usable gfx950 device / HIP runtime error */
 #define CCT_E_ARG 9       /* unsupported argument (block_size outside 3..64, n<0, ...) */
 #define CCT_E_MIXED 10    /* decode batch whose members differ in shape or flags */
+#define CCT_E_PNG 11      /* cct_png_read_batch / cct_png_info: not a PNG this reader takes -> ValueError */
+#define CCT_E_CRC 12      /* cct_png_read_batch: a chunk's CRC-32 does not match           -> ValueError */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
 #define CCT_FLAG_FRACTAL 1u       /* transforms.fractal      (core.py:234) */
@@ -223,6 +225,34 @@ size_t cct_png_bound(int rows, int cols);
 int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, int rows, int cols, int shift, int level,
                          uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 
+/* ---- PNG reader ------------------------------------------------------------------------ */
+/* The inverse of the writer and of the reference's png_to_array (lib/png.py:33-38, value >> 4): grayscale PNG files of bit
+ * depth 8 or 16 -> uint16 rasters, pixel = sample >> shift (8-bit samples widened first; 16-bit samples are big-endian in
+ * the file).  Accepted: colour type 0, depth 8 or 16, compression 0, filter method 0, interlace 0; the five row filter types;
+ * any number of IDAT chunks of any length (0 included); ancillary chunks anywhere.
+ * cct_png_info: host only, no device: signature + IHDR of one file; CCT_E_PNG for anything the reader does not take.
+ * cct_png_read_batch: n files laid out back to back (file i = h_files[h_offsets[i] .. h_offsets[i+1])), all of IHDR height ==
+ * rows and width == cols (the two depths may mix), -> n*rows*cols uint16 at `images` (host or device).  The host walks the
+ * chunk heads; the chunk CRC-32s are checked, the IDAT data gathered, the streams inflated and the rows unfiltered on the
+ * device (a decode slot, see the threading paragraph at the top).  Per-file refusals in h_status[i]; the other files still
+ * decode, and the call returns the first non-OK status:
+ *   CCT_E_PNG    bad signature; first chunk not a 13-byte IHDR; a chunk length running past the file; no IEND, or an IEND
+ *                with data; bytes after IEND; no IDAT; IDAT chunks not consecutive; an unknown critical chunk (upper-case
+ *                first letter; PLTE counts); a chunk type that is not four letters; any other colour type, depth, compression,
+ *                filter method or interlace
+ *   CCT_E_MIXED  IHDR size differs from rows x cols
+ *   CCT_E_CRC    CRC-32 mismatch on any chunk, ancillary ones included
+ *   CCT_E_ZLIB   whatever the device INFLATE rejects (cct_zlib_decompress_batch)
+ *   CCT_E_STREAM the stream inflates to fewer or more than rows * (1 + cols * depth/8) bytes, or a filter byte above 4
+ * This is stricter than Pillow in two intended ways: Pillow (12.2) checks no CRC of an ancillary chunk behind the image
+ * data, and it opens a stream that carries bytes to spare, or that is a whole row short, without an error.  The raster of a refused file is unspecified; nothing is written outside
+ * that file's own rows*cols slot.  Whole-call errors, before the device is touched: CCT_E_ARG for shift outside 0 .. 15, rows
+ * or cols < 1, n < 0, more than 2^30 - 512 filtered bytes (rows * (1 + 2*cols), the writer's limit); CCT_E_CAP for
+ * images_cap_px < n*rows*cols. */
+int cct_png_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *bit_depth);
+int cct_png_read_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int shift,
+                       uint16_t *images, int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
+
 /* INFLATE stage alone, on the device: n zlib streams (h_in[h_offsets[i] .. h_offsets[i+1])) -> the bytes
  * zlib.decompress returns for each (what the reference calls at core.py:421).  Output i lands at
  * h_out + i*out_stride (out_stride a multiple of 16); h_status[i] = CCT_OK, CCT_E_ZLIB (anything libz
@@ -284,10 +314,12 @@ int cct_packbits_decode_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
  * [0] encode kernel (HIP events on the library stream), [1] packed files device -> host, [2] DEFLATE (HIP events
  * on the device path, also after cct_zlib_compress_batch / _level / _strategy; host wall on the libz path), [3] INFLATE
  * (likewise), [4] decode kernel (HIP events),
- * [5] reserved. */
+ * [5] reserved.  After cct_png_read_batch: [3] INFLATE, [4] the unfilter kernel, [5] the unpack kernel (CRC check + IDAT
+ * gather), HIP events, summed over the passes of the call. */
 int cct_last_timings(float *out6);
 /* Options: "encode_slots" / "decode_slots" (1 or 2 batches on the device at a time), "device_deflate" / "device_inflate"
- * (0: that stage on the host thread team of "zlib_threads" threads), "inflate_lanes" (lanes per stream of the INFLATE kernel:
+ * (0: that stage on the host thread team of "zlib_threads" threads), "png_unfilter_waves" (waves per image of the PNG reader's
+ * unfilter kernel: 1, 2, 4 or 8), "inflate_lanes" (lanes per stream of the INFLATE kernel:
  * 256, 512, or 0 = 512 unless an encode call is in flight when the decode starts; "last_inflate_lanes" reads back the choice),
  * "tile_path", "stream_tpg", "deflate_graph", "deflate_compact_records", "wg_threads" (kernel choice and
  * tuning), "decode_yields" / "queue_ahead" (scheduling of pipelined calls; 0 switches them off). */
