@@ -1929,34 +1929,43 @@ __global__ void __launch_bounds__(256) dfl_adler_kernel(DeflateArgs a)
 	}
 }
 
-// bit offsets of every block, .cct header, zlib header, Adler trailer, final size (one lane per slice)
-__global__ void dfl_layout_kernel(DeflateArgs a, int n)
+// bit offsets of every block, .cct header, zlib header, Adler trailer, final size: one wave per slice.  The blocks' records are
+// loaded side by side, 64 at a time; only the running offset is serial (a stored block rounds it up to a byte), and that runs
+// in registers.  (One lane per slice paid a memory round trip per block, one after the other.)
+__global__ void __launch_bounds__(64) dfl_layout_kernel(DeflateArgs a, int n)
 {
-	const int s = blockIdx.x * blockDim.x + threadIdx.x;
+	const int s = blockIdx.x, lane = threadIdx.x;
 	if (s >= n) return;
 	uint8_t *out = a.out + (size_t)s * a.out_stride;
-	for (int i = 0; i < 13; i++) out[i] = a.header13[i];
-	out[13] = 0x78; out[14] = (uint8_t)a.zlib_flg;  // CMF/FLG for wbits 15 and the level (deflate.c:819-836)
-	uint64_t bit = 8ull * 15;
 	BlockMeta *meta = a.block_meta + (size_t)s * a.max_blocks;
 	const uint32_t nb = a.n_blocks[s];
-	for (uint32_t m = 0; m < nb; m++) {
-		BlockMeta bm = meta[m];
-		bm.bit_off = bit;
-		if (bm.type == 0) {  // _tr_stored_block: 3 header bits, bi_windup, LEN, NLEN, bytes
-			bit = (bit + 3 + 7) & ~7ull;
-			bit += 32 + 8ull * bm.stored_len;
-		} else {
-			bit += 3 + bm.hdr_nbits + bm.body_bits;
-		}
-		if (bm.last) bit = (bit + 7) & ~7ull;  // bi_windup
-		meta[m] = bm;
-	}
-	const uint64_t byte = bit >> 3;
 	const uint32_t ad = a.adler[s];
-	out[byte + 0] = (uint8_t)(ad >> 24); out[byte + 1] = (uint8_t)(ad >> 16);
-	out[byte + 2] = (uint8_t)(ad >> 8);  out[byte + 3] = (uint8_t)ad;
-	a.out_sizes[s] = (uint32_t)(byte + 4);
+	uint64_t bit = 8ull * 15;
+	for (uint32_t m0 = 0; m0 < nb; m0 += 64) {
+		const uint32_t m = m0 + (uint32_t)lane, cnt = min(64u, nb - m0);
+		const BlockMeta bm = meta[min(m, nb - 1)];
+		// bits of the block behind its 3 header bits (stored: behind the byte boundary that follows them -- _tr_stored_block:
+		// 3 header bits, bi_windup, LEN, NLEN, bytes)
+		const uint32_t flags = (bm.type == 0 ? 1u : 0u) | (bm.last ? 2u : 0u);
+		const uint64_t size = bm.type == 0 ? 32 + 8ull * bm.stored_len : 3ull + bm.hdr_nbits + bm.body_bits;
+		uint64_t mine = 0;
+		for (uint32_t j = 0; j < cnt; j++) {
+			const uint32_t fj = __shfl(flags, (int)j);
+			const uint64_t zj = __shfl((unsigned long long)size, (int)j);
+			if (j == (uint32_t)lane) mine = bit;
+			bit = (fj & 1u) ? ((bit + 3 + 7) & ~7ull) + zj : bit + zj;
+			if (fj & 2u) bit = (bit + 7) & ~7ull;  // bi_windup
+		}
+		if (m < nb) meta[m].bit_off = mine;
+	}
+	if (lane == 0) {
+		for (int i = 0; i < 13; i++) out[i] = a.header13[i];
+		out[13] = 0x78; out[14] = (uint8_t)a.zlib_flg;  // CMF/FLG for wbits 15 and the level (deflate.c:819-836)
+		const uint64_t byte = bit >> 3;
+		out[byte + 0] = (uint8_t)(ad >> 24); out[byte + 1] = (uint8_t)(ad >> 16);
+		out[byte + 2] = (uint8_t)(ad >> 8);  out[byte + 3] = (uint8_t)ad;
+		a.out_sizes[s] = (uint32_t)(byte + 4);
+	}
 }
 
 // ------------------------------------------------------------------ 6. bit emission
@@ -1973,10 +1982,18 @@ __device__ __forceinline__ void or_bits(uint32_t *words, uint64_t bit, uint64_t 
 	if (sh + nbits > 64) atomicOr(&words[w + 2], (uint32_t)hi);
 }
 
+// A lane codes EMIT_K consecutive symbols and joins their bits in registers, so the workgroup scan, its barriers and the flush
+// come once per EMIT_T symbols, and a lane ORs merged words into LDS (four 9-bit literals: two words) instead of every code.
+#ifndef CCT_EMIT_K
+#define CCT_EMIT_K 4
+#endif
+constexpr int EMIT_K = CCT_EMIT_K;
+constexpr int EMIT_T = 256 * EMIT_K;                  // symbols per iteration of a workgroup
+constexpr int EMIT_LIMBS = (EMIT_K * 48 + 63) / 64;   // 64-bit limbs of a lane's bit string (a symbol: <= 48 bits)
+constexpr int EMIT_WBUF = EMIT_T * 48 / 32 + 8;       // words of an iteration: 31 bits of offset + EMIT_T * 48 bits, rounded up
 __global__ void __launch_bounds__(256) dfl_emit_kernel(DeflateArgs a)
 {
-	__shared__ uint32_t wsum[4];
-	__shared__ unsigned long long s_run;
+	__shared__ uint32_t wsum[2][4];
 	const int s = blockIdx.y, m = blockIdx.x;
 	if ((uint32_t)m >= a.n_blocks[s]) return;
 	const BlockMeta bm = a.block_meta[(size_t)s * a.max_blocks + m];
@@ -2007,11 +2024,11 @@ __global__ void __launch_bounds__(256) dfl_emit_kernel(DeflateArgs a)
 	const uint32_t *sym = a.sym + (size_t)s * a.in_stride + bm.first_sym;
 	const bool dyn = bm.type == 2;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	// code tables of this block in LDS; code bits of 256 symbols are merged into LDS words first, so the
-	// output sees one atomic per 32-bit word instead of two or three per symbol
+	// code tables of this block in LDS; code bits of EMIT_T symbols are merged into LDS words first, so the
+	// output sees one store per 32-bit word instead of two or three atomics per symbol
 	__shared__ uint16_t t_lcode[L_CODES + 2], t_dcode[D_CODES + 2];
 	__shared__ uint8_t t_llen[L_CODES + 2], t_dlen[D_CODES + 2];
-	__shared__ uint32_t wbuf[400];  // 256 symbols x <= 48 bits = 384 words, + alignment word
+	__shared__ uint32_t wbuf[2][EMIT_WBUF];  // two iterations' words: one is flushed and zeroed while the next one fills the other
 	// the symbol -> code tables of trees.c, staged in LDS: a __constant__ lookup with a per-lane index is a global
 	// load, and every iteration with a match in it would wait for four of them in a row
 	__shared__ uint8_t t_length_code[256], t_dist_code[512], t_extra_l[32], t_extra_d[32];
@@ -2036,84 +2053,133 @@ __global__ void __launch_bounds__(256) dfl_emit_kernel(DeflateArgs a)
 		if (t < 29) { t_extra_l[t] = xl; t_base_length[t] = bl; }
 		if (t < 30) { t_extra_d[t] = xd; t_base_dist[t] = bd; }
 	}
-	if (threadIdx.x == 0) s_run = bit;
-	for (int i = threadIdx.x; i < 400; i += blockDim.x) wbuf[i] = 0;
+	for (int i = threadIdx.x; i < 2 * EMIT_WBUF; i += blockDim.x) (&wbuf[0][0])[i] = 0;
 	__syncthreads();
-	// the symbols of the next 256 are requested before these are coded (index clamped, not tested: a load inside a
+	// the symbols of the next iteration are requested before these are coded (index clamped, not tested: a load inside a
 	// conditional is waited for on the spot)
 	const uint32_t last_sym = bm.nsym ? bm.nsym - 1 : 0;
-	uint32_t vnext = sym[min((uint32_t)threadIdx.x, last_sym)];
-	for (uint32_t base = 0; base <= bm.nsym; base += blockDim.x) {  // one extra slot for END_BLOCK
-		const uint32_t i = base + threadIdx.x;
-		uint64_t bits = 0;
-		int nb = 0;
-		const uint32_t v = vnext;
-		vnext = sym[min(i + blockDim.x, last_sym)];
-		if (i < bm.nsym) {
-			uint32_t dist = v >> 16;
-			const uint32_t lc = v & 0xFFu;
-			if (dist == 0) {
-				bits = t_lcode[lc];
-				nb = t_llen[lc];
-			} else {  // compress_block, trees.c:1070-1110
-				int code = t_length_code[lc];
-				const int lsym = code + 256 + 1;
-				bits = t_lcode[lsym];
-				nb = t_llen[lsym];
-				int extra = t_extra_l[code];
-				if (extra) { bits |= (uint64_t)(lc - t_base_length[code]) << nb; nb += extra; }
-				dist--;
-				code = dist < 256 ? t_dist_code[dist] : t_dist_code[256 + (dist >> 7)];
-				bits |= (uint64_t)t_dcode[code] << nb;
-				nb += t_dlen[code];
-				extra = t_extra_d[code];
-				if (extra) { bits |= (uint64_t)(dist - t_base_dist[code]) << nb; nb += extra; }
+	uint32_t vnext[EMIT_K];
+#pragma unroll
+	for (int k = 0; k < EMIT_K; k++) vnext[k] = sym[min((uint32_t)(threadIdx.x * EMIT_K + k), last_sym)];
+	uint64_t run = bit;  // bit position of the iteration's first symbol, kept by every lane
+	int par = 0;
+	for (uint32_t base = 0; base <= bm.nsym; base += EMIT_T, par ^= 1) {  // one extra slot for END_BLOCK
+		const uint32_t i0 = base + threadIdx.x * EMIT_K;
+		uint32_t v[EMIT_K];
+#pragma unroll
+		for (int k = 0; k < EMIT_K; k++) v[k] = vnext[k];
+#pragma unroll
+		for (int k = 0; k < EMIT_K; k++) vnext[k] = sym[min(i0 + (uint32_t)(EMIT_T + k), last_sym)];
+		// the lane's symbols back to back, from bit 0 of acc
+		uint64_t acc[EMIT_LIMBS];
+#pragma unroll
+		for (int j = 0; j < EMIT_LIMBS; j++) acc[j] = 0;
+		uint32_t ltot = 0;
+#pragma unroll
+		for (int k = 0; k < EMIT_K; k++) {
+			const uint32_t i = i0 + k;
+			uint64_t bits = 0;
+			int nb = 0;
+			if (i < bm.nsym) {
+				uint32_t dist = v[k] >> 16;
+				const uint32_t lc = v[k] & 0xFFu;
+				if (dist == 0) {
+					bits = t_lcode[lc];
+					nb = t_llen[lc];
+				} else {  // compress_block, trees.c:1070-1110
+					int code = t_length_code[lc];
+					const int lsym = code + 256 + 1;
+					bits = t_lcode[lsym];
+					nb = t_llen[lsym];
+					int extra = t_extra_l[code];
+					if (extra) { bits |= (uint64_t)(lc - t_base_length[code]) << nb; nb += extra; }
+					dist--;
+					code = dist < 256 ? t_dist_code[dist] : t_dist_code[256 + (dist >> 7)];
+					bits |= (uint64_t)t_dcode[code] << nb;
+					nb += t_dlen[code];
+					extra = t_extra_d[code];
+					if (extra) { bits |= (uint64_t)(dist - t_base_dist[code]) << nb; nb += extra; }
+				}
+			} else if (i == bm.nsym) {
+				bits = t_lcode[END_BLOCK];
+				nb = t_llen[END_BLOCK];
 			}
-		} else if (i == bm.nsym) {
-			bits = t_lcode[END_BLOCK];
-			nb = t_llen[END_BLOCK];
+			const uint32_t q = ltot >> 6, r = ltot & 63;
+			const uint64_t lo = bits << r, hi = r ? bits >> (64 - r) : 0ull;
+#pragma unroll
+			for (int j = 0; j < EMIT_LIMBS; j++) {
+				if (q == (uint32_t)j) acc[j] |= lo;
+				if (q + 1 == (uint32_t)j) acc[j] |= hi;
+			}
+			ltot += (uint32_t)nb;
 		}
-		// exclusive scan of bit counts over the workgroup
-		uint32_t inc = (uint32_t)nb;
+		// exclusive scan of the lanes' bit counts over the workgroup
+		uint32_t inc = ltot;
 #pragma unroll
 		for (int d = 1; d < 64; d <<= 1) {
 			const uint32_t t = __shfl_up(inc, d);
 			if (lane >= d) inc += t;
 		}
-		if (lane == 63) wsum[wave] = inc;
+		if (lane == 63) wsum[par][wave] = inc;
 		__syncthreads();
 		uint32_t wb = 0, tot = 0;
-		for (int w = 0; w < 4; w++) { if (w < wave) wb += wsum[w]; tot += wsum[w]; }
-		const uint64_t run = s_run;
-		const uint32_t lbit = (uint32_t)(run & 31) + wb + inc - (uint32_t)nb;  // bit position inside wbuf
-		if (nb) {
-			const uint32_t w0 = lbit >> 5, sh = lbit & 31;
-			const uint64_t lo = bits << sh;
-			atomicOr(&wbuf[w0], (uint32_t)lo);
-			if (sh + nb > 32) atomicOr(&wbuf[w0 + 1], (uint32_t)(lo >> 32));
-			if (sh + nb > 64) atomicOr(&wbuf[w0 + 2], (uint32_t)(bits >> (64 - sh)));
+		for (int w = 0; w < 4; w++) { if (w < wave) wb += wsum[par][w]; tot += wsum[par][w]; }
+		uint32_t *wbf = wbuf[par];
+		const uint32_t lbit = (uint32_t)(run & 31) + wb + inc - ltot;  // bit position inside wbuf
+		if (ltot) {
+			// acc << sh as 32-bit words: word j = a[j] << sh | a[j - 1] >> (32 - sh), with a[] the 32-bit halves of acc
+			const uint32_t w0 = lbit >> 5, sh = lbit & 31, nw = (sh + ltot + 31) >> 5;
+#pragma unroll
+			for (int j = 0; j <= 2 * EMIT_LIMBS; j++) {
+				const uint32_t aj = j < 2 * EMIT_LIMBS ? (uint32_t)(acc[j >> 1] >> (32 * (j & 1))) : 0u;
+				const uint32_t ap = j > 0 ? (uint32_t)(acc[(j - 1) >> 1] >> (32 * ((j - 1) & 1))) : 0u;
+				const uint32_t w = (uint32_t)((((uint64_t)aj << 32) | ap) >> (32 - sh));
+				if ((uint32_t)j < nw && w) atomicOr(&wbf[w0 + j], w);  // (the first and the last word are shared with the neighbours)
+			}
 		}
 		__syncthreads();
+		// the words strictly inside the iteration's bit range are its own: plain stores, zeros included.  The first and the last
+		// are shared with the header, the neighbouring iterations, the next block or the trailer
 		const uint32_t nwords = ((uint32_t)(run & 31) + tot + 31) >> 5;
 		const uint64_t gw = run >> 5;
 		for (uint32_t k = threadIdx.x; k < nwords; k += blockDim.x) {
-			const uint32_t v = wbuf[k];
-			if (v) atomicOr(&words[gw + k], v);  // edge words are shared with the neighbouring 256 symbols / blocks
-			wbuf[k] = 0;
+			const uint32_t w = wbf[k];
+			wbf[k] = 0;
+			if (k == 0 || k == nwords - 1) { if (w) atomicOr(&words[gw + k], w); }
+			else words[gw + k] = w;
 		}
-		if (threadIdx.x == 0) s_run = run + tot;
-		__syncthreads();
+		run += tot;
+		// (no barrier here: the next iteration fills the other buffer and the other wsum row, and comes back to these only after
+		// its own two barriers)
 	}
 }
 
-// files back to back (exclusive scan of sizes by one workgroup, then a grid copy) for ONE device->host copy
+// files back to back (exclusive scan of sizes by one workgroup: chunks of 256 with a running carry, then a grid copy) for ONE
+// device->host copy
 __global__ void __launch_bounds__(256) dfl_pack_offsets_kernel(const uint32_t *sizes, int n, uint64_t *offsets, int exact)
 {
-	if (threadIdx.x == 0 && blockIdx.x == 0) {
-		uint64_t acc = 0;
-		for (int i = 0; i < n; i++) { offsets[i] = acc; acc += exact ? sizes[i] : ((sizes[i] + 15u) & ~15u); }
-		offsets[n] = acc;
+	__shared__ unsigned long long wsum[4];
+	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	unsigned long long carry = 0;
+	for (int base = 0; base < n; base += 256) {
+		const int i = base + t;
+		const uint32_t sz = i < n ? sizes[i] : 0u;
+		const unsigned long long v = exact ? sz : (unsigned long long)((sz + 15u) & ~15u);
+		unsigned long long inc = v;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const unsigned long long u = __shfl_up(inc, d);
+			if (lane >= d) inc += u;
+		}
+		if (lane == 63) wsum[wave] = inc;
+		__syncthreads();
+		unsigned long long wb = 0, tot = 0;
+		for (int w = 0; w < 4; w++) { if (w < wave) wb += wsum[w]; tot += wsum[w]; }
+		if (i < n) offsets[i] = carry + wb + inc - v;
+		carry += tot;
+		__syncthreads();
 	}
+	if (t == 0) offsets[n] = carry;
 }
 __global__ void __launch_bounds__(256) dfl_pack_kernel(const uint8_t *src, size_t stride, const uint32_t *sizes,
                                                        const uint64_t *offsets, uint8_t *dst)
@@ -2139,10 +2205,38 @@ __global__ void dfl_offsets_kernel(DeflateArgs a, int n)
 		for (int s = threadIdx.x; s < n; s += blockDim.x) { a.postloop_lit[s] = 0; a.heavy_count[s] = 0; a.deep_count[s] = 0; a.run_end_count[s] = 0; }  // (run_end_count: an empty slice has no chunk that would write it)
 		if (threadIdx.x == 0) *a.gen = *a.gen % GEN_MAX + 1u;  // tag of this pass's match records (see MatchRec)
 	}
-	// run-list counters of dfl_run_len_kernel (a memset node of a few megabytes at the head of the graph waited for the copy
-	// engine: with the files of the pass before still on the wire a pass of 1024^2 slices started 3 ms late)
-	const size_t nrc = (size_t)n * 2 * (size_t)a.run_chunks;
-	for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < nrc; t += (size_t)gridDim.x * blockDim.x) a.run_counts[t] = 0;
+	// sort histograms and, right behind them (DeflateArgs), the run-list counters of dfl_run_len_kernel (a memset node of a few
+	// megabytes at the head of the graph waited for the copy engine: with the files of the pass before still on the wire a pass
+	// of 1024^2 slices started 3 ms late)
+	const size_t nrc = (size_t)n * (SORT_HIST + 2 * (size_t)a.run_chunks);
+	for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < nrc; t += (size_t)gridDim.x * blockDim.x) a.sort_hist[t] = 0;
+}
+
+// Zeroes of the output, by need: dfl_layout_kernel's trailer and dfl_emit_kernel OR their bits into zeros, and nothing before
+// the layout kernel reads `out`.  A file is at most 13 + zlib_bound(in_size, memLevel) bytes (api.cpp); the slack covers the
+// 32-bit words of or_bits / dfl_emit_kernel that straddle the end and the 16-byte units dfl_pack_kernel copies.  Beyond that the
+// stride keeps whatever the pass before left there: nobody reads it.  W: bytes per store, 16 when the stride allows it.
+constexpr uint32_t CLEAR_SLACK = 64;
+__device__ __forceinline__ size_t clear_bytes(const DeflateArgs &a, int s)
+{
+	const size_t L = a.in_sizes[s];
+	const size_t bound = a.block_syms == (uint32_t)BLOCK_SYMS ? L + (L >> 12) + (L >> 14) + (L >> 25) + 13  // compressBound
+	                                                          : L + ((L + 7) >> 3) + ((L + 63) >> 6) + 5 + 6;
+	return min(a.out_stride, (13 + bound + CLEAR_SLACK + 15) & ~(size_t)15);
+}
+template <typename W>
+__global__ void __launch_bounds__(256) dfl_clear_kernel(DeflateArgs a)
+{
+	const int s = blockIdx.y;
+	const size_t units = clear_bytes(a, s) / sizeof(W);  // (the stride is a multiple of sizeof(W): launch_clear)
+	W *out = reinterpret_cast<W *>(a.out + (size_t)s * a.out_stride);
+	W zero{};
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < units; i += (size_t)gridDim.x * blockDim.x) out[i] = zero;
+}
+static void launch_clear(const DeflateArgs &a, int n, hipStream_t st)
+{
+	if (a.out_stride % 16 == 0 && (uintptr_t)a.out % 16 == 0) hipLaunchKernelGGL(dfl_clear_kernel<uint4>, dim3(16, n), dim3(256), 0, st, a);
+	else hipLaunchKernelGGL(dfl_clear_kernel<uint32_t>, dim3(32, n), dim3(256), 0, st, a);
 }
 
 }  // namespace
@@ -2243,7 +2337,8 @@ size_t deflate_sort_temp_bytes(size_t total, int n)
 // with it -- but they no longer come after it), and the two tail-bound matchers (long chains: a few waves walking thousands
 // of entries; runs: a binary search + scan per position) run side by side, with the Adler-32 sums behind the shorter one --
 //     main:  run lengths, sort A, sort B ─┬─ match ─────┬─ run matcher ──────────┬─ decisions, walk, symbols, trees, emit
-//     side:                               └─ run lists ─┴─ heavy matcher, Adler ─┘
+//     side:                               └─ run lists, ─┴─ heavy matcher, Adler ─┘
+//                                            clear, blk_entry
 // Under stream capture this becomes the same fork / join in the graph.  Next to the SORT passes nothing may run: pass B took
 // 0.60 instead of 0.34 ms beside the run-list kernels (profiles/r03_deflate_fork.log).
 //
@@ -2256,6 +2351,7 @@ static hipError_t launch_deflate_short(const DeflateArgs &a, int n, hipStream_t 
 {
 	const bool ml9 = a.block_syms == (uint32_t)BLOCK_SYMS_ML9;
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
+	launch_clear(a, n, st);
 	if (a.strategy == Z_RLE) {
 		hipLaunchKernelGGL((dfl_run_len_kernel<false, 15>), dim3(gx, n), dim3(256), 0, st, a);  // run-length words
 		hipLaunchKernelGGL(dfl_rle_rec_kernel, dim3(gx, n), dim3(256), 0, st, a);
@@ -2269,7 +2365,7 @@ static hipError_t launch_deflate_short(const DeflateArgs &a, int n, hipStream_t 
 	}
 	hipLaunchKernelGGL(dfl_adler_kernel, dim3(n), dim3(256), 0, st, a);
 	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
-	hipLaunchKernelGGL(dfl_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a, n);
+	hipLaunchKernelGGL(dfl_layout_kernel, dim3(n), dim3(64), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_emit_kernel, dim3(a.max_blocks, n), dim3(256), 0, st, a);
 	return hipGetLastError();
 }
@@ -2281,10 +2377,9 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 	const bool ml9 = a.hash_bits == 16;
 	if ((a.hash_bits != 15 && !ml9) || a.block_syms != (uint32_t)(ml9 ? BLOCK_SYMS_ML9 : BLOCK_SYMS)) return hipErrorInvalidValue;
 	if (ml9 && a.pos_mask != 0xFFFFFFFFu) return hipErrorInvalidValue;  // memLevel 9: wide records only ("Sort records")
-	if ((e = hipMemsetAsync(a.out, 0, (size_t)n * a.out_stride, st)) != hipSuccess) return e;
+	if ((a.out_stride & 3) || ((uintptr_t)a.out & 3)) return hipErrorInvalidValue;
 	if (short_pass(a.strategy)) return launch_deflate_short(a, n, st);
-	if ((e = hipMemsetAsync(a.sort_hist, 0, (size_t)n * SORT_HIST * 4, st)) != hipSuccess) return e;
-	hipLaunchKernelGGL(dfl_offsets_kernel, dim3(64), dim3(256), 0, st, a, n);  // (also zeroes run_counts)
+	hipLaunchKernelGGL(dfl_offsets_kernel, dim3(64), dim3(256), 0, st, a, n);  // (also zeroes sort_hist and run_counts)
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
 	(void)sort_temp; (void)sort_temp_bytes;
 	if (ml9) {
@@ -2304,6 +2399,10 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 	}
 	hipLaunchKernelGGL(dfl_run_lists_kernel, dim3(a.run_chunks, n), dim3(256), 0, s2, a);
 	hipLaunchKernelGGL(dfl_run_info_kernel, dim3(8, n), dim3(256), 0, s2, a);
+	// neither depends on anything before it: beside the match kernel, which is bound by its instructions, they are off the
+	// serial path (the clear takes 30 us here and 11 us alone; the pass is shorter this way)
+	launch_clear(a, n, s2);
+	hipLaunchKernelGGL(dfl_offsets2_kernel, dim3(256), dim3(256), 0, s2, a, n);
 	// wide records: one 256-lane block per 256 positions (more of them in flight hide the scattered accesses better than grid-stride
 	// loops); compact records: the kernel is bound by its instructions, and 256 blocks per slice with four turns each measured best
 	// (486 us against 499 / 510 with 128 / 512, profiles/r03_match_grid.log)
@@ -2332,18 +2431,19 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 		if ((e = hipStreamWaitEvent(st, ev[3], 0)) != hipSuccess) return e;
 	}
 	hipLaunchKernelGGL(dfl_rec_kernel, dim3(gx, n), dim3(256), 0, st, a);
-	hipLaunchKernelGGL(dfl_offsets2_kernel, dim3(256), dim3(256), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_walk_kernel, dim3(n), dim3(WALK_T), 0, st, a, n);
 	if (ml9) hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS_ML9>, dim3(gx, n), dim3(256), 0, st, a);
 	else hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS>, dim3(gx, n), dim3(256), 0, st, a);
 	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
-	hipLaunchKernelGGL(dfl_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a, n);
+	hipLaunchKernelGGL(dfl_layout_kernel, dim3(n), dim3(64), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_emit_kernel, dim3(a.max_blocks, n), dim3(256), 0, st, a);
 	return hipGetLastError();
 }
 
-// exact = 1: files touch each other (archive layout); bytes are moved one at a time since the
-// destinations are unaligned
+// exact = 1: files touch each other (archive layout), so a destination has any alignment.  The source is dword-aligned (the
+// stride is a multiple of 4): aligned destination dwords are composed from two source dwords, and only the bytes before the
+// first and after the last aligned dword of a file are stored one at a time.  A composed dword reads its second source dword
+// only when it takes bytes from it (head != 0), and then that dword starts inside the file: nothing beyond the stride is read.
 __global__ void __launch_bounds__(256) dfl_pack_exact_kernel(const uint8_t *src, size_t stride, const uint32_t *sizes,
                                                              const uint64_t *offsets, uint8_t *dst)
 {
@@ -2351,13 +2451,25 @@ __global__ void __launch_bounds__(256) dfl_pack_exact_kernel(const uint8_t *src,
 	const uint32_t nbytes = sizes[s];
 	const uint8_t *in = src + (size_t)s * stride;
 	uint8_t *out = dst + offsets[s];
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nbytes; i += gridDim.x * blockDim.x) out[i] = in[i];
+	const uint32_t head = min((uint32_t)(-(uintptr_t)out & 3u), nbytes);  // bytes before the first aligned destination dword
+	const uint32_t nd = (nbytes - head) >> 2;                            // aligned destination dwords
+	const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+	const uint32_t *in32 = reinterpret_cast<const uint32_t *>(in);
+	uint32_t *out32 = reinterpret_cast<uint32_t *>(out + head);
+	const uint32_t sh = 8u * head, up = head ? 1u : 0u;
+	for (uint32_t j = tid; j < nd; j += nth) {  // destination bytes head + 4j .. + 3 = source bytes of dwords j and j + 1
+		const uint64_t pair = ((uint64_t)in32[j + up] << 32) | in32[j];
+		out32[j] = (uint32_t)(pair >> sh);
+	}
+	const uint32_t tail0 = head + 4u * nd;
+	if (tid < head) out[tid] = in[tid];
+	if (tid < nbytes - tail0) out[tail0 + tid] = in[tail0 + tid];
 }
 
 hipError_t launch_pack(const uint8_t *src, size_t stride, const uint32_t *sizes, int n, uint64_t *offsets, uint8_t *dst,
                        int exact, hipStream_t st)
 {
-	hipLaunchKernelGGL(dfl_pack_offsets_kernel, dim3(1), dim3(64), 0, st, sizes, n, offsets, exact);
+	hipLaunchKernelGGL(dfl_pack_offsets_kernel, dim3(1), dim3(256), 0, st, sizes, n, offsets, exact);
 	if (exact) hipLaunchKernelGGL(dfl_pack_exact_kernel, dim3(32, n), dim3(256), 0, st, src, stride, sizes, offsets, dst);
 	else hipLaunchKernelGGL(dfl_pack_kernel, dim3(16, n), dim3(256), 0, st, src, stride, sizes, offsets, dst);
 	return hipGetLastError();
