@@ -359,16 +359,19 @@ def zlib_compress_batch(blobs, level=9, strategy=0, mem_level=8):
     return [out[i, : sizes[i]].tobytes() for i in range(n)]
 
 
-def _png_args(images, level, shift, shape):
-    """Validated (ptr, on_device, n, rows, cols, level, shift, keep) of png_encode_batch; raises before any device call."""
+def _png_level(level):
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
         raise TypeError(f"PNG compress_level must be an integer, got {level!r}")
-    level = int(level)
-    if level == -1:
-        level = 6
+    level = 6 if int(level) == -1 else int(level)
     if not 4 <= level <= 9:
         raise ValueError(f"PNG compress_level {level}: supported levels are -1 and 4 to 9 "
                          "(0 to 3 are deflate_stored / deflate_fast, not on the device)")
+    return level
+
+
+def _png_args(images, level, shift, shape):
+    """Validated (ptr, on_device, n, rows, cols, level, shift, keep) of png_encode_batch; raises before any device call."""
+    level = _png_level(level)
     if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)):
         raise TypeError(f"PNG sample shift must be an integer, got {shift!r}")
     shift = int(shift)
@@ -445,6 +448,113 @@ def decode_png_batch(files, config=None, level=9):
     d_img = DeviceBuffer(max(2 * len(files) * hdr.width * hdr.height, 2))
     n, w, h = decode_batch(files, config, out_dev=d_img)
     return png_encode_batch(d_img, level=level, shift=4, shape=(n, w, h))
+
+
+def _png_window(window):
+    """(lo, hi) of a window argument, 0 <= lo < hi <= 65535, or TypeError / ValueError"""
+    if isinstance(window, (str, bytes)) or not hasattr(window, "__len__") or len(window) != 2:
+        raise TypeError(f"PNG window must be a pair (lo, hi), got {window!r}")
+    for x in window:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"PNG window bounds must be integers, got {window!r}")
+    lo, hi = int(window[0]), int(window[1])
+    if not 0 <= lo < hi <= 65535:
+        raise ValueError(f"PNG window ({lo}, {hi}): 0 <= lo < hi <= 65535")
+    return lo, hi
+
+
+def _png8_args(images, window, level, shape, dtype):
+    """Validated (ptr, on_device, n, rows, cols, src_bits, lo, hi, level, keep) of png8_encode_batch; raises before any
+    device call."""
+    level = _png_level(level)
+    if isinstance(images, DeviceBuffer):
+        if shape is None or dtype is None:
+            raise ValueError("png8_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols) and "
+                             "dtype=np.uint8 or np.uint16")
+        try:
+            dt = np.dtype(dtype)
+        except TypeError:
+            raise TypeError(f"8-bit PNGs take uint8 or uint16 samples, got dtype {dtype!r}") from None
+        shape = tuple(int(x) for x in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise ValueError(f"PNG batch shape {shape}: (n, rows, cols) or (rows, cols)")
+        n, rows, cols = shape
+        ptr, on_device, keep = images.ptr, 1, images
+    else:
+        if dtype is not None or shape is not None:
+            raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
+        arr = np.asarray(images)
+        dt = arr.dtype
+        if arr.ndim == 2:
+            arr = arr[None]
+        if arr.ndim != 3:
+            raise ValueError(f"PNG batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
+        n, rows, cols = arr.shape
+    if dt == np.uint8:
+        if window is not None:
+            raise ValueError("uint8 samples are written as they are: window must be None")
+        src_bits, lo, hi = 8, 0, 255
+    elif dt == np.uint16:
+        if window is None:
+            raise ValueError("uint16 samples need window=(lo, hi): v <= lo is written as 0 and v >= hi as 255")
+        src_bits = 16
+        lo, hi = _png_window(window)
+    else:
+        raise TypeError(f"8-bit PNGs take uint8 or uint16 samples, got {dt}")
+    _check_png_shape(rows, cols)  # the 16-bit writer's limit: cct_png_bound, which sizes the output, has no figure beyond it
+    if isinstance(images, DeviceBuffer):
+        if n < 0 or n * rows * cols * (src_bits // 8) > images.nbytes:
+            raise ValueError(f"PNG batch shape {shape} of {dt} does not fit the {images.nbytes}-byte DeviceBuffer")
+    else:
+        arr = np.ascontiguousarray(arr)
+        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    return ptr, on_device, n, rows, cols, src_bits, lo, hi, level, keep
+
+
+def png8_encode_batch(images, window=None, level=6, shape=None, dtype=None):
+    """8-bit grayscale PNGs on the device: a uint8 array (window must be None) or a uint16 array with window=(lo, hi), of
+    shape (n, rows, cols) or (rows, cols), or a DeviceBuffer with shape= and dtype= (np.uint8 or np.uint16) given, -> a list
+    of n `bytes`.  A uint16 value v becomes the byte ((min(max(v, lo), hi) - lo) * 510 + (hi - lo)) // (2 * (hi - lo)):
+    round((v - lo) * 255 / (hi - lo)) with halves rounded up, 0 at and below lo, 255 at and above hi; the map runs in
+    integers inside the filter kernel.  File i is byte-identical to what Pillow writes for
+    Image.fromarray(bytes_i).save(f, "PNG", compress_level=level): level -1 (= 6) or 4 to 9.  Filters, zlib stream and chunks
+    as in png_encode_batch, and so is the largest shape (the C entry also takes shapes up to 2^30 - 512 filtered bytes of
+    rows * (1 + cols)); png_read_batch reads the files back.  Arguments are checked (TypeError / ValueError) before any
+    device call."""
+    ptr, on_device, n, rows, cols, src_bits, lo, hi, level, keep = _png8_args(images, window, level, shape, dtype)
+    if n == 0:
+        return []
+    L = _ffi.lib()
+    out_stride = L.cct_png_bound(rows, cols)
+    out = np.empty((n, out_stride), dtype=np.uint8)
+    sizes = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_png_encode8_batch(ptr, on_device, n, rows, cols, src_bits, lo, hi, level, out.ctypes.data, out_stride,
+                                       sizes.ctypes.data))
+    del keep
+    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+
+
+def decode_png8_batch(files, window, config=None, level=6):
+    """Window/level previews of .cct files: each slice is decoded into HBM and written there as an 8-bit PNG through
+    window=(lo, hi) (png8_encode_batch), without the rasters coming back to the host.  Returns a list of PNG `bytes`."""
+    lo, hi = _png_window(window)
+    level = _png_level(level)
+    if isinstance(files, (bytes, bytearray, memoryview, str)):
+        raise TypeError("decode_png8_batch takes a list of bytes objects, one per file")
+    files = list(files)
+    for f in files:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise TypeError(f"a .cct file is a bytes object, got {type(f).__name__}")
+    config = config or default_config()
+    if not files:
+        return []
+    hdr = _ffi.Header()
+    _ffi.check(_ffi.lib().cct_read_header(files[0], len(files[0]), magic_bytes(config), C.byref(hdr)))
+    d_img = DeviceBuffer(max(2 * len(files) * hdr.width * hdr.height, 2))
+    n, w, h = decode_batch(files, config, out_dev=d_img)
+    return png8_encode_batch(d_img, window=(lo, hi), level=level, shape=(n, w, h), dtype=np.uint16)
 
 
 def png_info(file):

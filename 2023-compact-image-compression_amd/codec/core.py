@@ -244,12 +244,20 @@ class Decoder:
         self.deflate_compression = bool(fb[12])
 
     def decode(self):
+        # config["decoder"]["preview_window"] = [lo, hi] (absent in the reference's config): checked before any device call
+        window = self.config.get("decoder", {}).get("preview_window")
+        if window is not None:
+            window = batch._png_window(window)
         self.read_header()
         self.size = self.width * self.height
         self.total_size = self.size * self.channels * self.bytes_per_channel
         pixels = batch.decode_batch([bytes(self.file_bytes)], self.config)[0]  # (width, height) uint16
         self._pixels = pixels
 
+        if self.out_path is not None and window is not None:  # extension: 8-bit window/level preview, written on the device
+            with open(self.out_path, "wb") as fout:
+                fout.write(batch.png8_encode_batch(pixels, window=window)[0])
+            return pixels
         if self.out_path is not None:  # core.py:522-540: 16-bit PNG preview, value << 4
             preview = (pixels.astype(np.uint32) << 4).astype(np.uint16)
             _write_png16(self.out_path, preview)

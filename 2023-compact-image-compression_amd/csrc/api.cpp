@@ -84,7 +84,7 @@ struct EncSlot {
 	// device DEFLATE workspaces
 	DevBuf z_vals_in, z_vals_out, z_mr, z_rec, z_exitp, z_exitc, z_sym, z_bentry, z_bsym,
 	    z_small, z_bend, z_meta, z_tables, z_sorttmp, z_out, z_outsizes, z_in, z_insizes, z_packed, z_packoffs, z_gen, z_runs;
-	DevBuf png_img, png_out, png_sizes;  // PNG writer: rasters from the host, files, their sizes (cct_png_encode_batch)
+	DevBuf png_img, png_out, png_sizes;  // PNG writer: rasters from the host, files, their sizes (cct_png_encode_batch, cct_png_encode8_batch)
 	// match records are valid by tag (deflate_kernels.hip MatchRec): the device counter z_gen has run z_gen_passes times since
 	// the buffer z_mr_cleared (z_mr at that time) was last zeroed together with it
 	const void *z_mr_cleared = nullptr;
@@ -1659,18 +1659,35 @@ int cct_zlib_compress_batch_params(const uint8_t *h_in, const uint64_t *h_offset
 // bufsize of ImageFile._save, max(65536, 4 * cols) bytes.  One DEFLATE pass takes at most DEFLATE_PASS_BYTES of filtered rows.
 constexpr int PNG_MEM_LEVEL = 9;
 constexpr size_t PNG_MAX_FILTERED = DEFLATE_PASS_BYTES - 512;
-static size_t png_filtered_bytes(int rows, int cols) { return (size_t)rows * (1 + 2 * (size_t)cols); }
+// bps: bytes per sample, 2 in the 16-bit files and 1 in the 8-bit ones
+static size_t png_filtered_bytes(int rows, int cols, int bps = 2) { return (size_t)rows * (1 + (size_t)bps * (size_t)cols); }
 static size_t png_in_stride(size_t filtered) { return (filtered + 16 + 255) & ~(size_t)255; }
 static size_t png_zstride(size_t in_stride) { return (13 + zlib_bound(in_stride, PNG_MEM_LEVEL) + 63) & ~(size_t)63; }
 static uint32_t png_chunk(int cols) { return (uint32_t)std::max<size_t>(65536, 4 * (size_t)cols); }
 // signature + IHDR (33), the stream, 12 bytes per IDAT chunk, IEND (12)
 static size_t png_file_bytes(size_t zlen, uint32_t chunk) { return 33 + zlen + 12 * ((zlen + chunk - 1) / chunk) + 12; }
 
+// every term grows with the filtered bytes, so the bound of the 16-bit file covers the 8-bit file of the same shape
+static size_t png_bound_of(size_t filtered, int cols)
+{
+	return (png_file_bytes(png_zstride(png_in_stride(filtered)) - 13, png_chunk(cols)) + 63) & ~(size_t)63;
+}
+
 size_t cct_png_bound(int rows, int cols)
 {
 	if (rows < 1 || cols < 1 || png_filtered_bytes(rows, cols) > PNG_MAX_FILTERED) return 0;
-	return (png_file_bytes(png_zstride(png_in_stride(png_filtered_bytes(rows, cols))) - 13, png_chunk(cols)) + 63) & ~(size_t)63;
+	return png_bound_of(png_filtered_bytes(rows, cols), cols);
 }
+
+// What the two writers differ in: the file's bit depth, the source rasters' bytes per pixel and the arguments of the filter kernel.
+struct PngFormat {
+	int depth;            // 16: png_filter_kernel with `shift`; 8: png_filter8_kernel with src_bits and the window
+	int shift;
+	int src_bits, lo, hi;
+};
+
+static int png_encode_impl(const void *images, int images_on_device, int n, int rows, int cols, const PngFormat &fmt, int level,
+                           uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 
 int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, int rows, int cols, int shift, int level,
                          uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
@@ -1687,14 +1704,44 @@ int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, in
 	if (!images && n > 0) return fail(CCT_E_ARG, "images is required");
 	const size_t bound = cct_png_bound(rows, cols);
 	if (out_stride < bound) return fail(CCT_E_CAP, "out_stride %zu too small (need cct_png_bound = %zu)", out_stride, bound);
+	const PngFormat fmt{16, shift, 16, 0, 0};
+	return png_encode_impl(images, images_on_device, n, rows, cols, fmt, level, h_out, out_stride, h_out_sizes);
+}
+
+int cct_png_encode8_batch(const void *images, int images_on_device, int n, int rows, int cols, int src_bits, int lo, int hi,
+                          int level, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
+{
+	if (level == -1) level = 6;
+	if (level >= 0 && level <= 3) return fail(CCT_E_ARG, "PNG compress_level %d: deflate_stored / deflate_fast: not on the device", level);
+	if (level < 4 || level > 9) return fail(CCT_E_ARG, "PNG compress_level %d: levels are -1 and 4 .. 9", level);
+	if (src_bits != 8 && src_bits != 16) return fail(CCT_E_ARG, "PNG source of %d bits: 8 or 16", src_bits);
+	if (lo < 0 || hi > 65535 || lo >= hi) return fail(CCT_E_ARG, "PNG window (%d, %d): 0 <= lo < hi <= 65535", lo, hi);
+	if (src_bits == 8 && (lo != 0 || hi != 255)) return fail(CCT_E_ARG, "PNG window (%d, %d) of an 8-bit source: (0, 255)", lo, hi);
+	if (rows < 1 || cols < 1) return fail(CCT_E_ARG, "PNG shape %d x %d: rows and cols must be >= 1", rows, cols);
+	if (png_filtered_bytes(rows, cols, 1) > PNG_MAX_FILTERED)
+		return fail(CCT_E_ARG, "PNG shape %d x %d: %zu filtered bytes exceed one DEFLATE pass (%zu)", rows, cols,
+		            png_filtered_bytes(rows, cols, 1), PNG_MAX_FILTERED);
+	if (n < 0) return fail(CCT_E_ARG, "negative batch size");
+	if (!images && n > 0) return fail(CCT_E_ARG, "images is required");
+	// a shape only the 8-bit file fits in one pass has no cct_png_bound: its own bound then
+	const size_t bound16 = cct_png_bound(rows, cols), bound = bound16 ? bound16 : png_bound_of(png_filtered_bytes(rows, cols, 1), cols);
+	if (out_stride < bound)
+		return fail(CCT_E_CAP, "out_stride %zu too small (need %s = %zu)", out_stride, bound16 ? "cct_png_bound" : "the 8-bit bound", bound);
+	const PngFormat fmt{8, 0, src_bits, lo, hi};
+	return png_encode_impl(images, images_on_device, n, rows, cols, fmt, level, h_out, out_stride, h_out_sizes);
+}
+
+static int png_encode_impl(const void *images, int images_on_device, int n, int rows, int cols, const PngFormat &fmt, int level,
+                           uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
+{
 	std::lock_guard<std::mutex> lk(g_mu);
 	ApiCall in_call;
 	int rc = ensure_ctx();
 	if (rc) return rc;
 	if (n == 0) return CCT_OK;
 	EncSlot &E = g_enc[0];
-	const size_t F = png_filtered_bytes(rows, cols), in_stride = png_in_stride(F), zstride = png_zstride(in_stride);
-	const size_t img_bytes = (size_t)rows * cols * 2;
+	const size_t F = png_filtered_bytes(rows, cols, fmt.depth / 8), in_stride = png_in_stride(F), zstride = png_zstride(in_stride);
+	const size_t img_bytes = (size_t)rows * cols * (size_t)(fmt.src_bits / 8);
 	const uint32_t chunk = png_chunk(cols);
 	const size_t pstride = png_file_bytes(zstride - 13, chunk);
 	const uint32_t max_chunks = (uint32_t)((zstride - 13 + chunk - 1) / chunk);
@@ -1702,13 +1749,13 @@ int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, in
 	const bool host_img = !images_on_device;
 	PngPackArgs pk{};
 	pk.chunk = chunk;
-	{  // IHDR: width, height, depth 16, color type 0 (grayscale), compression 0, filter 0, interlace 0
+	{  // IHDR: width, height, depth, color type 0 (grayscale), compression 0, filter 0, interlace 0
 		uint8_t *h = pk.ihdr;
 		const uint8_t fixed[8] = {0, 0, 0, 13, 'I', 'H', 'D', 'R'};
 		memcpy(h, fixed, 8);
 		const uint32_t w = (uint32_t)cols, ht = (uint32_t)rows;
 		const uint8_t data[13] = {(uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w,
-		                          (uint8_t)(ht >> 24), (uint8_t)(ht >> 16), (uint8_t)(ht >> 8), (uint8_t)ht, 16, 0, 0, 0, 0};
+		                          (uint8_t)(ht >> 24), (uint8_t)(ht >> 16), (uint8_t)(ht >> 8), (uint8_t)ht, (uint8_t)fmt.depth, 0, 0, 0, 0};
 		memcpy(h + 8, data, 13);
 		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), h + 4, 17);
 		h[21] = (uint8_t)(crc >> 24); h[22] = (uint8_t)(crc >> 16); h[23] = (uint8_t)(crc >> 8); h[24] = (uint8_t)crc;
@@ -1722,15 +1769,18 @@ int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, in
 		if ((rc = E.z_insizes.ensure((size_t)nc * 4))) return rc;
 		if ((rc = E.png_out.ensure((size_t)nc * pstride))) return rc;
 		if ((rc = E.png_sizes.ensure((size_t)nc * 4))) return rc;
-		const uint16_t *d_img = images + (size_t)c0 * rows * cols;
+		const void *d_img = (const uint8_t *)images + (size_t)c0 * img_bytes;
 		if (host_img) {
 			if ((rc = E.png_img.ensure((size_t)nc * img_bytes))) return rc;
 			HIP_TRY(hipMemcpyAsync(E.png_img.p, d_img, (size_t)nc * img_bytes, hipMemcpyHostToDevice, E.stream));
-			d_img = (const uint16_t *)E.png_img.p;
+			d_img = E.png_img.p;
 		}
 		sizes.assign((size_t)nc, (uint32_t)F);
 		HIP_TRY(hipMemcpyAsync(E.z_insizes.p, sizes.data(), (size_t)nc * 4, hipMemcpyHostToDevice, E.stream));
-		HIP_TRY(launch_png_filter(d_img, nc, rows, cols, shift, (uint8_t *)E.z_in.p, in_stride, E.stream));
+		if (fmt.depth == 16)
+			HIP_TRY(launch_png_filter((const uint16_t *)d_img, nc, rows, cols, fmt.shift, (uint8_t *)E.z_in.p, in_stride, E.stream));
+		else
+			HIP_TRY(launch_png_filter8(d_img, fmt.src_bits, nc, rows, cols, fmt.lo, fmt.hi, (uint8_t *)E.z_in.p, in_stride, E.stream));
 		if (g_ctx.device_deflate) {
 			const uint8_t hdr13[13] = {0};
 			rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, nc, hdr13, zstride, level,

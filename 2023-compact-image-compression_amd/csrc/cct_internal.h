@@ -203,6 +203,10 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 // n rasters (rows x cols uint16, C order) -> filter byte + filtered big-endian row, rows * (1 + 2 cols) bytes at d_out + i*out_stride
 hipError_t launch_png_filter(const uint16_t *d_img, int n, int rows, int cols, int shift, uint8_t *d_out, size_t out_stride,
                              hipStream_t st);
+// 8-bit samples: n rasters (rows x cols, uint16 mapped through the window [lo, hi] to 0 .. 255 when src_bits is 16, uint8 with
+// the window (0, 255) when it is 8) -> filter byte + filtered row, rows * (1 + cols) bytes at d_out + i*out_stride
+hipError_t launch_png_filter8(const void *d_img, int src_bits, int n, int rows, int cols, int lo, int hi, uint8_t *d_out,
+                              size_t out_stride, hipStream_t st);
 struct PngPackArgs {
 	const uint8_t *src; size_t src_stride; uint32_t src_skip;  // zlib stream i = src + i*src_stride + src_skip ..
 	const uint32_t *src_sizes;                                 // .. of src_sizes[i] - src_skip bytes (device)

@@ -5,7 +5,8 @@
 //            zeros.  Pillow's choice: the cost of a filtered row is the sum of min(v, 256 - v) over its bytes (the filter
 //            byte not counted); None first, then Up, Sub and Paeth, each tried only while the best cost is > 0 and taken
 //            only when strictly cheaper (Average needs optimize=True, which is not offered).  Filter byte + filtered row
-//            land in the DEFLATE pass's input.
+//            land in the DEFLATE pass's input.  png_filter8_kernel: the same for the 8-bit files of cct_png_encode8_batch
+//            (bpp = 1), whose samples are uint8 rasters or uint16 rasters mapped through a window on load.
 //   deflate  the device DEFLATE at memLevel 9 / Z_FILTERED (deflate_kernels.hip), or host libz
 //   pack     png_pack_kernel: signature, IHDR, the zlib stream cut into IDAT chunks of max(65536, 4*cols) bytes (the
 //            bufsize of Pillow's ImageFile._save; the last one shorter) and IEND, every chunk with its CRC-32
@@ -91,6 +92,106 @@ __global__ void __launch_bounds__(256) png_filter_kernel(const uint16_t *img, in
 	}
 }
 
+// The 8-bit writer's filter (cct_png_encode8_batch): the samples are bytes, so bpp = 1 and the left neighbour is the previous
+// pixel.  A uint16 raster is mapped to bytes through the window as it is loaded (no 8-bit raster exists in memory); a uint8
+// raster takes the same path with the window (0, 255), which is the identity.  Pillow's costs, order and rule are those of
+// png_filter_kernel above.
+// The map y = ((clamp(v, lo, hi) - lo) * 510 + w) / (2 w), w = hi - lo, in integers: the numerator is below 2^25 (511 w,
+// w < 2^16), and for 0 <= n < 2^25 and a divisor d with l = ceil(log2 d), floor(n / d) = (n * ceil(2^(25 + l) / d)) >> (25 + l)
+// exactly (Granlund and Montgomery 1994, theorem 4.2); the multiplier is below 2^27, so the product fits 64 bits.
+// launch_png_filter8 computes multiplier and shift on the host.
+struct PngWindow {
+	uint32_t lo, hi, w, mul, shift;
+};
+
+constexpr int FILTER8_PX = 8;  // pixels per lane per step: one 16-byte load of uint16 samples, one 8-byte store of filtered bytes
+
+// One wave per row as above; lane l takes pixels [8 (l + 64 i), 8 (l + 64 i) + 8) in step i.  The group of a lane starts at any
+// address (a row starts at r * cols samples and its output at r * (1 + cols) + 1 bytes): whole groups are moved with
+// __builtin_memcpy, which gfx950 turns into one load or store at any alignment (deflate_kernels.hip compares matches the same
+// way); the last, partial group of a row goes pixel by pixel.  Nothing outside [0, cols) of the two rows is read.  A pixel
+// costs at most 128, so a lane's sums stay below 2^32 for any row the DEFLATE pass takes; the wave adds them in 64 bits.
+template <class T>
+__global__ void __launch_bounds__(256) png_filter8_kernel(const T *img, int rows, int cols, PngWindow win, uint8_t *out,
+                                                          size_t out_stride)
+{
+	const int s = blockIdx.y, r = (int)blockIdx.x * FILTER_ROWS + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+	if (r >= rows) return;
+	const T *cur = img + ((size_t)s * rows + r) * (size_t)cols;
+	const bool has_up = r > 0;
+	const T *up = has_up ? cur - cols : cur;
+	uint8_t *o = out + (size_t)s * out_stride + (size_t)r * (1 + (size_t)cols);
+	auto smp = [&](uint32_t v) {
+		const uint32_t c = min(max(v, win.lo), win.hi);
+		return (uint32_t)(((uint64_t)((c - win.lo) * 510u + win.w) * win.mul) >> win.shift);
+	};
+	// y[0] = sample c0 - 1 of `row` (0 in front of the row), y[1 + i] = sample c0 + i for i < nv
+	auto load = [&](const T *row, int c0, int nv, uint32_t (&y)[1 + FILTER8_PX]) {
+		constexpr int PER_WORD = 4 / (int)sizeof(T);  // samples in a 32-bit word, the lowest address in the low bits
+		uint32_t raw[FILTER8_PX];
+		if (nv == FILTER8_PX) {
+			uint32_t words[FILTER8_PX / PER_WORD];
+			__builtin_memcpy(words, row + c0, sizeof(words));
+#pragma unroll
+			for (int i = 0; i < FILTER8_PX; i++) raw[i] = (words[i / PER_WORD] >> (8 * (int)sizeof(T) * (i % PER_WORD))) & (T)~(T)0;
+		} else {
+#pragma unroll
+			for (int i = 0; i < FILTER8_PX; i++) raw[i] = i < nv ? (uint32_t)row[c0 + i] : 0u;
+		}
+		y[0] = c0 ? smp(row[c0 - 1]) : 0u;
+#pragma unroll
+		for (int i = 0; i < FILTER8_PX; i++) y[1 + i] = smp(raw[i]);
+	};
+	auto load_both = [&](int c0, int nv, uint32_t (&x)[1 + FILTER8_PX], uint32_t (&b)[1 + FILTER8_PX]) {
+		load(cur, c0, nv, x);
+		if (has_up) {
+			load(up, c0, nv, b);
+		} else {
+#pragma unroll
+			for (int i = 0; i <= FILTER8_PX; i++) b[i] = 0u;
+		}
+	};
+	uint32_t c_none = 0, c_sub = 0, c_up = 0, c_paeth = 0;
+	for (int c0 = lane * FILTER8_PX; c0 < cols; c0 += 64 * FILTER8_PX) {
+		const int nv = min(FILTER8_PX, cols - c0);
+		uint32_t x[1 + FILTER8_PX], b[1 + FILTER8_PX];
+		load_both(c0, nv, x, b);
+#pragma unroll
+		for (int i = 0; i < FILTER8_PX; i++) {
+			if (i < nv) {
+				c_none += png_cost(x[1 + i]);
+				c_sub += png_cost(x[1 + i] - x[i]);
+				c_up += png_cost(x[1 + i] - b[1 + i]);
+				c_paeth += png_cost(x[1 + i] - paeth(x[i], b[1 + i], b[i]));
+			}
+		}
+	}
+	const uint64_t s_none = wave_sum_u64(c_none), s_sub = wave_sum_u64(c_sub), s_up = wave_sum_u64(c_up), s_paeth = wave_sum_u64(c_paeth);
+	uint64_t best = s_none;
+	int f = 0;
+	if (best > 0 && s_up < best) { best = s_up; f = 2; }
+	if (best > 0 && s_sub < best) { best = s_sub; f = 1; }
+	if (best > 0 && s_paeth < best) { best = s_paeth; f = 4; }
+	if (lane == 0) o[0] = (uint8_t)f;
+	for (int c0 = lane * FILTER8_PX; c0 < cols; c0 += 64 * FILTER8_PX) {
+		const int nv = min(FILTER8_PX, cols - c0);
+		uint32_t x[1 + FILTER8_PX], b[1 + FILTER8_PX];
+		load_both(c0, nv, x, b);
+		uint32_t q[FILTER8_PX];
+#pragma unroll
+		for (int i = 0; i < FILTER8_PX; i++) q[i] = png_filter_byte(f, x[1 + i], x[i], b[1 + i], b[i]);
+		uint8_t *dst = o + 1 + (size_t)c0;
+		if (nv == FILTER8_PX) {
+			const uint32_t words[2] = {q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24), q[4] | (q[5] << 8) | (q[6] << 16) | (q[7] << 24)};
+			__builtin_memcpy(dst, words, sizeof(words));
+		} else {
+#pragma unroll
+			for (int i = 0; i < FILTER8_PX; i++)
+				if (i < nv) dst[i] = (uint8_t)q[i];
+		}
+	}
+}
+
 __constant__ uint8_t c_png_sig[8] = {0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A};
 __constant__ uint8_t c_png_iend[12] = {0, 0, 0, 0, 0x49, 0x45, 0x4E, 0x44, 0xAE, 0x42, 0x60, 0x82};
 __constant__ uint8_t c_idat[4] = {0x49, 0x44, 0x41, 0x54};
@@ -165,6 +266,25 @@ hipError_t launch_png_filter(const uint16_t *d_img, int n, int rows, int cols, i
 	if (n <= 0) return hipSuccess;
 	hipLaunchKernelGGL(png_filter_kernel, dim3((rows + FILTER_ROWS - 1) / FILTER_ROWS, n), dim3(64 * FILTER_ROWS), 0, st, d_img,
 	                   rows, cols, shift, d_out, out_stride);
+	return hipGetLastError();
+}
+
+hipError_t launch_png_filter8(const void *d_img, int src_bits, int n, int rows, int cols, int lo, int hi, uint8_t *d_out,
+                              size_t out_stride, hipStream_t st)
+{
+	if (n <= 0) return hipSuccess;
+	PngWindow win{};
+	win.lo = (uint32_t)lo; win.hi = (uint32_t)hi; win.w = win.hi - win.lo;
+	const uint32_t d = 2u * win.w;
+	uint32_t l = 1;
+	while ((1u << l) < d) l++;
+	win.shift = 25u + l;
+	win.mul = (uint32_t)((((uint64_t)1 << win.shift) + d - 1) / d);
+	const dim3 grid((rows + FILTER_ROWS - 1) / FILTER_ROWS, n), block(64 * FILTER_ROWS);
+	if (src_bits == 16)
+		hipLaunchKernelGGL(png_filter8_kernel<uint16_t>, grid, block, 0, st, (const uint16_t *)d_img, rows, cols, win, d_out, out_stride);
+	else
+		hipLaunchKernelGGL(png_filter8_kernel<uint8_t>, grid, block, 0, st, (const uint8_t *)d_img, rows, cols, win, d_out, out_stride);
 	return hipGetLastError();
 }
 

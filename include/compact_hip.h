@@ -225,6 +225,26 @@ size_t cct_png_bound(int rows, int cols);
 int cct_png_encode_batch(const uint16_t *images, int images_on_device, int n, int rows, int cols, int shift, int level,
                          uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 
+/* The 8-bit writer: grayscale files of bit depth 8, the second kind cct_png_read_batch reads, and the window/level previews
+ * of CT slices.  n rasters of shape (rows, cols), C order, on the host or the device, of uint16 (src_bits 16) or uint8
+ * (src_bits 8) samples.  A uint16 value v goes through the window 0 <= lo < hi <= 65535 to a byte, in integers only:
+ *     w = hi - lo;  c = min(max(v, lo), hi);  y = ((c - lo) * 510 + w) / (2 * w)
+ * which is round((c - lo) * 255 / w) with halves rounded up: v <= lo gives 0, v >= hi gives 255.  uint8 samples are written
+ * as they are; their window must be (0, 255), the identity.  File i is byte-identical to Pillow's
+ * Image.fromarray(y.astype(uint8)).save(f, "PNG", compress_level=level) and lands at h_out + i*out_stride, its size in
+ * h_out_sizes[i].  The map is applied as the filter kernel loads a row (no 8-bit raster is written to device memory); filter
+ * choice, zlib stream (level -1 = 6, or 4 .. 9; host libz with device_deflate 0), IDAT chunk size and packing are those of
+ * cct_png_encode_batch, and the call takes the encode slot like it.  CCT_E_ARG before the device is touched: levels 0 .. 3 and
+ * outside -1 .. 9, src_bits not 8 or 16, lo < 0, hi > 65535, lo >= hi, src_bits 8 with another window than (0, 255), rows
+ * or cols < 1, n < 0, more than 2^30 - 512 filtered bytes (rows * (1 + cols)).  out_stride >= cct_png_bound(rows, cols)
+ * (CCT_E_CAP otherwise): the bound of the 16-bit file is sufficient for the 8-bit file of the same shape, whose rows, zlib
+ * stream and chunk count are never larger.  A shape that only the 8-bit file fits (cct_png_bound returns 0 while
+ * rows * (1 + cols) is within the limit) needs the same expression on its own filtered bytes; the CCT_E_CAP message names
+ * the figure. */
+int cct_png_encode8_batch(const void *images, int images_on_device, int n, int rows, int cols,
+                          int src_bits /* 8 or 16 */, int lo, int hi, int level,
+                          uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+
 /* ---- PNG reader ------------------------------------------------------------------------ */
 /* The inverse of the writer and of the reference's png_to_array (lib/png.py:33-38, value >> 4): grayscale PNG files of bit
  * depth 8 or 16 -> uint16 rasters, pixel = sample >> shift (8-bit samples widened first; 16-bit samples are big-endian in

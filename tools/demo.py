@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Round-trip demo: the counterpart of the reference's scripts/demo.py:38-106 without pydicom.
 
-    python tools/demo.py INPUT [--workdir DIR] [--shape W,H]
+    python tools/demo.py INPUT [--workdir DIR] [--shape W,H] [--window LO HI]
 
 Encodes one slice to `<workdir>/testing.<extension>` through codec.core.Encoder, reads the file back, decodes it
 through codec.core.Decoder into the preview file get_filename() names (scripts/demo.py:16-25: "decoded-<name>.<format>"),
 and prints what the reference prints: process times, error count, MSE, RMSE and the two SHA-1 digests.  Exit code 1
-if the reconstruction is not exact.
+if the reconstruction is not exact.  --window LO HI writes the preview as an 8-bit window/level PNG
+(config["decoder"]["preview_window"]) in place of the reference's 16-bit value << 4 file.
 """
 import argparse
 import hashlib
@@ -45,10 +46,14 @@ def main(argv=None):
     ap.add_argument("input")
     ap.add_argument("--workdir", default=os.path.join(ROOT, "gpurun_out", "demo"))
     ap.add_argument("--shape", default=None, help="W,H for raw inputs that are not square")
+    ap.add_argument("--window", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="8-bit preview: values <= LO black, >= HI white")
     args = ap.parse_args(argv)
     from codec.core import Decoder, Encoder
     with open(os.path.join(ROOT, "2023-compact-image-compression_amd", "config.json")) as f:
         config = json.load(f)
+    if args.window is not None:
+        config["decoder"]["preview_window"] = list(args.window)
     shape = tuple(int(x) for x in args.shape.split(",")) if args.shape else None
     image = load_slice(args.input, shape)
     os.makedirs(args.workdir, exist_ok=True)
