@@ -3,4 +3,5 @@ from . import _ffi  # noqa: F401
 from .batch import (DeviceBuffer, Event, PinnedArray, codec_params, decode_batch, decode_payload_dev,  # noqa: F401
                     zlib_compress_batch, zlib_decompress_batch, png_encode_batch, decode_png_batch, png_info, png_read_batch,
                     png8_encode_batch, decode_png8_batch,
+                    dicom_rle_encode_batch, dicom_rle_decode_batch, dicom_encapsulate, dicom_fragments,
                     default_config, device_info, encode_batch, encode_payload_dev)

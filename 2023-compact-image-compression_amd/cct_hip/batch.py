@@ -635,3 +635,166 @@ def zlib_decompress_batch(streams, max_out, raise_errors=True):
         _ffi.check(rc)
     outs = [out[i, : sizes[i]].tobytes() if status[i] == 0 else None for i in range(n)]
     return outs if raise_errors else (outs, status)
+
+
+# ---- DICOM RLE Lossless (PS3.5 Annex G): frames on the device, encapsulation on the host ----------------------------
+
+_DICOM_ITEM = b"\xfe\xff\x00\xe0"
+_DICOM_SEQ_DELIM = b"\xfe\xff\xdd\xe0\x00\x00\x00\x00"
+_RLE_MAX_PIXELS = 1 << 26
+
+
+def _check_rle_shape(rows, cols):
+    if rows < 1 or cols < 1:
+        raise ValueError(f"DICOM RLE frame of {rows} x {cols} samples: rows and cols must be >= 1")
+    if rows * cols > _RLE_MAX_PIXELS:
+        raise ValueError(f"DICOM RLE frame of {rows} x {cols} samples: more than {_RLE_MAX_PIXELS} pixels")
+
+
+def dicom_rle_encode_batch(images, shape=None, dtype=None):
+    """DICOM RLE Lossless frames (transfer syntax 1.2.840.10008.1.2.5) on the device: a uint16 or uint8 array of shape
+    (n, rows, cols) or (rows, cols), or a DeviceBuffer with shape= given (dtype= np.uint16 unless np.uint8 is named), -> a
+    list of n `bytes`.  Frame i is the 64-byte header and one PackBits segment per byte plane (high byte first), rows coded
+    one by one with the rule of pydicom's pure-Python encoder; tests/dicom_rle_model.py states it.  dicom_encapsulate wraps
+    frames as PixelData.  Arguments are checked (TypeError / ValueError) before any device call."""
+    if isinstance(images, DeviceBuffer):
+        if shape is None:
+            raise ValueError("dicom_rle_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)")
+        dt = np.dtype(np.uint16 if dtype is None else dtype)
+        shape = tuple(int(x) for x in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise ValueError(f"frame batch shape {shape}: (n, rows, cols) or (rows, cols)")
+        n, rows, cols = shape
+        ptr, on_device, keep = images.ptr, 1, images
+    else:
+        if shape is not None or dtype is not None:
+            raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
+        arr = np.asarray(images)
+        dt = arr.dtype
+        if arr.ndim == 2:
+            arr = arr[None]
+        if arr.ndim != 3:
+            raise ValueError(f"frame batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
+        n, rows, cols = arr.shape
+    if dt != np.uint8 and dt != np.uint16:
+        raise TypeError(f"DICOM RLE frames take uint8 or uint16 samples, got {dt}")
+    if n == 0:
+        return []
+    _check_rle_shape(rows, cols)
+    bits = 8 * dt.itemsize
+    if isinstance(images, DeviceBuffer):
+        if n < 0 or n * rows * cols * dt.itemsize > images.nbytes:
+            raise ValueError(f"frame batch shape {shape} of {dt} does not fit the {images.nbytes}-byte DeviceBuffer")
+    else:
+        arr = np.ascontiguousarray(arr)
+        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    L = _ffi.lib()
+    out_stride = L.cct_dicom_rle_bound(rows, cols, bits)
+    out = np.empty((n, out_stride), dtype=np.uint8)
+    sizes = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_dicom_rle_encode_batch(ptr, on_device, n, rows, cols, bits, out.ctypes.data, out_stride, sizes.ctypes.data))
+    del keep
+    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+
+
+def dicom_rle_decode_batch(frames, rows, cols, bits=16, out_dev=None, raise_errors=True):
+    """DICOM RLE Lossless frames (a list of `bytes`, one sample per pixel, `bits` = 8 or 16 allocated) -> an (n, rows, cols)
+    uint8 / uint16 array, decoded on the device; frames of any conforming encoder are read (packets may cross row ends).
+    With out_dev it fills that DeviceBuffer and returns the shape, like decode_batch.  With raise_errors=False it returns
+    (array or shape, status) with status[i] 0 or CCT_E_STREAM (a frame shorter than its header, a segment count other than
+    bits / 8, offsets that do not start at 64, do not increase or leave the frame, a segment that yields fewer than
+    rows * cols bytes); the raster of a refused frame is unspecified.  Arguments are checked before any device call."""
+    for name, x in (("rows", rows), ("cols", cols), ("bits", bits)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {x!r}")
+    rows, cols, bits = int(rows), int(cols), int(bits)
+    if bits not in (8, 16):
+        raise ValueError(f"DICOM RLE frames of {bits} bits allocated: 8 or 16")
+    _check_rle_shape(rows, cols)
+    if isinstance(frames, (bytes, bytearray, memoryview, str)):
+        raise TypeError("dicom_rle_decode_batch takes a list of bytes objects, one per frame")
+    frames = list(frames)
+    for f in frames:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise TypeError(f"a frame is a bytes object, got {type(f).__name__}")
+    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
+        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+    n, dt = len(frames), np.dtype(np.uint8 if bits == 8 else np.uint16)
+    if n == 0:
+        res = (0, rows, cols) if out_dev is not None else np.zeros((0, rows, cols), dtype=dt)
+        return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
+    if out_dev is not None and n * rows * cols * dt.itemsize > out_dev.nbytes:
+        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
+    L = _ffi.lib()
+    blob = b"".join(bytes(f) for f in frames) or b"\0"
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(f) for f in frames], out=offs[1:])
+    status = np.zeros(n, dtype=np.uint32)
+    if out_dev is not None:
+        rc = L.cct_dicom_rle_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, out_dev.ptr, 1,
+                                          out_dev.nbytes // dt.itemsize, status.ctypes.data)
+        res = (n, rows, cols)
+    else:
+        res = np.empty((n, rows, cols), dtype=dt)
+        rc = L.cct_dicom_rle_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, res.ctypes.data, 0, res.size,
+                                          status.ctypes.data)
+    if raise_errors or rc != _ffi.E_STREAM:
+        _ffi.check(rc)
+    return res if raise_errors else (res, status)
+
+
+def dicom_encapsulate(frames):
+    """Encapsulated PixelData of a list of frames (PS3.5 A.4): the Basic Offset Table item with one uint32 offset per frame,
+    one item per frame (each frame in exactly one fragment, padded to even length), the sequence delimiter.  Host only."""
+    if isinstance(frames, (bytes, bytearray, memoryview, str)):
+        raise TypeError("dicom_encapsulate takes a list of bytes objects, one per frame")
+    items, offsets = bytearray(), []
+    for f in frames:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise TypeError(f"a frame is a bytes object, got {type(f).__name__}")
+        f = bytes(f)
+        if len(f) & 1:
+            f += b"\0"
+        offsets.append(len(items))
+        items += _DICOM_ITEM + len(f).to_bytes(4, "little") + f
+    bot = b"".join(o.to_bytes(4, "little") for o in offsets)
+    return _DICOM_ITEM + len(bot).to_bytes(4, "little") + bot + bytes(items) + _DICOM_SEQ_DELIM
+
+
+def dicom_fragments(pixel_data):
+    """The frames of encapsulated PixelData (one fragment per frame; a fragment keeps its pad byte, which the RLE decoder
+    ignores).  ValueError on a malformed item structure: an unknown tag, an item running past the data, no sequence
+    delimiter or bytes behind it, no Basic Offset Table item, a table that does not list the fragments.  Host only."""
+    if not isinstance(pixel_data, (bytes, bytearray, memoryview)):
+        raise TypeError(f"PixelData is a bytes object, got {type(pixel_data).__name__}")
+    d = bytes(pixel_data)
+    pos, items = 0, []
+    while True:
+        if pos + 8 > len(d):
+            raise ValueError("PixelData ends without a sequence delimiter")
+        tag, ln = d[pos:pos + 4], int.from_bytes(d[pos + 4:pos + 8], "little")
+        pos += 8
+        if tag == _DICOM_SEQ_DELIM[:4]:
+            if ln != 0 or pos != len(d):
+                raise ValueError("sequence delimiter with a length, or bytes behind it")
+            break
+        if tag != _DICOM_ITEM:
+            raise ValueError(f"tag {tag.hex()} where an item was expected")
+        if pos + ln > len(d):
+            raise ValueError("item runs past the PixelData")
+        items.append(d[pos:pos + ln])
+        pos += ln
+    if not items:
+        raise ValueError("no Basic Offset Table item")
+    bot, frames = items[0], items[1:]
+    if len(bot) % 4 or (bot and len(bot) != 4 * len(frames)):
+        raise ValueError("Basic Offset Table does not list the fragments")
+    starts, at = [], 0
+    for f in frames:
+        starts.append(at)
+        at += 8 + len(f)
+    if bot and [int.from_bytes(bot[4 * k:4 * k + 4], "little") for k in range(len(frames))] != starts:
+        raise ValueError("Basic Offset Table does not list the fragments")
+    return frames

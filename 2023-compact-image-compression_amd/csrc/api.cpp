@@ -139,7 +139,7 @@ struct DecSlot {
 	DecSlot(const DecSlot &) = delete;
 	DecSlot &operator=(const DecSlot &) = delete;
 };
-constexpr int N_DEC_SLOTS = 2;
+constexpr int N_DEC_SLOTS = DEC_SLOTS;
 
 struct Context {
 	bool ready = false;
@@ -935,6 +935,7 @@ int cct_shutdown(void)
 		if (k > 0 && E.stream) (void)hipStreamDestroy(E.stream);
 	}
 	comm_release();
+	dicom_rle_release();
 	if (g_gate) { (void)hipFree(g_gate); g_gate = nullptr; }
 	for (auto &kv : g_ctx.luts) {
 		ShapeTables &t = kv.second;
@@ -1836,6 +1837,25 @@ static DecSlot &acquire_decode_slot(std::unique_lock<std::mutex> &lk)
 		std::this_thread::sleep_for(std::chrono::microseconds(50));
 	}
 }
+
+}  // extern "C"
+
+int cct::lease_decode_slot(DecLease &l)
+{
+	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device before slot and shared lock (cct_zlib_decompress_batch)
+		std::lock_guard<std::mutex> lk(g_mu);
+		int rc0 = ensure_ctx();
+		if (rc0) return rc0;
+	}
+	DecSlot &D = acquire_decode_slot(l.lk);
+	l.stream = D.stream;
+	l.slot = (int)(&D - g_dec);
+	return CCT_OK;
+}
+
+void cct::set_last_kernel_ms(bool encode, float ms) { (encode ? tl_enc_kernel_ms : tl_dec_kernel_ms) = ms; }
+
+extern "C" {
 
 int cct_zlib_decompress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, uint8_t *h_out, size_t out_stride,
                               uint32_t *h_out_sizes, uint32_t *h_status)

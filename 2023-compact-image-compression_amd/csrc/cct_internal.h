@@ -277,4 +277,35 @@ hipError_t launch_packbits_encode(const uint8_t *d_in, const uint64_t *d_offsets
 hipError_t launch_packbits_decode(const uint8_t *d_in, const uint64_t *d_offsets, int n, int delta, uint8_t *d_out, size_t out_stride,
                                   uint32_t *d_out_sizes, uint32_t *d_status, hipStream_t st);
 
+// ---- DICOM RLE Lossless (dicom_rle_kernels.hip) -----------------------------------------------
+// Encode: n rasters of rows x cols samples of `planes` bytes (1: uint8, 2: uint16) -> frame i at out + i * out_stride
+// (out_stride a multiple of 4, >= 64 + planes * 2 * rows * cols), its size in out_sizes[i].  rowinfo holds
+// n * planes * rows words: the size pass leaves each coded row's length there, the scan turns it into the row's offset in
+// the frame, the write pass reads it.  Every store of the write pass lies in [offset, offset + length) of its row.
+hipError_t launch_dicom_rle_encode(const void *d_images, int n, int rows, int cols, int planes, uint32_t *d_rowinfo, uint8_t *d_out,
+                                   size_t out_stride, uint32_t *d_out_sizes, hipStream_t st);
+// Decode: the host has parsed the frame headers; what reaches the device is a list of segments.  A segment is cut into
+// tiles of RLE_TILE coded bytes (its tiles are tile0 .. tile0 + ceil(len / RLE_TILE) - 1 of the pass, tile0 increasing
+// with the segment index).  A packet is at most 129 bytes long, so the first packet head of a tile lies at one of
+// RLE_ENTRIES offsets.
+constexpr uint32_t RLE_TILE = 2048, RLE_ENTRIES = 129;
+struct RleSegment {
+	uint64_t src;    // offset of the segment in the uploaded frames
+	uint64_t dst;    // byte offset in `images` of the first sample's byte this segment fills
+	uint32_t len;    // coded bytes (>= 1)
+	uint32_t tile0;
+};
+struct RleDecodeArgs {
+	const uint8_t *frames;       // uploaded frames; readable for 16 bytes past the last one
+	const RleSegment *segs;
+	uint32_t nseg, ntiles;
+	uint32_t want;               // rows * cols: bytes every segment has to yield
+	uint32_t step;               // bytes per sample in `images`: decoded byte k lands at dst + k * step
+	uint32_t *table;             // ntiles * RLE_ENTRIES words: (exit offset | bytes produced << 12) per entry offset
+	uint2 *tinfo;                // ntiles: the tile's true entry offset and the output index it starts at (clipped to want)
+	uint32_t *short_seg;         // nseg: 1 for a segment that yields fewer than `want` bytes
+	uint8_t *images;
+};
+hipError_t launch_dicom_rle_decode(const RleDecodeArgs &a, hipStream_t st);
+
 }  // namespace cct

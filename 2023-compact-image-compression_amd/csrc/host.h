@@ -1,5 +1,5 @@
 // Host-side declarations shared by the translation units of libcompact_hip.so (api.cpp: context, encode, decode;
-// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility).  Not part of the C ABI.
+// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec).  Not part of the C ABI.
 #pragma once
 #include <cstdarg>
 #include <cstddef>
@@ -96,5 +96,14 @@ hipStream_t main_stream();       // valid once ensure_ctx() has succeeded
 int bound_device();
 bool forked_after_init();        // this process is a fork() child of the one that initialised the device
 void comm_release();             // cct_shutdown: drop the communicator and its buffers (api_comm.cpp)
+
+// A decode slot lent to a translation unit outside api.cpp: its lock, its stream and its index (workspaces of such a caller
+// are its own, one set per slot).  Binds the device on first use, then waits for a free slot; the caller opens its ApiCall
+// once it holds the lease, as every decode entry point does.
+constexpr int DEC_SLOTS = 2;
+struct DecLease { std::unique_lock<std::mutex> lk; hipStream_t stream = nullptr; int slot = 0; };
+int lease_decode_slot(DecLease &l);
+void set_last_kernel_ms(bool encode, float ms);  // cct_last_timings [0] / [4] of the calling thread
+void dicom_rle_release();        // cct_shutdown: workspaces and events of api_dicom_rle.cpp
 
 }  // namespace cct

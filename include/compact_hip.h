@@ -328,6 +328,38 @@ int cct_packbits_encode_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 int cct_packbits_decode_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, int delta_transform,
                               uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, uint32_t *h_status);
 
+/* ---- DICOM RLE Lossless ------------------------------------------------------------- */
+/* The RLE column of the reference's comparison (scripts/evaluate.py:78-85, pydicom's Dataset.compress with
+ * RLELossless): frames of transfer syntax 1.2.840.10008.1.2.5 (DICOM PS3.5 Annex G) for one sample per pixel with 8 or 16
+ * bits allocated.  A frame is sixteen little-endian uint32 (the segment count, the segments' offsets from the frame start,
+ * zeros), then one segment per byte plane, most significant byte first: the plane in raster order, PackBits-coded row by
+ * row, padded with one 0x00 to an even length.  This is not the PackBits of cct_packbits_* above (chunks of 127, one string
+ * per wave), which stays what it is.
+ * cct_dicom_rle_encode_batch: n rasters of shape (rows, cols), C order, uint16 (bits 16) or uint8 (bits 8), on the host
+ * (images_on_device 0) or the device (1).  Frame i lands at h_out + i*out_stride, its size in h_out_sizes[i].  Rows are
+ * coded with the rule of pydicom's pure-Python encoder: maximal groups of equal bytes; a group of one joins the pending
+ * literals; a longer group flushes them and leaves as (129, v) per full 128 bytes and (257 - r, v) for a remainder r >= 2
+ * or (0, v) for r = 1; literals leave in chunks of 128; nothing carries across rows (tests/dicom_rle_model.py states the
+ * rule in Python).  The call takes the encode slot, like the PNG writer.  out_stride >= cct_dicom_rle_bound(rows, cols,
+ * bits) = 64 + bits/8 * 2 * rows * cols (CCT_E_CAP otherwise; 0 for a refused shape).
+ * cct_dicom_rle_decode_batch: n frames laid out back to back (frame i = h_frames[h_offsets[i] .. h_offsets[i+1])) ->
+ * n*rows*cols uint16 (bits 16) or uint8 (bits 8) at `images` (host or device), images_cap_px counted in pixels.  The host
+ * parses the headers, the device decodes the segments (a decode slot, like the PNG reader): header byte h < 128 copies the
+ * next h + 1 bytes (what is there, if the segment ends first), h > 128 writes 257 - h copies of the next byte (nothing, if
+ * there is none), 128 does nothing; a segment is read until rows*cols bytes are out and whatever follows is ignored (pad,
+ * encoder slack); packets may cross row ends.  Per-frame refusals in h_status[i], CCT_E_STREAM: a frame shorter than 64
+ * bytes, a segment count other than bits/8, a first offset other than 64, offsets that do not increase or lie past the
+ * frame, a segment that yields fewer than rows*cols bytes.  The other frames still decode, nothing is written outside a
+ * refused frame's own rows*cols slot, and the call returns the first non-OK status.
+ * Whole-call errors of both, before the device is touched: CCT_E_ARG for bits other than 8 or 16, rows or cols < 1, n < 0,
+ * rows*cols above 2^26; CCT_E_CAP for out_stride below the bound, or images_cap_px < n*rows*cols.
+ * cct_last_timings: [0] the three encode kernels, [4] the three decode kernels, HIP events, summed over the passes. */
+size_t cct_dicom_rle_bound(int rows, int cols, int bits);
+int cct_dicom_rle_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int bits /* 8 or 16 */,
+                               uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+int cct_dicom_rle_decode_batch(const uint8_t *h_frames, const uint64_t *h_offsets, int n, int rows, int cols, int bits,
+                               void *images, int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per frame */);
+
 /* ---- tuning / introspection (bench.py) --------------------------------------------- */
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per
  * thread: an encode and a decode driven from two threads do not overwrite each other; takes no lock):

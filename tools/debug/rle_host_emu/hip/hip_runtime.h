@@ -1,0 +1,77 @@
+// host emulation shim: one std::thread per GPU thread, blocks run one after another
+#pragma once
+#include <pthread.h>
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <thread>
+#include <vector>
+typedef int hipError_t; typedef void *hipStream_t; typedef void *hipEvent_t;
+constexpr hipError_t hipSuccess = 0;
+struct uint2 { uint32_t x, y; };
+static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
+struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
+extern thread_local dim3 threadIdx, blockIdx, blockDim;
+struct BlockCtx { pthread_barrier_t bar; pthread_barrier_t wbar[16]; uint64_t wslot[16][64]; int orflag[2]; int phase; };
+extern BlockCtx *g_blk;
+#define __global__
+#define __device__
+#define __forceinline__ inline
+#define __shared__ static
+#define __launch_bounds__(...)
+using std::min; using std::max;
+static inline void __syncthreads() { pthread_barrier_wait(&g_blk->bar); }
+static inline int __syncthreads_or(int v)
+{
+	static thread_local int ph = 0;
+	int *f = &g_blk->orflag[ph & 1];
+	if (v) __atomic_store_n(f, 1, __ATOMIC_SEQ_CST);
+	pthread_barrier_wait(&g_blk->bar);
+	int r = __atomic_load_n(f, __ATOMIC_SEQ_CST);
+	pthread_barrier_wait(&g_blk->bar);
+	if (threadIdx.x == 0) g_blk->orflag[ph & 1] = 0;
+	pthread_barrier_wait(&g_blk->bar);
+	return r;
+}
+static inline uint64_t wave_xchg(uint64_t v, int src)  // every lane of the wave must call
+{
+	const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+	g_blk->wslot[w][l] = v;
+	pthread_barrier_wait(&g_blk->wbar[w]);
+	uint64_t r = (src >= 0 && src < 64) ? g_blk->wslot[w][src] : v;
+	pthread_barrier_wait(&g_blk->wbar[w]);
+	return r;
+}
+static inline int __shfl(int v, int src) { return (int)wave_xchg((uint32_t)v, src & 63); }
+static inline int __shfl_up(int v, int d) { int l = threadIdx.x & 63; return (int)wave_xchg((uint32_t)v, l - d >= 0 ? l - d : -1); }
+static inline int __shfl_down(int v, int d) { int l = threadIdx.x & 63; return (int)wave_xchg((uint32_t)v, l + d < 64 ? l + d : -1); }
+static inline uint64_t __ballot(bool b)
+{
+	const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+	g_blk->wslot[w][l] = b;
+	pthread_barrier_wait(&g_blk->wbar[w]);
+	uint64_t r = 0;
+	for (int k = 0; k < 64; k++) r |= (uint64_t)(g_blk->wslot[w][k] & 1) << k;
+	pthread_barrier_wait(&g_blk->wbar[w]);
+	return r;
+}
+static inline int __clzll(long long x) { return x ? __builtin_clzll((unsigned long long)x) : 64; }
+static inline int __ffsll(long long x) { return __builtin_ffsll(x); }
+static inline hipError_t hipGetLastError() { return 0; }
+template <class K, class... A>
+void emu_launch(K kernel, dim3 grid, dim3 block, A... args)
+{
+	for (unsigned b = 0; b < grid.x; b++) {
+		BlockCtx ctx{};
+		pthread_barrier_init(&ctx.bar, nullptr, block.x);
+		for (unsigned w = 0; w < (block.x + 63) / 64; w++) pthread_barrier_init(&ctx.wbar[w], nullptr, std::min(64u, block.x - 64 * w));
+		g_blk = &ctx;
+		std::vector<std::thread> th;
+		for (unsigned t = 0; t < block.x; t++)
+			th.emplace_back([=]() { threadIdx = dim3(t); blockIdx = dim3(b); blockDim = block; kernel(args...); });
+		for (auto &x : th) x.join();
+	}
+}
+#define hipLaunchKernelGGL(k, g, b, sh, st, ...) emu_launch(k, g, b, __VA_ARGS__)
