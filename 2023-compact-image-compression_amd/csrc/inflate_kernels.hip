@@ -924,6 +924,8 @@ __global__ void __launch_bounds__(G::NT) inflate_kernel(InflateArgs a, uint64_t 
 	if (!err) {
 		__syncthreads();
 		flush_to(pos);
+	}
+	if (!err) {  // an output that outgrew its slot in this last flush was not summed: it is too long, not a bad stream
 		// Adler-32 trailer, big-endian, after the bit reader is byte aligned
 		getbits(br, br.cnt & 7);
 		uint32_t want = 0;
