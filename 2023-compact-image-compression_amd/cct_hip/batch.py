@@ -798,3 +798,143 @@ def dicom_fragments(pixel_data):
     if bot and [int.from_bytes(bot[4 * k:4 * k + 4], "little") for k in range(len(frames))] != starts:
         raise ValueError("Basic Offset Table does not list the fragments")
     return frames
+
+
+# ---- JPEG Lossless, SOF3 (T.81 process 14; DICOM 1.2.840.10008.1.2.4.70): frames on the device ----------------------
+
+_JPL_MAX_PIXELS = 1 << 26
+
+
+def _check_jpl_shape(rows, cols):
+    if not 1 <= rows <= 65535 or not 1 <= cols <= 65535:
+        raise ValueError(f"JPEG Lossless frame of {rows} x {cols} samples: rows and cols are 1 to 65535")
+    if rows * cols > _JPL_MAX_PIXELS:
+        raise ValueError(f"JPEG Lossless frame of {rows} x {cols} samples: more than {_JPL_MAX_PIXELS} pixels")
+
+
+def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=None, dtype=None):
+    """JPEG Lossless frames with selection value 1 (DICOM transfer syntax 1.2.840.10008.1.2.4.70) on the device: a uint16 or
+    uint8 array of shape (n, rows, cols) or (rows, cols), or a DeviceBuffer with shape= given (dtype= np.uint16 unless
+    np.uint8 is named), -> a list of n `bytes`, each one interchange file: SOI, SOF3, DHT, DRI (with restart_rows > 0: a
+    restart interval of that many rows, at most 65535 samples), SOS, entropy-coded segment, EOI.  precision is 2 .. 16 and
+    defaults to the sample width; uint8 samples take at most 8.  The Huffman table is the frame's own (T.81 Annex K.2);
+    tests/jpeg_lossless_model.py states the file.  A sample >= 2^precision raises OverflowError.  dicom_encapsulate wraps
+    the frames as PixelData.  Arguments are checked (TypeError / ValueError) before any device call.
+    Memory: the call reserves cct_jpegll_bound(rows, cols, restart_rows) bytes per frame on the host, the worst case of 31
+    bits a sample doubled by byte stuffing, about 7.75 bytes a sample (2 MB for 512 x 512, 520 MB for 256 such frames;
+    pages a file does not reach are never touched), and on the device that plus 4 bytes a sample, at most 512 MB at a time:
+    split a large batch if the address space matters."""
+    if isinstance(images, DeviceBuffer):
+        if shape is None:
+            raise ValueError("jpeg_lossless_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)")
+        dt = np.dtype(np.uint16 if dtype is None else dtype)
+        shape = tuple(int(x) for x in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise ValueError(f"frame batch shape {shape}: (n, rows, cols) or (rows, cols)")
+        n, rows, cols = shape
+        ptr, on_device, keep = images.ptr, 1, images
+    else:
+        if shape is not None or dtype is not None:
+            raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
+        arr = np.asarray(images)
+        dt = arr.dtype
+        if arr.ndim == 2:
+            arr = arr[None]
+        if arr.ndim != 3:
+            raise ValueError(f"frame batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
+        n, rows, cols = arr.shape
+    if dt != np.uint8 and dt != np.uint16:
+        raise TypeError(f"JPEG Lossless frames take uint8 or uint16 samples, got {dt}")
+    src_bits = 8 * dt.itemsize
+    if precision is None:
+        precision = src_bits
+    for name, x in (("precision", precision), ("restart_rows", restart_rows)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {x!r}")
+    precision, restart_rows = int(precision), int(restart_rows)
+    if not 2 <= precision <= 16:
+        raise ValueError(f"JPEG Lossless precision {precision}: 2 to 16")
+    if precision > src_bits:
+        raise ValueError(f"precision {precision} for {dt} samples: at most {src_bits}")
+    if restart_rows < 0:
+        raise ValueError(f"restart_rows {restart_rows}: 0 (no restart intervals) or a number of rows")
+    if n == 0:
+        return []
+    _check_jpl_shape(rows, cols)
+    if restart_rows * cols > 65535:
+        raise ValueError(f"a restart interval of {restart_rows} rows of {cols} samples: Ri is at most 65535")
+    if isinstance(images, DeviceBuffer):
+        if n < 0 or n * rows * cols * dt.itemsize > images.nbytes:
+            raise ValueError(f"frame batch shape {shape} of {dt} does not fit the {images.nbytes}-byte DeviceBuffer")
+    else:
+        arr = np.ascontiguousarray(arr)
+        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    L = _ffi.lib()
+    out_stride = L.cct_jpegll_bound(rows, cols, restart_rows)
+    out = np.empty((n, out_stride), dtype=np.uint8)
+    sizes = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_jpegll_encode_batch(ptr, on_device, n, rows, cols, src_bits, precision, restart_rows, out.ctypes.data,
+                                         out_stride, sizes.ctypes.data, status.ctypes.data))
+    del keep
+    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+
+
+def jpeg_lossless_info(file):
+    """(rows, cols, precision) of one JPEG Lossless file (`bytes`), from its SOF3 after the whole marker walk; host only.
+    ValueError for anything jpeg_lossless_decode_batch refuses by structure (CCT_E_JPEG in include/compact_hip.h)."""
+    if not isinstance(file, (bytes, bytearray, memoryview)):
+        raise TypeError(f"a JPEG file is a bytes object, got {type(file).__name__}")
+    file = bytes(file)
+    rows, cols, prec = C.c_int(0), C.c_int(0), C.c_int(0)
+    _ffi.check(_ffi.lib().cct_jpegll_info(file, len(file), C.byref(rows), C.byref(cols), C.byref(prec)))
+    return rows.value, cols.value, prec.value
+
+
+def jpeg_lossless_decode_batch(files, rows, cols, bits=16, out_dev=None, raise_errors=True):
+    """JPEG Lossless files (a list of `bytes`: SOF3, one component, precision <= `bits` = 8 or 16 allocated) -> an
+    (n, rows, cols) uint8 / uint16 array, decoded on the device: any of the seven predictors, a point transform (the sample
+    returned is value << Pt), restart intervals of whole rows, any Huffman table over the categories 0 .. 16.  With out_dev
+    it fills that DeviceBuffer and returns the shape, like decode_batch.  With raise_errors=False it returns (array or
+    shape, status) with status[i] 0, CCT_E_JPEG (13: the structure), CCT_E_MIXED (10: not rows x cols, or a precision above
+    bits) or CCT_E_STREAM (4: the entropy-coded data); include/compact_hip.h lists the cases.  The raster of a refused file
+    is unspecified.  Arguments are checked before any device call."""
+    for name, x in (("rows", rows), ("cols", cols), ("bits", bits)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {x!r}")
+    rows, cols, bits = int(rows), int(cols), int(bits)
+    if bits not in (8, 16):
+        raise ValueError(f"JPEG Lossless rasters of {bits} bits allocated: 8 or 16")
+    _check_jpl_shape(rows, cols)
+    if isinstance(files, (bytes, bytearray, memoryview, str)):
+        raise TypeError("jpeg_lossless_decode_batch takes a list of bytes objects, one per file")
+    files = list(files)
+    for f in files:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise TypeError(f"a JPEG file is a bytes object, got {type(f).__name__}")
+    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
+        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+    n, dt = len(files), np.dtype(np.uint8 if bits == 8 else np.uint16)
+    if n == 0:
+        res = (0, rows, cols) if out_dev is not None else np.zeros((0, rows, cols), dtype=dt)
+        return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
+    if out_dev is not None and n * rows * cols * dt.itemsize > out_dev.nbytes:
+        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
+    L = _ffi.lib()
+    blob = b"".join(bytes(f) for f in files) or b"\0"
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(f) for f in files], out=offs[1:])
+    status = np.zeros(n, dtype=np.uint32)
+    if out_dev is not None:
+        rc = L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, out_dev.ptr, 1,
+                                       out_dev.nbytes // dt.itemsize, status.ctypes.data)
+        res = (n, rows, cols)
+    else:
+        res = np.empty((n, rows, cols), dtype=dt)
+        rc = L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, res.ctypes.data, 0, res.size,
+                                       status.ctypes.data)
+    if raise_errors or rc not in (_ffi.E_JPEG, _ffi.E_MIXED, _ffi.E_STREAM):
+        _ffi.check(rc)
+    return res if raise_errors else (res, status)

@@ -308,4 +308,61 @@ struct RleDecodeArgs {
 };
 hipError_t launch_dicom_rle_decode(const RleDecodeArgs &a, hipStream_t st);
 
+// ---- JPEG Lossless, SOF3 (jpeg_lossless_kernels.hip) --------------------------------------------
+constexpr uint32_t JPL_HDR_MAX = 72;     // SOI 2, SOF3 13, DHT 4 + 1 + 16 + 17, DRI 6, SOS 10 = 69 bytes at most, rounded up
+constexpr uint32_t JPL_CHUNK = 1024;     // samples per step of the emit kernel: 4 per lane
+constexpr uint32_t JPL_SUB = 1024;       // bits per subsequence of the Huffman decoder (a coded sample has 31 at most)
+constexpr uint32_t JPL_ST_OVERFLOW = 1u; // encode: a sample >= 2^precision
+constexpr uint32_t JPL_ST_STREAM = 1u;   // decode: RST sequence, a code outside the table, data that ends early or is left over
+constexpr uint32_t JPL_ST_INTERVALS = 2u; // decode, set by jpl_unstuff_kernel only: the frame's interval starts are not valid, nothing of it is decoded
+struct JplCode {             // one frame's Huffman table as its DHT states it, and the code of every category (size 0: none)
+	uint8_t bits[16], huffval[17], nval;
+	uint8_t size[17];
+	uint16_t code[17];
+};
+// Encode.  Interval k of a frame holds rows [k * rpi, min(rows, (k + 1) * rpi)); n_int = ceil(rows / rpi).  bitbuf gives every
+// sample one word: interval k's unstuffed bytes start at word k * rpi * cols, 31 bits a sample fit.  The bytes of word w
+// are taken from its top down.  out_stride >= jpl_bound(): the layout kernel derives every offset from ibytes + iff, which
+// count bytes that exist in bitbuf, so no store leaves [0, bound).
+struct JplEncArgs {
+	const void *images;        // n * rows * cols samples of src_bits (8 or 16)
+	uint32_t src_bits, n, rows, cols, precision, rpi, n_int, restart;  // restart: a DRI segment and RST markers are written
+	uint32_t *hist;            // n * 17, zero on entry
+	uint32_t *status;          // n, zero on entry: JPL_ST_OVERFLOW
+	JplCode *codes;            // n
+	uint32_t *bitbuf;          // n * rows * cols words
+	uint32_t *ibytes, *iff;    // n * n_int: unstuffed bytes of an interval, and how many of them are 0xFF
+	uint32_t *ioff;            // n * n_int: offset in the file of the interval's first byte
+	uint8_t *out; size_t out_stride; uint32_t *out_sizes;  // a frame with a status gets size 0
+};
+hipError_t launch_jpl_encode(const JplEncArgs &a, hipStream_t st);
+// Decode.  The host has walked the markers (api_jpeg_lossless.cpp); a frame reaches the device as the byte range of its
+// entropy-coded segment, its decoding table and its scan parameters.
+struct JplFrame {
+	uint64_t src;              // offset of the entropy-coded segment in the upload; the unstuffed bytes go to the same offset of ubuf
+	uint32_t len;              // its bytes, RST markers included; the two bytes behind it (the next marker) are readable
+	uint32_t slot;             // the raster this frame fills: images + slot * rows * cols
+	uint32_t ss, pt, init;     // predictor, point transform, 2^(P - Pt - 1)
+	uint32_t rpi, n_int;       // rows per interval, intervals
+	uint32_t int0;             // index of its interval 0 among the pass's intervals; its n_int + 1 interval starts sit at istart[int0 + frame index ..]
+	uint32_t sub0;             // its first entry of the subsequence tables
+	int32_t maxcode[17];       // [l]: the largest code of length l, -1 where there is none
+	int32_t delta[17];         // [l]: index into huffval of the first code of length l, minus that code
+	uint8_t huffval[20];
+};
+struct JplDecArgs {
+	const uint8_t *files;      // the upload
+	const JplFrame *frames; uint32_t nframes;
+	const uint32_t *int_frame; uint32_t total_int;  // frame index of every interval of the pass
+	uint32_t rows, cols, out_bits;                  // out_bits 8 or 16: the sample type of images
+	uint8_t *ubuf;             // unstuffed entropy-coded bytes
+	uint32_t *istart;          // total_int + nframes: byte offset of every interval inside its frame's unstuffed data, and the end
+	uint32_t *sub_start, *sub_land, *sub_cnt;       // per subsequence: entry bit, landing bit, samples that start inside
+	uint16_t *diff;            // nslots * rows * cols: the differences, modulo 2^16
+	uint32_t *status;          // nframes, zero on entry: JPL_ST_STREAM
+	void *images;
+	uint32_t any_generic;      // some frame has a predictor other than 1
+};
+hipError_t launch_jpl_decode(const JplDecArgs &a, hipStream_t st);
+
 }  // namespace cct

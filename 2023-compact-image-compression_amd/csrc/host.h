@@ -1,5 +1,5 @@
 // Host-side declarations shared by the translation units of libcompact_hip.so (api.cpp: context, encode, decode;
-// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec).  Not part of the C ABI.
+// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec).  Not part of the C ABI.
 #pragma once
 #include <cstdarg>
 #include <cstddef>
@@ -105,5 +105,6 @@ struct DecLease { std::unique_lock<std::mutex> lk; hipStream_t stream = nullptr;
 int lease_decode_slot(DecLease &l);
 void set_last_kernel_ms(bool encode, float ms);  // cct_last_timings [0] / [4] of the calling thread
 void dicom_rle_release();        // cct_shutdown: workspaces and events of api_dicom_rle.cpp
+void jpegll_release();           // cct_shutdown: workspaces and events of api_jpeg_lossless.cpp
 
 }  // namespace cct

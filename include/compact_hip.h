@@ -63,6 +63,7 @@ extern "C" {
 #define CCT_E_MIXED 10    /* decode batch whose members differ in shape or flags */
 #define CCT_E_PNG 11      /* cct_png_read_batch / cct_png_info: not a PNG this reader takes -> ValueError */
 #define CCT_E_CRC 12      /* cct_png_read_batch: a chunk's CRC-32 does not match           -> ValueError */
+#define CCT_E_JPEG 13     /* cct_jpegll_decode_batch / cct_jpegll_info: not a JPEG this reader takes -> ValueError */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
 #define CCT_FLAG_FRACTAL 1u       /* transforms.fractal      (core.py:234) */
@@ -359,6 +360,44 @@ int cct_dicom_rle_encode_batch(const void *images, int images_on_device, int n, 
                                uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
 int cct_dicom_rle_decode_batch(const uint8_t *h_frames, const uint64_t *h_offsets, int n, int rows, int cols, int bits,
                                void *images, int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per frame */);
+
+/* ---- JPEG Lossless (SOF3) ------------------------------------------------------------- */
+/* JPEG Lossless, Non-Hierarchical, First-Order Prediction (ITU-T T.81 process 14 with selection value 1, DICOM transfer
+ * syntax 1.2.840.10008.1.2.4.70) for one sample per pixel; tests/jpeg_lossless_model.py states both directions in Python.
+ * cct_jpegll_encode_batch: n rasters of shape (rows, cols), C order, uint16 (src_bits 16) or uint8 (src_bits 8), on the
+ * host (images_on_device 0) or the device (1); precision P is 2 .. src_bits.  Frame i lands at h_out + i*out_stride, its
+ * size in h_out_sizes[i]: SOI, SOF3, one DHT, DRI (only with restart_rows > 0: Ri = restart_rows * cols <= 65535), SOS
+ * (Ss 1, Pt 0), the entropy-coded segment, EOI; no APPn.  The first sample of the image and of every restart interval is
+ * predicted by 2^(P-1), the rest of that row by the sample to the left, column 0 of a later row by the sample above.
+ * Differences are taken modulo 2^16; the Huffman table is built per frame by Annex K.2 (ties go to the larger symbol, the
+ * reserved symbol 256 has frequency 1).  A frame with a sample >= 2^P gets CCT_E_OVERFLOW in h_status[i] and size 0; the
+ * other frames are written and the call returns the first non-OK status.  The call takes the encode slot, like the RLE codec.
+ * cct_jpegll_bound(rows, cols, restart_rows): a sample costs at most 31 bits (a 16-bit code and 15 extra bits), an interval
+ * of s samples at most ceil(31 s / 8) bytes, doubled by byte stuffing, plus 2 for its RST; headers and EOI stay below 72:
+ * 72 + intervals * (2 * ceil(31 s / 8) + 2).  0 for a refused shape; out_stride below it is CCT_E_CAP.
+ * That is about 7.75 bytes a sample (2 MB for 512 x 512): size h_out for it, the files themselves are a fraction of it
+ * and each is copied out at its own length.
+ * cct_jpegll_info: (rows, cols, precision) of one file from its SOF3, after the whole marker walk; host only.
+ * cct_jpegll_decode_batch: n files laid out back to back -> n*rows*cols uint16 (bits 16) or uint8 (bits 8) at `images`
+ * (host or device), images_cap_px counted in pixels; a decode slot.  The host walks the markers and takes: any APPn / COM
+ * segment; SOF3 with Nf = 1, P 2 .. 16 (<= bits), Y = rows, X = cols (anything else: CCT_E_MIXED); DHT segments of class 0
+ * with ids 0 .. 3, which may hold several tables and redefine one, symbols <= 16, codes not over-subscribed; DRI with Ri a
+ * multiple of cols; one SOS with Ns = 1, Ss 1 .. 7, Se = 0, Ah = 0, Al = Pt < P; RST markers in sequence; bytes behind
+ * EOI.  The sample written is value << Pt.  CCT_E_JPEG, decided before upload: no SOI, SOF3 or EOI, another SOF type,
+ * Nf != 1, Y = 0, DNL, a second scan, a table the scan names but nobody defined, a bad segment length, a DRI that is not
+ * whole rows.  CCT_E_STREAM, found on the device: a code that is not in the table, entropy-coded data that ends early or
+ * leaves whole bytes over, a wrong, missing or spare RST.  Refused files leave the others decoded, nothing is written
+ * outside a refused file's own rows*cols slot, and the call returns the first non-OK status.
+ * Whole-call errors, before the device is touched: CCT_E_ARG for rows or cols outside 1 .. 65535, rows*cols above 2^26,
+ * n < 0, bits or src_bits other than 8 or 16, a precision outside 2 .. src_bits, Ri above 65535; CCT_E_CAP as above.
+ * cct_last_timings: [0] the five encode kernels, [4] the decode kernels, HIP events, summed over the passes. */
+size_t cct_jpegll_bound(int rows, int cols, int restart_rows);
+int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int src_bits /* 8 or 16 */,
+                            int precision, int restart_rows, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes,
+                            uint32_t *h_status /* CCT_E_* per frame */);
+int cct_jpegll_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
+int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits, void *images,
+                            int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
 
 /* ---- tuning / introspection (bench.py) --------------------------------------------- */
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per
