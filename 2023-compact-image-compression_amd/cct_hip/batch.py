@@ -28,9 +28,22 @@ def magic_bytes(config):
 Z_HUFFMAN_ONLY, Z_RLE = 2, 3  # zlib strategies that run deflate_huff / deflate_rle, which read no level table
 
 
+def _is_int(x):
+    """an integer that is not a bool"""
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def _ints(**named):
+    """the named arguments as a list of ints; TypeError for the first that is not an integer"""
+    for name, x in named.items():
+        if not _is_int(x):
+            raise TypeError(f"{name} must be an integer, got {x!r}")
+    return [int(x) for x in named.values()]
+
+
 def _check_strategy(strategy):
     """zlib strategy 0 .. 4 (Z_DEFAULT_STRATEGY, Z_FILTERED, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED) or ValueError"""
-    if isinstance(strategy, bool) or not isinstance(strategy, (int, np.integer)):
+    if not _is_int(strategy):
         raise ValueError(f"deflate strategy must be an integer (zlib's Z_* constants), got {strategy!r}")
     strategy = int(strategy)
     if not 0 <= strategy <= 4:
@@ -40,7 +53,7 @@ def _check_strategy(strategy):
 
 def _check_level(level, strategy):
     """zlib level of (level, strategy) on the device: -1 -> 6; 4 .. 9; also 1 .. 3 under Z_HUFFMAN_ONLY / Z_RLE"""
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+    if not _is_int(level):
         raise ValueError(f"deflate_level must be an integer, got {level!r}")
     level = int(level)
     if level == -1:
@@ -237,6 +250,101 @@ def partition_roles(image, config=None):
     return d_roles.download(np.uint8, nb)
 
 
+# ---- what the batch entry points below share: how they read their arguments and hand buffers to the C ABI --------------
+
+def _raster_batch(images, shape, dtype, fn, noun, dtype_words=""):
+    """(source, (n, rows, cols), dtype) of an encoder's rasters: an array of shape (n, rows, cols) or (rows, cols), or a
+    DeviceBuffer that shape= (and dtype=, np.uint16 if absent; required where dtype_words names the choice) describe.
+    fn and noun ("PNG", "frame") are the caller's words in the messages."""
+    if isinstance(images, DeviceBuffer):
+        if shape is None or (dtype_words and dtype is None):
+            raise ValueError(f"{fn} of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)"
+                             + (f" and dtype={dtype_words}" if dtype_words else ""))
+        dt = np.dtype(np.uint16 if dtype is None else dtype)
+        shape = tuple(int(x) for x in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise ValueError(f"{noun} batch shape {shape}: (n, rows, cols) or (rows, cols)")
+        return images, shape, dt
+    if shape is not None or dtype is not None:
+        raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
+    arr = np.asarray(images)
+    if arr.ndim == 2:
+        arr = arr[None]
+    if arr.ndim != 3:
+        raise ValueError(f"{noun} batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
+    return arr, arr.shape, arr.dtype
+
+
+def _raster_ptr(src, shape, dt, what):
+    """(ptr, on_device, keep) of a checked _raster_batch: a DeviceBuffer must hold the batch (`what` names it in the
+    message), an array is made contiguous; keep is what has to outlive the C call."""
+    if isinstance(src, DeviceBuffer):
+        n, rows, cols = shape
+        if n < 0 or n * rows * cols * dt.itemsize > src.nbytes:
+            raise ValueError(f"{what} does not fit the {src.nbytes}-byte DeviceBuffer")
+        return src.ptr, 1, src
+    arr = np.ascontiguousarray(src)
+    return arr.ctypes.data, 0, arr
+
+
+def _file_list(files, fn, per, what):
+    """files as a list of bytes objects, or TypeError: "<fn> takes a list .. one per <per>", "<what> is a bytes object" """
+    if isinstance(files, (bytes, bytearray, memoryview, str)):
+        raise TypeError(f"{fn} takes a list of bytes objects, one per {per}")
+    files = list(files)
+    for f in files:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise TypeError(f"{what} is a bytes object, got {type(f).__name__}")
+    return files
+
+
+def _archive(files):
+    """(blob, offs): the files back to back (one byte where there is none: the C side wants an address) and the n + 1
+    offsets of an archive argument"""
+    offs = np.zeros(len(files) + 1, dtype=np.uint64)
+    np.cumsum([len(f) for f in files], out=offs[1:])
+    return b"".join(files) or b"\0", offs
+
+
+def _files_out(n, out_stride):
+    """(out, sizes) for an encoder that writes file i at out[i] and its length to sizes[i]"""
+    return np.empty((n, out_stride), dtype=np.uint8), np.zeros(n, dtype=np.uint32)
+
+
+def _files_of(out, sizes):
+    return [out[i, : sizes[i]].tobytes() for i in range(len(sizes))]
+
+
+def _check_out_dev(out_dev):
+    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
+        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+
+
+def _no_rasters(shape, dt, out_dev, raise_errors):
+    """what a raster decoder returns for an empty batch"""
+    res = shape if out_dev is not None else np.zeros(shape, dtype=dt)
+    return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
+
+
+def _decode_rasters(call, n, rows, cols, dt, out_dev, raise_errors, per_file_codes):
+    """Run call(images, images_on_device, images_cap_px, status) -> rc into a fresh (n, rows, cols) array or into out_dev.
+    Returns the array (the shape with out_dev); with raise_errors=False, (that, status), and the per-file codes pass."""
+    if out_dev is not None and n * rows * cols * dt.itemsize > out_dev.nbytes:
+        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
+    status = np.zeros(n, dtype=np.uint32)
+    if out_dev is not None:
+        res = (n, rows, cols)
+        rc = call(out_dev.ptr, 1, out_dev.nbytes // dt.itemsize, status.ctypes.data)
+    else:
+        res = np.empty((n, rows, cols), dtype=dt)
+        rc = call(res.ctypes.data, 0, res.size, status.ctypes.data)
+    if raise_errors or rc not in per_file_codes:
+        _ffi.check(rc)
+    return res if raise_errors else (res, status)
+
+
 def encode_batch(images, config=None, return_info=False):
     """images: (n, W, H) array of a 2-byte dtype (or a DeviceBuffer + shape via encode_batch_dev).
     Returns a list of n `bytes`, each exactly what Encoder(config, images[i]).encode() returns."""
@@ -282,7 +390,7 @@ def _encode(ptr, on_device, n, w, h, config, dtype, return_info, keep=None):
         _ffi.check(L.cct_encode_batch(ptr, on_device, n, w, h, bs, flags, eof, magic, ch, bpc,
                                       out.ctypes.data, out_stride, sizes.ctypes.data, status.ctypes.data,
                                       psizes.ctypes.data, C.cast(stats, C.c_void_p)))
-        files = [out[i, : sizes[i]].tobytes() for i in range(n)]
+        files = _files_of(out, sizes[:n])
     if return_info:
         info = [{"payload_len": int(psizes[i]), "n_short": stats[i].n_short, "n_full": stats[i].n_full,
                  "n_jump": stats[i].n_jump, "n_difficult": stats[i].n_difficult,
@@ -306,9 +414,7 @@ def decode_batch(files, config=None, out_dev=None):
     w, h = hdr.width, hdr.height
     if (w * h) % bs != 0 or w * h == 0:  # core.py:429
         raise ValueError(f"cannot reshape array of size {w * h} into shape ({(w * h) // bs},{bs})")
-    blob = b"".join(files)
-    offs = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(f) for f in files], out=offs[1:])
+    blob, offs = _archive(files)
     status = np.zeros(n, dtype=np.uint32)
     if out_dev is not None:
         rc = L.cct_decode_batch(blob, offs.ctypes.data, n, bs, magic, out_dev.ptr, 1, out_dev.nbytes // 2,
@@ -323,7 +429,7 @@ def decode_batch(files, config=None, out_dev=None):
 
 def _check_mem_level(mem_level):
     """zlib memLevel on the device: 8 (zlib's default) or 9 (Pillow's PNG writer), or ValueError"""
-    if isinstance(mem_level, bool) or not isinstance(mem_level, (int, np.integer)) or int(mem_level) not in (8, 9):
+    if not _is_int(mem_level) or int(mem_level) not in (8, 9):
         raise ValueError(f"zlib mem_level {mem_level!r}: the device runs memLevel 8 and 9")
     return int(mem_level)
 
@@ -341,9 +447,7 @@ def zlib_compress_batch(blobs, level=9, strategy=0, mem_level=8):
     n = len(blobs)
     if n == 0:
         return []
-    offs = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in blobs], out=offs[1:])
-    data = b"".join(blobs) or b"\0"
+    data, offs = _archive(blobs)
     longest = max(len(b) for b in blobs)
     in_stride = (longest + 16 + 255) & ~255
     # compressBound at memLevel 8, deflateBound's general bound at 9 (api.cpp zlib_bound), + slack
@@ -352,15 +456,14 @@ def zlib_compress_batch(blobs, level=9, strategy=0, mem_level=8):
     else:
         bound = in_stride + ((in_stride + 7) >> 3) + ((in_stride + 63) >> 6) + 11
     out_stride = (bound + 11 + 128 + 63) & ~63
-    out = np.empty((n, out_stride), dtype=np.uint8)
-    sizes = np.zeros(n, dtype=np.uint32)
+    out, sizes = _files_out(n, out_stride)
     _ffi.check(L.cct_zlib_compress_batch_params(data, offs.ctypes.data, n, level, strategy, mem_level, out.ctypes.data,
                                                 out_stride, sizes.ctypes.data))
-    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+    return _files_of(out, sizes)
 
 
 def _png_level(level):
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+    if not _is_int(level):
         raise TypeError(f"PNG compress_level must be an integer, got {level!r}")
     level = 6 if int(level) == -1 else int(level)
     if not 4 <= level <= 9:
@@ -369,40 +472,12 @@ def _png_level(level):
     return level
 
 
-def _png_args(images, level, shift, shape):
-    """Validated (ptr, on_device, n, rows, cols, level, shift, keep) of png_encode_batch; raises before any device call."""
-    level = _png_level(level)
-    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)):
+def _png_shift(shift):
+    if not _is_int(shift):
         raise TypeError(f"PNG sample shift must be an integer, got {shift!r}")
-    shift = int(shift)
-    if not 0 <= shift <= 15:
-        raise ValueError(f"PNG sample shift {shift}: 0 to 15")
-    if isinstance(images, DeviceBuffer):
-        if shape is None:
-            raise ValueError("png_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)")
-        shape = tuple(int(x) for x in shape)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3:
-            raise ValueError(f"PNG batch shape {shape}: (n, rows, cols) or (rows, cols)")
-        n, rows, cols = shape
-        if n < 0 or n * rows * cols * 2 > images.nbytes:
-            raise ValueError(f"PNG batch shape {shape} does not fit the {images.nbytes}-byte DeviceBuffer")
-        ptr, on_device, keep = images.ptr, 1, images
-    else:
-        arr = np.asarray(images)
-        if arr.dtype != np.uint16:
-            raise TypeError(f"16-bit PNGs take uint16 samples, got {arr.dtype}")
-        if arr.ndim == 2:
-            arr = arr[None]
-        if arr.ndim != 3:
-            raise ValueError(f"PNG batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
-        n, rows, cols = arr.shape
-        _check_png_shape(rows, cols)  # before the copy below
-        arr = np.ascontiguousarray(arr)
-        ptr, on_device, keep = arr.ctypes.data, 0, arr
-    _check_png_shape(rows, cols)
-    return ptr, on_device, n, rows, cols, level, shift, keep
+    if not 0 <= int(shift) <= 15:
+        raise ValueError(f"PNG sample shift {int(shift)}: 0 to 15")
+    return int(shift)
 
 
 def _check_png_shape(rows, cols):
@@ -410,6 +485,23 @@ def _check_png_shape(rows, cols):
         raise ValueError(f"PNG of {rows} x {cols} samples: rows and cols must be >= 1")
     if rows * (1 + 2 * cols) > (1 << 30) - 512:
         raise ValueError(f"PNG of {rows} x {cols} samples: more filtered bytes than one device DEFLATE pass takes")
+
+
+def _png_args(images, level, shift, shape):
+    """Validated (ptr, on_device, n, rows, cols, level, shift, keep) of png_encode_batch; raises before any device call."""
+    level, shift = _png_level(level), _png_shift(shift)
+    on_host = not isinstance(images, DeviceBuffer)
+    if on_host:
+        shape = None  # an array carries its own; this writer has always let a shape= beside it pass
+        if np.asarray(images).dtype != np.uint16:  # this writer names the dtype before the rank, the others the rank first
+            raise TypeError(f"16-bit PNGs take uint16 samples, got {np.asarray(images).dtype}")
+    src, shape, dt = _raster_batch(images, shape, None, "png_encode_batch", "PNG")
+    n, rows, cols = shape
+    if on_host:
+        _check_png_shape(rows, cols)  # before the copy below
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"PNG batch shape {shape}")
+    _check_png_shape(rows, cols)
+    return ptr, on_device, n, rows, cols, level, shift, keep
 
 
 def png_encode_batch(images, level=6, shift=0, shape=None):
@@ -424,12 +516,11 @@ def png_encode_batch(images, level=6, shift=0, shape=None):
         return []
     L = _ffi.lib()
     out_stride = L.cct_png_bound(rows, cols)
-    out = np.empty((n, out_stride), dtype=np.uint8)
-    sizes = np.zeros(n, dtype=np.uint32)
+    out, sizes = _files_out(n, out_stride)
     _ffi.check(L.cct_png_encode_batch(ptr, on_device, n, rows, cols, shift, level, out.ctypes.data, out_stride,
                                       sizes.ctypes.data))
     del keep
-    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+    return _files_of(out, sizes)
 
 
 def decode_png_batch(files, config=None, level=9):
@@ -437,26 +528,30 @@ def decode_png_batch(files, config=None, level=9):
     writes them (imageio -> Pillow at compress_level 9, value << 4: core.py:522-538): files are decoded into HBM and
     turned into PNGs there, without the rasters coming back to the host.  Returns a list of PNG `bytes`."""
     config = config or default_config()
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+    if not _is_int(level):
         raise TypeError(f"PNG compress_level must be an integer, got {level!r}")
     if not (int(level) == -1 or 4 <= int(level) <= 9):
         raise ValueError(f"PNG compress_level {level}: supported levels are -1 and 4 to 9")
     if not files:
         return []
+    n, w, h, d_img = _decode_to_device(files, config)
+    return png_encode_batch(d_img, level=level, shift=4, shape=(n, w, h))
+
+
+def _decode_to_device(files, config):
+    """(n, w, h, DeviceBuffer) of .cct files decoded into HBM"""
     hdr = _ffi.Header()
     _ffi.check(_ffi.lib().cct_read_header(files[0], len(files[0]), magic_bytes(config), C.byref(hdr)))
     d_img = DeviceBuffer(max(2 * len(files) * hdr.width * hdr.height, 2))
-    n, w, h = decode_batch(files, config, out_dev=d_img)
-    return png_encode_batch(d_img, level=level, shift=4, shape=(n, w, h))
+    return decode_batch(files, config, out_dev=d_img) + (d_img,)
 
 
 def _png_window(window):
     """(lo, hi) of a window argument, 0 <= lo < hi <= 65535, or TypeError / ValueError"""
     if isinstance(window, (str, bytes)) or not hasattr(window, "__len__") or len(window) != 2:
         raise TypeError(f"PNG window must be a pair (lo, hi), got {window!r}")
-    for x in window:
-        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
-            raise TypeError(f"PNG window bounds must be integers, got {window!r}")
+    if not all(_is_int(x) for x in window):
+        raise TypeError(f"PNG window bounds must be integers, got {window!r}")
     lo, hi = int(window[0]), int(window[1])
     if not 0 <= lo < hi <= 65535:
         raise ValueError(f"PNG window ({lo}, {hi}): 0 <= lo < hi <= 65535")
@@ -467,31 +562,13 @@ def _png8_args(images, window, level, shape, dtype):
     """Validated (ptr, on_device, n, rows, cols, src_bits, lo, hi, level, keep) of png8_encode_batch; raises before any
     device call."""
     level = _png_level(level)
-    if isinstance(images, DeviceBuffer):
-        if shape is None or dtype is None:
-            raise ValueError("png8_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols) and "
-                             "dtype=np.uint8 or np.uint16")
-        try:
-            dt = np.dtype(dtype)
+    if isinstance(images, DeviceBuffer) and shape is not None and dtype is not None:
+        try:  # this writer answers for a dtype numpy does not know in its own words
+            np.dtype(dtype)
         except TypeError:
             raise TypeError(f"8-bit PNGs take uint8 or uint16 samples, got dtype {dtype!r}") from None
-        shape = tuple(int(x) for x in shape)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3:
-            raise ValueError(f"PNG batch shape {shape}: (n, rows, cols) or (rows, cols)")
-        n, rows, cols = shape
-        ptr, on_device, keep = images.ptr, 1, images
-    else:
-        if dtype is not None or shape is not None:
-            raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
-        arr = np.asarray(images)
-        dt = arr.dtype
-        if arr.ndim == 2:
-            arr = arr[None]
-        if arr.ndim != 3:
-            raise ValueError(f"PNG batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
-        n, rows, cols = arr.shape
+    src, shape, dt = _raster_batch(images, shape, dtype, "png8_encode_batch", "PNG", "np.uint8 or np.uint16")
+    n, rows, cols = shape
     if dt == np.uint8:
         if window is not None:
             raise ValueError("uint8 samples are written as they are: window must be None")
@@ -504,12 +581,7 @@ def _png8_args(images, window, level, shape, dtype):
     else:
         raise TypeError(f"8-bit PNGs take uint8 or uint16 samples, got {dt}")
     _check_png_shape(rows, cols)  # the 16-bit writer's limit: cct_png_bound, which sizes the output, has no figure beyond it
-    if isinstance(images, DeviceBuffer):
-        if n < 0 or n * rows * cols * (src_bits // 8) > images.nbytes:
-            raise ValueError(f"PNG batch shape {shape} of {dt} does not fit the {images.nbytes}-byte DeviceBuffer")
-    else:
-        arr = np.ascontiguousarray(arr)
-        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"PNG batch shape {shape} of {dt}")
     return ptr, on_device, n, rows, cols, src_bits, lo, hi, level, keep
 
 
@@ -528,12 +600,11 @@ def png8_encode_batch(images, window=None, level=6, shape=None, dtype=None):
         return []
     L = _ffi.lib()
     out_stride = L.cct_png_bound(rows, cols)
-    out = np.empty((n, out_stride), dtype=np.uint8)
-    sizes = np.zeros(n, dtype=np.uint32)
+    out, sizes = _files_out(n, out_stride)
     _ffi.check(L.cct_png_encode8_batch(ptr, on_device, n, rows, cols, src_bits, lo, hi, level, out.ctypes.data, out_stride,
                                        sizes.ctypes.data))
     del keep
-    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+    return _files_of(out, sizes)
 
 
 def decode_png8_batch(files, window, config=None, level=6):
@@ -541,19 +612,11 @@ def decode_png8_batch(files, window, config=None, level=6):
     window=(lo, hi) (png8_encode_batch), without the rasters coming back to the host.  Returns a list of PNG `bytes`."""
     lo, hi = _png_window(window)
     level = _png_level(level)
-    if isinstance(files, (bytes, bytearray, memoryview, str)):
-        raise TypeError("decode_png8_batch takes a list of bytes objects, one per file")
-    files = list(files)
-    for f in files:
-        if not isinstance(f, (bytes, bytearray, memoryview)):
-            raise TypeError(f"a .cct file is a bytes object, got {type(f).__name__}")
+    files = _file_list(files, "decode_png8_batch", "file", "a .cct file")
     config = config or default_config()
     if not files:
         return []
-    hdr = _ffi.Header()
-    _ffi.check(_ffi.lib().cct_read_header(files[0], len(files[0]), magic_bytes(config), C.byref(hdr)))
-    d_img = DeviceBuffer(max(2 * len(files) * hdr.width * hdr.height, 2))
-    n, w, h = decode_batch(files, config, out_dev=d_img)
+    n, w, h, d_img = _decode_to_device(files, config)
     return png8_encode_batch(d_img, window=(lo, hi), level=level, shape=(n, w, h), dtype=np.uint16)
 
 
@@ -575,43 +638,19 @@ def png_read_batch(files, shift=0, out_dev=None, raise_errors=True):
     With out_dev it fills that DeviceBuffer and returns the shape, like decode_batch.  With raise_errors=False it returns
     (array or shape, status) with status[i] a CCT_E_* code (include/compact_hip.h lists the refusals); the raster of a
     refused file is unspecified.  Arguments are checked (TypeError / ValueError) before any device call."""
-    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)):
-        raise TypeError(f"PNG sample shift must be an integer, got {shift!r}")
-    shift = int(shift)
-    if not 0 <= shift <= 15:
-        raise ValueError(f"PNG sample shift {shift}: 0 to 15")
-    if isinstance(files, (bytes, bytearray, memoryview, str)):
-        raise TypeError("png_read_batch takes a list of bytes objects, one per file")
-    files = list(files)
-    for f in files:
-        if not isinstance(f, (bytes, bytearray, memoryview)):
-            raise TypeError(f"a PNG file is a bytes object, got {type(f).__name__}")
-    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
-        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+    shift = _png_shift(shift)
+    files = _file_list(files, "png_read_batch", "file", "a PNG file")
+    _check_out_dev(out_dev)
     n = len(files)
     if n == 0:
-        res = (0, 0, 0) if out_dev is not None else np.zeros((0, 0, 0), dtype=np.uint16)
-        return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
+        return _no_rasters((0, 0, 0), np.uint16, out_dev, raise_errors)
     rows, cols, _ = png_info(files[0])
     _check_png_shape(rows, cols)
-    if out_dev is not None and n * rows * cols * 2 > out_dev.nbytes:
-        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
     L = _ffi.lib()
-    blob = b"".join(files)
-    offs = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(f) for f in files], out=offs[1:])
-    status = np.zeros(n, dtype=np.uint32)
-    if out_dev is not None:
-        rc = L.cct_png_read_batch(blob, offs.ctypes.data, n, rows, cols, shift, out_dev.ptr, 1, out_dev.nbytes // 2,
-                                  status.ctypes.data)
-        res = (n, rows, cols)
-    else:
-        res = np.empty((n, rows, cols), dtype=np.uint16)
-        rc = L.cct_png_read_batch(blob, offs.ctypes.data, n, rows, cols, shift, res.ctypes.data, 0, res.size,
-                                  status.ctypes.data)
-    if raise_errors or rc not in (_ffi.E_PNG, _ffi.E_MIXED, _ffi.E_CRC, _ffi.E_ZLIB, _ffi.E_STREAM):
-        _ffi.check(rc)
-    return res if raise_errors else (res, status)
+    blob, offs = _archive(files)
+    return _decode_rasters(lambda *to: L.cct_png_read_batch(blob, offs.ctypes.data, n, rows, cols, shift, *to), n, rows, cols,
+                           np.dtype(np.uint16), out_dev, raise_errors,
+                           (_ffi.E_PNG, _ffi.E_MIXED, _ffi.E_CRC, _ffi.E_ZLIB, _ffi.E_STREAM))
 
 
 def zlib_decompress_batch(streams, max_out, raise_errors=True):
@@ -622,18 +661,15 @@ def zlib_decompress_batch(streams, max_out, raise_errors=True):
     n = len(streams)
     if n == 0:
         return [] if raise_errors else ([], np.zeros(0, dtype=np.uint32))
-    offs = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in streams], out=offs[1:])
-    data = b"".join(streams) or b"\0"
+    data, offs = _archive(streams)
     out_stride = (int(max_out) + 15 + 16) & ~15
-    out = np.empty((n, out_stride), dtype=np.uint8)
-    sizes = np.zeros(n, dtype=np.uint32)
+    out, sizes = _files_out(n, out_stride)
     status = np.zeros(n, dtype=np.uint32)
     rc = L.cct_zlib_decompress_batch(data, offs.ctypes.data, n, out.ctypes.data, out_stride, sizes.ctypes.data,
                                      status.ctypes.data)
     if raise_errors:
         _ffi.check(rc)
-    outs = [out[i, : sizes[i]].tobytes() if status[i] == 0 else None for i in range(n)]
+    outs = [f if status[i] == 0 else None for i, f in enumerate(_files_of(out, sizes))]
     return outs if raise_errors else (outs, status)
 
 
@@ -657,46 +693,21 @@ def dicom_rle_encode_batch(images, shape=None, dtype=None):
     list of n `bytes`.  Frame i is the 64-byte header and one PackBits segment per byte plane (high byte first), rows coded
     one by one with the rule of pydicom's pure-Python encoder; tests/dicom_rle_model.py states it.  dicom_encapsulate wraps
     frames as PixelData.  Arguments are checked (TypeError / ValueError) before any device call."""
-    if isinstance(images, DeviceBuffer):
-        if shape is None:
-            raise ValueError("dicom_rle_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)")
-        dt = np.dtype(np.uint16 if dtype is None else dtype)
-        shape = tuple(int(x) for x in shape)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3:
-            raise ValueError(f"frame batch shape {shape}: (n, rows, cols) or (rows, cols)")
-        n, rows, cols = shape
-        ptr, on_device, keep = images.ptr, 1, images
-    else:
-        if shape is not None or dtype is not None:
-            raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
-        arr = np.asarray(images)
-        dt = arr.dtype
-        if arr.ndim == 2:
-            arr = arr[None]
-        if arr.ndim != 3:
-            raise ValueError(f"frame batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
-        n, rows, cols = arr.shape
+    src, shape, dt = _raster_batch(images, shape, dtype, "dicom_rle_encode_batch", "frame")
+    n, rows, cols = shape
     if dt != np.uint8 and dt != np.uint16:
         raise TypeError(f"DICOM RLE frames take uint8 or uint16 samples, got {dt}")
     if n == 0:
         return []
     _check_rle_shape(rows, cols)
     bits = 8 * dt.itemsize
-    if isinstance(images, DeviceBuffer):
-        if n < 0 or n * rows * cols * dt.itemsize > images.nbytes:
-            raise ValueError(f"frame batch shape {shape} of {dt} does not fit the {images.nbytes}-byte DeviceBuffer")
-    else:
-        arr = np.ascontiguousarray(arr)
-        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"frame batch shape {shape} of {dt}")
     L = _ffi.lib()
     out_stride = L.cct_dicom_rle_bound(rows, cols, bits)
-    out = np.empty((n, out_stride), dtype=np.uint8)
-    sizes = np.zeros(n, dtype=np.uint32)
+    out, sizes = _files_out(n, out_stride)
     _ffi.check(L.cct_dicom_rle_encode_batch(ptr, on_device, n, rows, cols, bits, out.ctypes.data, out_stride, sizes.ctypes.data))
     del keep
-    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+    return _files_of(out, sizes)
 
 
 def dicom_rle_decode_batch(frames, rows, cols, bits=16, out_dev=None, raise_errors=True):
@@ -706,54 +717,26 @@ def dicom_rle_decode_batch(frames, rows, cols, bits=16, out_dev=None, raise_erro
     (array or shape, status) with status[i] 0 or CCT_E_STREAM (a frame shorter than its header, a segment count other than
     bits / 8, offsets that do not start at 64, do not increase or leave the frame, a segment that yields fewer than
     rows * cols bytes); the raster of a refused frame is unspecified.  Arguments are checked before any device call."""
-    for name, x in (("rows", rows), ("cols", cols), ("bits", bits)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise TypeError(f"{name} must be an integer, got {x!r}")
-    rows, cols, bits = int(rows), int(cols), int(bits)
+    rows, cols, bits = _ints(rows=rows, cols=cols, bits=bits)
     if bits not in (8, 16):
         raise ValueError(f"DICOM RLE frames of {bits} bits allocated: 8 or 16")
     _check_rle_shape(rows, cols)
-    if isinstance(frames, (bytes, bytearray, memoryview, str)):
-        raise TypeError("dicom_rle_decode_batch takes a list of bytes objects, one per frame")
-    frames = list(frames)
-    for f in frames:
-        if not isinstance(f, (bytes, bytearray, memoryview)):
-            raise TypeError(f"a frame is a bytes object, got {type(f).__name__}")
-    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
-        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+    frames = _file_list(frames, "dicom_rle_decode_batch", "frame", "a frame")
+    _check_out_dev(out_dev)
     n, dt = len(frames), np.dtype(np.uint8 if bits == 8 else np.uint16)
     if n == 0:
-        res = (0, rows, cols) if out_dev is not None else np.zeros((0, rows, cols), dtype=dt)
-        return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
-    if out_dev is not None and n * rows * cols * dt.itemsize > out_dev.nbytes:
-        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
+        return _no_rasters((0, rows, cols), dt, out_dev, raise_errors)
     L = _ffi.lib()
-    blob = b"".join(bytes(f) for f in frames) or b"\0"
-    offs = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(f) for f in frames], out=offs[1:])
-    status = np.zeros(n, dtype=np.uint32)
-    if out_dev is not None:
-        rc = L.cct_dicom_rle_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, out_dev.ptr, 1,
-                                          out_dev.nbytes // dt.itemsize, status.ctypes.data)
-        res = (n, rows, cols)
-    else:
-        res = np.empty((n, rows, cols), dtype=dt)
-        rc = L.cct_dicom_rle_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, res.ctypes.data, 0, res.size,
-                                          status.ctypes.data)
-    if raise_errors or rc != _ffi.E_STREAM:
-        _ffi.check(rc)
-    return res if raise_errors else (res, status)
+    blob, offs = _archive(frames)
+    return _decode_rasters(lambda *to: L.cct_dicom_rle_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, *to), n, rows,
+                           cols, dt, out_dev, raise_errors, (_ffi.E_STREAM,))
 
 
 def dicom_encapsulate(frames):
     """Encapsulated PixelData of a list of frames (PS3.5 A.4): the Basic Offset Table item with one uint32 offset per frame,
     one item per frame (each frame in exactly one fragment, padded to even length), the sequence delimiter.  Host only."""
-    if isinstance(frames, (bytes, bytearray, memoryview, str)):
-        raise TypeError("dicom_encapsulate takes a list of bytes objects, one per frame")
     items, offsets = bytearray(), []
-    for f in frames:
-        if not isinstance(f, (bytes, bytearray, memoryview)):
-            raise TypeError(f"a frame is a bytes object, got {type(f).__name__}")
+    for f in _file_list(frames, "dicom_encapsulate", "frame", "a frame"):
         f = bytes(f)
         if len(f) & 1:
             f += b"\0"
@@ -824,36 +807,12 @@ def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=Non
     bits a sample doubled by byte stuffing, about 7.75 bytes a sample (2 MB for 512 x 512, 520 MB for 256 such frames;
     pages a file does not reach are never touched), and on the device that plus 4 bytes a sample, at most 512 MB at a time:
     split a large batch if the address space matters."""
-    if isinstance(images, DeviceBuffer):
-        if shape is None:
-            raise ValueError("jpeg_lossless_encode_batch of a DeviceBuffer needs shape=(n, rows, cols) or (rows, cols)")
-        dt = np.dtype(np.uint16 if dtype is None else dtype)
-        shape = tuple(int(x) for x in shape)
-        if len(shape) == 2:
-            shape = (1,) + shape
-        if len(shape) != 3:
-            raise ValueError(f"frame batch shape {shape}: (n, rows, cols) or (rows, cols)")
-        n, rows, cols = shape
-        ptr, on_device, keep = images.ptr, 1, images
-    else:
-        if shape is not None or dtype is not None:
-            raise ValueError("shape= and dtype= describe a DeviceBuffer; an array carries its own")
-        arr = np.asarray(images)
-        dt = arr.dtype
-        if arr.ndim == 2:
-            arr = arr[None]
-        if arr.ndim != 3:
-            raise ValueError(f"frame batch of shape {arr.shape}: (n, rows, cols) or (rows, cols) expected")
-        n, rows, cols = arr.shape
+    src, shape, dt = _raster_batch(images, shape, dtype, "jpeg_lossless_encode_batch", "frame")
+    n, rows, cols = shape
     if dt != np.uint8 and dt != np.uint16:
         raise TypeError(f"JPEG Lossless frames take uint8 or uint16 samples, got {dt}")
     src_bits = 8 * dt.itemsize
-    if precision is None:
-        precision = src_bits
-    for name, x in (("precision", precision), ("restart_rows", restart_rows)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise TypeError(f"{name} must be an integer, got {x!r}")
-    precision, restart_rows = int(precision), int(restart_rows)
+    precision, restart_rows = _ints(precision=src_bits if precision is None else precision, restart_rows=restart_rows)
     if not 2 <= precision <= 16:
         raise ValueError(f"JPEG Lossless precision {precision}: 2 to 16")
     if precision > src_bits:
@@ -865,21 +824,15 @@ def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=Non
     _check_jpl_shape(rows, cols)
     if restart_rows * cols > 65535:
         raise ValueError(f"a restart interval of {restart_rows} rows of {cols} samples: Ri is at most 65535")
-    if isinstance(images, DeviceBuffer):
-        if n < 0 or n * rows * cols * dt.itemsize > images.nbytes:
-            raise ValueError(f"frame batch shape {shape} of {dt} does not fit the {images.nbytes}-byte DeviceBuffer")
-    else:
-        arr = np.ascontiguousarray(arr)
-        ptr, on_device, keep = arr.ctypes.data, 0, arr
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"frame batch shape {shape} of {dt}")
     L = _ffi.lib()
     out_stride = L.cct_jpegll_bound(rows, cols, restart_rows)
-    out = np.empty((n, out_stride), dtype=np.uint8)
-    sizes = np.zeros(n, dtype=np.uint32)
+    out, sizes = _files_out(n, out_stride)
     status = np.zeros(n, dtype=np.uint32)
     _ffi.check(L.cct_jpegll_encode_batch(ptr, on_device, n, rows, cols, src_bits, precision, restart_rows, out.ctypes.data,
                                          out_stride, sizes.ctypes.data, status.ctypes.data))
     del keep
-    return [out[i, : sizes[i]].tobytes() for i in range(n)]
+    return _files_of(out, sizes)
 
 
 def jpeg_lossless_info(file):
@@ -901,40 +854,16 @@ def jpeg_lossless_decode_batch(files, rows, cols, bits=16, out_dev=None, raise_e
     shape, status) with status[i] 0, CCT_E_JPEG (13: the structure), CCT_E_MIXED (10: not rows x cols, or a precision above
     bits) or CCT_E_STREAM (4: the entropy-coded data); include/compact_hip.h lists the cases.  The raster of a refused file
     is unspecified.  Arguments are checked before any device call."""
-    for name, x in (("rows", rows), ("cols", cols), ("bits", bits)):
-        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-            raise TypeError(f"{name} must be an integer, got {x!r}")
-    rows, cols, bits = int(rows), int(cols), int(bits)
+    rows, cols, bits = _ints(rows=rows, cols=cols, bits=bits)
     if bits not in (8, 16):
         raise ValueError(f"JPEG Lossless rasters of {bits} bits allocated: 8 or 16")
     _check_jpl_shape(rows, cols)
-    if isinstance(files, (bytes, bytearray, memoryview, str)):
-        raise TypeError("jpeg_lossless_decode_batch takes a list of bytes objects, one per file")
-    files = list(files)
-    for f in files:
-        if not isinstance(f, (bytes, bytearray, memoryview)):
-            raise TypeError(f"a JPEG file is a bytes object, got {type(f).__name__}")
-    if out_dev is not None and not isinstance(out_dev, DeviceBuffer):
-        raise TypeError(f"out_dev must be a DeviceBuffer, got {type(out_dev).__name__}")
+    files = _file_list(files, "jpeg_lossless_decode_batch", "file", "a JPEG file")
+    _check_out_dev(out_dev)
     n, dt = len(files), np.dtype(np.uint8 if bits == 8 else np.uint16)
     if n == 0:
-        res = (0, rows, cols) if out_dev is not None else np.zeros((0, rows, cols), dtype=dt)
-        return res if raise_errors else (res, np.zeros(0, dtype=np.uint32))
-    if out_dev is not None and n * rows * cols * dt.itemsize > out_dev.nbytes:
-        raise ValueError(f"{n} rasters of {rows} x {cols} do not fit the {out_dev.nbytes}-byte DeviceBuffer")
+        return _no_rasters((0, rows, cols), dt, out_dev, raise_errors)
     L = _ffi.lib()
-    blob = b"".join(bytes(f) for f in files) or b"\0"
-    offs = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum([len(f) for f in files], out=offs[1:])
-    status = np.zeros(n, dtype=np.uint32)
-    if out_dev is not None:
-        rc = L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, out_dev.ptr, 1,
-                                       out_dev.nbytes // dt.itemsize, status.ctypes.data)
-        res = (n, rows, cols)
-    else:
-        res = np.empty((n, rows, cols), dtype=dt)
-        rc = L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, res.ctypes.data, 0, res.size,
-                                       status.ctypes.data)
-    if raise_errors or rc not in (_ffi.E_JPEG, _ffi.E_MIXED, _ffi.E_STREAM):
-        _ffi.check(rc)
-    return res if raise_errors else (res, status)
+    blob, offs = _archive(files)
+    return _decode_rasters(lambda *to: L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, *to), n, rows,
+                           cols, dt, out_dev, raise_errors, (_ffi.E_JPEG, _ffi.E_MIXED, _ffi.E_STREAM))

@@ -97,6 +97,7 @@ struct EncSlot {
 	hipEvent_t ev_small[2] = {nullptr, nullptr};                                // sizes and status have reached the host
 	hipStream_t stream_side = nullptr;                                          // side branch of the DEFLATE pass (launch_deflate)
 	hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr};
+	EventPair ev_zlib;  // around the DEFLATE pass of cct_zlib_compress_batch*
 	unsigned call_parity = 0;
 	DevBuf *all_bufs[48];
 	int n_bufs = 0;
@@ -228,15 +229,6 @@ int default_device()
 	const char *lr = getenv("LOCAL_RANK");
 	return lr ? atoi(lr) : 0;
 }
-
-// Asynchronous copies that target locals (std::vector on the stack frame) or caller memory must have landed before an
-// error return unwinds the frame: declare one of these AFTER those locals; it drains the stream unless disarmed.
-struct DrainOnExit {
-	hipStream_t s; bool armed = true;
-	explicit DrainOnExit(hipStream_t st) : s(st) {}
-	~DrainOnExit() { if (armed) (void)hipStreamSynchronize(s); }
-	void disarm() { armed = false; }
-};
 
 }  // namespace
 
@@ -930,6 +922,7 @@ int cct_shutdown(void)
 		                    E.ev_small[0], E.ev_small[1], E.ev_pack[0], E.ev_pack[1], E.ev_copied[0], E.ev_copied[1],
 		                    E.ev_fork[0], E.ev_fork[1], E.ev_fork[2], E.ev_fork[3]};
 		for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+		E.ev_zlib.release();
 		if (E.stream_copy) (void)hipStreamDestroy(E.stream_copy);
 		if (E.stream_side) { (void)hipStreamSynchronize(E.stream_side); (void)hipStreamDestroy(E.stream_side); }
 		if (k > 0 && E.stream) (void)hipStreamDestroy(E.stream);
@@ -1417,7 +1410,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 	if (h_stats)
 		HIP_TRY(hipMemcpyAsync(qa ? l_stats : h_stats, E.e_stats.p, (size_t)n * sizeof(cct_slice_stats), hipMemcpyDeviceToHost, E.stream));
 	std::vector<uint32_t> psz(n);
-	DrainOnExit drain(E.stream);  // until the first synchronisation below
+	StreamDrain drain(E.stream);  // until the first synchronisation below
 	HIP_TRY(hipMemcpyAsync(qa ? l_psz : psz.data(), E.e_sizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
 	HIP_TRY(hipMemcpyAsync(qa ? l_status : h_status, E.e_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
 	// With DEFLATE on the device and the whole batch in one pass the host does not need sizes or status before
@@ -1588,7 +1581,7 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 	if ((rc = E.z_in.ensure((size_t)n * in_stride))) return rc;
 	if ((rc = E.z_insizes.ensure((size_t)n * 4))) return rc;
 	std::vector<uint32_t> isz(n), osz(n);
-	DrainOnExit drain(E.stream);
+	StreamDrain drain(E.stream);
 	HIP_TRY(hipMemsetAsync(E.z_in.p, 0, (size_t)n * in_stride, E.stream));
 	for (int i = 0; i < n; i++) {
 		isz[i] = (uint32_t)(h_offsets[i + 1] - h_offsets[i]);
@@ -1598,27 +1591,18 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 	}
 	HIP_TRY(hipMemcpyAsync(E.z_insizes.p, isz.data(), (size_t)n * 4, hipMemcpyHostToDevice, E.stream));
 	uint8_t hdr13[13] = {0};
-	struct Events {  // the DEFLATE pass alone, for cct_last_timings
-		hipEvent_t e[2] = {nullptr, nullptr};
-		~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-	} ev;
-	HIP_TRY(hipEventCreate(&ev.e[0]));
-	HIP_TRY(hipEventCreate(&ev.e[1]));
-	HIP_TRY(hipEventRecord(ev.e[0], E.stream));
+	if ((rc = E.ev_zlib.begin(E.stream))) return rc;  // the DEFLATE pass alone, for cct_last_timings
 	rc = deflate_locked(E, (const uint8_t *)E.z_in.p, in_stride, (const uint32_t *)E.z_insizes.p, n, hdr13, zstride, level, strategy,
 	                    mem_level);
 	if (rc) return rc;
-	HIP_TRY(hipEventRecord(ev.e[1], E.stream));
+	if ((rc = E.ev_zlib.end(E.stream))) return rc;
 	HIP_TRY(hipMemcpyAsync(osz.data(), E.z_outsizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
 	HIP_TRY(hipStreamSynchronize(E.stream));
-	HIP_TRY(hipEventElapsedTime(&tl_deflate_ms, ev.e[0], ev.e[1]));
-	for (int i = 0; i < n; i++) {
-		h_out_sizes[i] = osz[i] - 13;
-		HIP_TRY(hipMemcpyAsync(h_out + (size_t)i * out_stride, (uint8_t *)E.z_out.p + (size_t)i * zstride + 13, osz[i] - 13,
-		                       hipMemcpyDeviceToHost, E.stream));
-	}
-	HIP_TRY(hipStreamSynchronize(E.stream));
-	return CCT_OK;
+	float ms = 0;
+	if ((rc = E.ev_zlib.add_ms(ms))) return rc;
+	tl_deflate_ms = ms;
+	for (int i = 0; i < n; i++) h_out_sizes[i] = osz[i] - 13;
+	return files_to_host(h_out, out_stride, h_out_sizes, n, E.z_out.p, zstride, 13, zstride - 13, "stream", 0, "bound", E.stream);
 }
 
 int cct_zlib_compress_batch(const uint8_t *h_in, const uint64_t *h_offsets, int n, uint8_t *h_out, size_t out_stride,
@@ -1748,7 +1732,6 @@ static int png_encode_impl(const void *images, int images_on_device, int n, int 
 	const size_t pstride = png_file_bytes(zstride - 13, chunk);
 	const uint32_t max_chunks = (uint32_t)((zstride - 13 + chunk - 1) / chunk);
 	const int per_pass = (int)std::max<size_t>(1, DEFLATE_PASS_BYTES / in_stride);
-	const bool host_img = !images_on_device;
 	PngPackArgs pk{};
 	pk.chunk = chunk;
 	{  // IHDR: width, height, depth, color type 0 (grayscale), compression 0, filter 0, interlace 0
@@ -1762,7 +1745,7 @@ static int png_encode_impl(const void *images, int images_on_device, int n, int 
 		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), h + 4, 17);
 		h[21] = (uint8_t)(crc >> 24); h[22] = (uint8_t)(crc >> 16); h[23] = (uint8_t)(crc >> 8); h[24] = (uint8_t)crc;
 	}
-	DrainOnExit drain(E.stream);
+	StreamDrain drain(E.stream);
 	std::vector<uint32_t> sizes;
 	std::vector<uint8_t> host_rows, host_z;
 	for (int c0 = 0; c0 < n; c0 += per_pass) {
@@ -1771,12 +1754,8 @@ static int png_encode_impl(const void *images, int images_on_device, int n, int 
 		if ((rc = E.z_insizes.ensure((size_t)nc * 4))) return rc;
 		if ((rc = E.png_out.ensure((size_t)nc * pstride))) return rc;
 		if ((rc = E.png_sizes.ensure((size_t)nc * 4))) return rc;
-		const void *d_img = (const uint8_t *)images + (size_t)c0 * img_bytes;
-		if (host_img) {
-			if ((rc = E.png_img.ensure((size_t)nc * img_bytes))) return rc;
-			HIP_TRY(hipMemcpyAsync(E.png_img.p, d_img, (size_t)nc * img_bytes, hipMemcpyHostToDevice, E.stream));
-			d_img = E.png_img.p;
-		}
+		const void *d_img;
+		if ((rc = rasters_to_device(images, images_on_device, c0, nc, img_bytes, E.png_img, E.stream, &d_img))) return rc;
 		sizes.assign((size_t)nc, (uint32_t)F);
 		HIP_TRY(hipMemcpyAsync(E.z_insizes.p, sizes.data(), (size_t)nc * 4, hipMemcpyHostToDevice, E.stream));
 		if (fmt.depth == 16)
@@ -1816,41 +1795,50 @@ static int png_encode_impl(const void *images, int images_on_device, int n, int 
 		HIP_TRY(launch_png_pack(pk, nc, max_chunks, E.stream));
 		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, E.png_sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, E.stream));
 		HIP_TRY(hipStreamSynchronize(E.stream));
-		for (int i = 0; i < nc; i++) {
-			if (h_out_sizes[c0 + i] > pstride) return fail(CCT_E_DEVICE, "PNG %d: size %u beyond its stride", c0 + i, h_out_sizes[c0 + i]);
-			HIP_TRY(hipMemcpyAsync(h_out + (size_t)(c0 + i) * out_stride, (uint8_t *)E.png_out.p + (size_t)i * pstride,
-			                       h_out_sizes[c0 + i], hipMemcpyDeviceToHost, E.stream));
-		}
-		HIP_TRY(hipStreamSynchronize(E.stream));
+		if ((rc = files_to_host(h_out + (size_t)c0 * out_stride, out_stride, h_out_sizes + c0, nc, E.png_out.p, pstride, 0, pstride, "PNG", c0,
+		                        "stride", E.stream)))
+			return rc;
 	}
 	return CCT_OK;
 }
 
-// take a free decode slot (see DecSlot)
-static DecSlot &acquire_decode_slot(std::unique_lock<std::mutex> &lk)
+// launch_inflate's arguments: streams in `in` at the offsets of D.d_archoffs, each `skip` bytes in; the outputs are the slot's
+static InflateArgs inflate_args(DecSlot &D, const DevBuf &in, size_t in_total, uint32_t skip, size_t out_stride)
 {
-	const int nslots = std::max(1, std::min(g_ctx.dec_slots, N_DEC_SLOTS));
-	for (;;) {
-		for (int k = 0; k < nslots; k++) {
-			std::unique_lock<std::mutex> t(g_mu_dec[k], std::try_to_lock);
-			if (t.owns_lock()) { lk = std::move(t); return g_dec[k]; }
-		}
-		std::this_thread::sleep_for(std::chrono::microseconds(50));
-	}
+	InflateArgs ia{};
+	ia.in = (const uint8_t *)in.p; ia.in_total = in_total;
+	ia.offsets = (const uint64_t *)D.d_archoffs.p; ia.skip = skip;
+	ia.out = (uint8_t *)D.d_payload.p; ia.out_stride = out_stride;
+	ia.out_sizes = (uint32_t *)D.d_sizes.p; ia.status = (uint32_t *)D.d_zstatus.p;
+	return ia;
 }
+
+// The INFLATE kernel reads ahead of a stream's end: the last 48 bytes of the padded archive (pad + 16 bytes) are zero
+static hipError_t zero_read_ahead(void *arch, size_t pad, hipStream_t st) { return hipMemsetAsync((uint8_t *)arch + (pad > 32 ? pad - 32 : 0), 0, pad > 32 ? 48 : pad + 16, st); }
 
 }  // extern "C"
 
+// On the first call of a process the device is bound BEFORE the slot and the shared lock are taken.  A thread must never wait
+// for g_mu while it counts as a call in flight: a first encode holds g_mu through HIP initialisation and then asks
+// for an exclusive section, which waits for every call in flight to leave.  Then the slot, the ApiCall, the thread's device.
 int cct::lease_decode_slot(DecLease &l)
 {
-	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device before slot and shared lock (cct_zlib_decompress_batch)
+	if (!(g_ctx.ready && g_ctx.pid == getpid())) {
 		std::lock_guard<std::mutex> lk(g_mu);
-		int rc0 = ensure_ctx();
-		if (rc0) return rc0;
+		if (int rc = ensure_ctx()) return rc;
 	}
-	DecSlot &D = acquire_decode_slot(l.lk);
-	l.stream = D.stream;
-	l.slot = (int)(&D - g_dec);
+	const int nslots = std::max(1, std::min(g_ctx.dec_slots, N_DEC_SLOTS));
+	for (;;) {  // wait for a free decode slot (see DecSlot)
+		for (int k = 0; k < nslots && !l.lk.owns_lock(); k++) {
+			l.lk = std::unique_lock<std::mutex>(g_mu_dec[k], std::try_to_lock);
+			l.slot = k;
+		}
+		if (l.lk.owns_lock()) break;
+		std::this_thread::sleep_for(std::chrono::microseconds(50));
+	}
+	l.in_call.emplace();
+	l.stream = g_dec[l.slot].stream;
+	HIP_TRY(hipSetDevice(g_ctx.device));
 	return CCT_OK;
 }
 
@@ -1863,20 +1851,10 @@ int cct_zlib_decompress_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 {
 	if (n < 0) return fail(CCT_E_ARG, "negative batch size");
 	if (out_stride == 0 || (out_stride & 15)) return fail(CCT_E_ARG, "out_stride must be a positive multiple of 16");
-	// first use in this process: bind the device BEFORE the slot and the shared lock are taken.  A thread must never wait
-	// for g_mu while it counts as a call in flight: a first encode holds g_mu through HIP initialisation and then asks
-	// for an exclusive section, which waits for every call in flight to leave
-	if (!(g_ctx.ready && g_ctx.pid == getpid())) {
-		std::lock_guard<std::mutex> lk(g_mu);
-		int rc0 = ensure_ctx();
-		if (rc0) return rc0;
-	}
-	std::unique_lock<std::mutex> lkd;
-	DecSlot &D = acquire_decode_slot(lkd);
-	ApiCall in_call;
-	if (n == 0) return CCT_OK;
-	int rc;
-	HIP_TRY(hipSetDevice(g_ctx.device));
+	DecLease lease;
+	int rc = lease_decode_slot(lease);
+	if (rc || n == 0) return rc;
+	DecSlot &D = g_dec[lease.slot];
 	const uint64_t a0 = h_offsets[0], a1 = h_offsets[n];
 	const size_t abytes = (size_t)(a1 - a0), apad = (abytes + 31) & ~(size_t)15;
 	if ((rc = D.d_arch.ensure(apad + 16))) return rc;
@@ -1888,16 +1866,11 @@ int cct_zlib_decompress_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 	std::vector<uint32_t> zst(n), osz(n);
 	for (int i = 0; i <= n; i++) rel[i] = h_offsets[i] - a0;
 	hipStream_t st = D.stream;
-	DrainOnExit drain(st);
-	HIP_TRY(hipMemsetAsync((uint8_t *)D.d_arch.p + (apad > 32 ? apad - 32 : 0), 0, apad > 32 ? 48 : apad + 16, st));
+	StreamDrain drain(st);
+	HIP_TRY(zero_read_ahead(D.d_arch.p, apad, st));
 	if (abytes) HIP_TRY(hipMemcpyAsync(D.d_arch.p, h_in + a0, abytes, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(D.d_archoffs.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-	InflateArgs ia{};
-	ia.in = (const uint8_t *)D.d_arch.p; ia.in_total = apad;
-	ia.offsets = (const uint64_t *)D.d_archoffs.p; ia.skip = 0;
-	ia.out = (uint8_t *)D.d_payload.p; ia.out_stride = out_stride;
-	ia.out_sizes = (uint32_t *)D.d_sizes.p; ia.status = (uint32_t *)D.d_zstatus.p;
-	HIP_TRY(launch_inflate(ia, n, st, inflate_lanes_now()));
+	HIP_TRY(launch_inflate(inflate_args(D, D.d_arch, apad, 0, out_stride), n, st, inflate_lanes_now()));
 	HIP_TRY(hipMemcpyAsync(zst.data(), D.d_zstatus.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(osz.data(), D.d_sizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -1905,16 +1878,13 @@ int cct_zlib_decompress_batch(const uint8_t *h_in, const uint64_t *h_offsets, in
 	for (int i = 0; i < n; i++) {
 		h_status[i] = (zst[i] & CCT_ST_ZLIB) ? CCT_E_ZLIB : (zst[i] & CCT_ST_STREAM) ? CCT_E_CAP : CCT_OK;
 		h_out_sizes[i] = h_status[i] == CCT_OK ? osz[i] : 0;
-		if (h_status[i] == CCT_OK && osz[i])
-			HIP_TRY(hipMemcpyAsync(h_out + (size_t)i * out_stride, (uint8_t *)D.d_payload.p + (size_t)i * out_stride, osz[i],
-			                       hipMemcpyDeviceToHost, st));
 		if (h_status[i] != CCT_OK && first == CCT_OK) {
 			first = (int)h_status[i];
 			fail(first, "stream %d: %s", i, first == CCT_E_ZLIB ? "invalid DEFLATE stream" : "output larger than out_stride");
 		}
 	}
-	HIP_TRY(hipStreamSynchronize(st));
-	return first;
+	rc = files_to_host(h_out, out_stride, h_out_sizes, n, D.d_payload.p, out_stride, 0, out_stride, "stream", 0, "stride", st);  // a refused stream has size 0
+	return rc ? rc : first;
 }
 
 // ---- PNG reader (png_read_kernels.hip) ---------------------------------------------------------------
@@ -2024,8 +1994,8 @@ static int png_read_pass(DecSlot &D, const uint8_t *h_files, const uint64_t *h_o
                          int shift, uint16_t *d_img, uint32_t *h_status, float ms[3])
 {
 	int rc;
+	if ((rc = check_offsets(h_offsets + c0, nc, "file"))) return rc;
 	const uint64_t a0 = h_offsets[c0], a1 = h_offsets[c0 + nc];
-	if (a1 < a0) return fail(CCT_E_ARG, "file offsets must not decrease");
 	std::vector<PngChunk> tab;
 	std::vector<uint64_t> zoffs((size_t)nc + 1, 0);
 	std::vector<uint32_t> fst((size_t)nc, 0), zst((size_t)nc, 0), osz((size_t)nc, 0);
@@ -2034,7 +2004,6 @@ static int png_read_pass(DecSlot &D, const uint8_t *h_files, const uint64_t *h_o
 	int max_bpp = 0;
 	for (int i = 0; i < nc; i++) {
 		const uint64_t f0 = h_offsets[c0 + i], f1 = h_offsets[c0 + i + 1];
-		if (f1 < f0) return fail(CCT_E_ARG, "file offsets must not decrease");
 		int depth = 16;
 		h_status[i] = (uint32_t)png_walk_file(h_files + f0, (size_t)(f1 - f0), f0 - a0, (uint32_t)i, rows, cols, &depth, tab, &zoff);
 		zoffs[(size_t)i + 1] = zoff;
@@ -2055,25 +2024,20 @@ static int png_read_pass(DecSlot &D, const uint8_t *h_files, const uint64_t *h_o
 	if ((rc = D.d_sizes.ensure((size_t)nc * 4))) return rc;
 	if ((rc = D.d_payload.ensure((size_t)nc * stride))) return rc;
 	hipStream_t st = D.stream;
-	DrainOnExit drain(st);
+	StreamDrain drain(st);
 	HIP_TRY(hipMemcpyAsync(D.d_arch.p, h_files + a0, abytes, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(D.d_png_tab.p, tab.data(), tab.size() * sizeof(PngChunk), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(D.d_png_bpp.p, bpp.data(), (size_t)nc, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(D.d_archoffs.p, zoffs.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(D.d_status.p, fst.data(), (size_t)nc * 4, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync((uint8_t *)D.d_png_z.p + (zpad > 32 ? zpad - 32 : 0), 0, zpad > 32 ? 48 : zpad + 16, st));  // the INFLATE kernel reads ahead
+	HIP_TRY(zero_read_ahead(D.d_png_z.p, zpad, st));
 	PngUnpackArgs ua{};
 	ua.files = (const uint8_t *)D.d_arch.p; ua.chunks = (const PngChunk *)D.d_png_tab.p;
 	ua.streams = (uint8_t *)D.d_png_z.p; ua.status = (uint32_t *)D.d_status.p;
 	HIP_TRY(hipEventRecord(D.ev_d0, st));
 	HIP_TRY(launch_png_unpack(ua, (uint32_t)tab.size(), st));
 	HIP_TRY(hipEventRecord(D.ev_d1, st));
-	InflateArgs ia{};
-	ia.in = (const uint8_t *)D.d_png_z.p; ia.in_total = zpad;
-	ia.offsets = (const uint64_t *)D.d_archoffs.p; ia.skip = 0;
-	ia.out = (uint8_t *)D.d_payload.p; ia.out_stride = stride;
-	ia.out_sizes = (uint32_t *)D.d_sizes.p; ia.status = (uint32_t *)D.d_zstatus.p;
-	HIP_TRY(launch_inflate(ia, nc, st, inflate_lanes_now()));
+	HIP_TRY(launch_inflate(inflate_args(D, D.d_png_z, zpad, 0, stride), nc, st, inflate_lanes_now()));
 	HIP_TRY(hipEventRecord(D.ev_k_dec0, st));
 	PngUnfilterArgs fa{};
 	fa.rows = (uint8_t *)D.d_payload.p; fa.rows_stride = stride;
@@ -2115,16 +2079,10 @@ int cct_png_read_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n,
 	const size_t N = (size_t)rows * cols;
 	if (images_cap_px / N < (size_t)n) return fail(CCT_E_CAP, "output holds %zu pixels, need %zu", images_cap_px, (size_t)n * N);
 	if (n == 0) return CCT_OK;
-	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device before slot and shared lock (cct_zlib_decompress_batch)
-		std::lock_guard<std::mutex> lk(g_mu);
-		int rc0 = ensure_ctx();
-		if (rc0) return rc0;
-	}
-	std::unique_lock<std::mutex> lkd;
-	DecSlot &D = acquire_decode_slot(lkd);
-	ApiCall in_call;
-	int rc;
-	HIP_TRY(hipSetDevice(g_ctx.device));
+	DecLease lease;
+	int rc = lease_decode_slot(lease);
+	if (rc) return rc;
+	DecSlot &D = g_dec[lease.slot];
 	// a pass holds the inflated rows of its files: at most DEFLATE_PASS_BYTES of them, as the writer's passes do
 	const size_t stride16 = ((png_filtered_bytes(rows, cols) + 15) & ~(size_t)15) + 16;
 	const int per_pass = (int)std::max<size_t>(1, DEFLATE_PASS_BYTES / stride16);
@@ -2178,17 +2136,12 @@ int cct_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, i
 {
 	if (n < 0) return fail(CCT_E_ARG, "negative batch size");
 	if (n == 0) return CCT_OK;
-	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device before slot and shared lock (see above)
-		std::lock_guard<std::mutex> lk(g_mu);
-		int rc0 = ensure_ctx();
-		if (rc0) return rc0;
-	}
-	std::unique_lock<std::mutex> lkd;
-	DecSlot &D = acquire_decode_slot(lkd);
-	ApiCall in_call;
-	cct_header h0;
-	int rc = cct_read_header(h_files + h_offsets[0], (size_t)(h_offsets[1] - h_offsets[0]), magic, &h0);
+	DecLease lease;
+	int rc = lease_decode_slot(lease);
 	if (rc) return rc;
+	DecSlot &D = g_dec[lease.slot];
+	cct_header h0;
+	if ((rc = cct_read_header(h_files + h_offsets[0], (size_t)(h_offsets[1] - h_offsets[0]), magic, &h0))) return rc;
 	for (int i = 1; i < n; i++) {
 		cct_header h;
 		if ((rc = cct_read_header(h_files + h_offsets[i], (size_t)(h_offsets[i + 1] - h_offsets[i]), magic, &h))) return rc;
@@ -2198,7 +2151,7 @@ int cct_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, i
 	if (h0.width == 0 || h0.height == 0) return fail(CCT_E_SHAPE, "empty image");
 	if ((rc = check_shape(n, h0.width, h0.height, block_size))) return rc;
 	const size_t N = (size_t)h0.width * h0.height;
-	if (images_cap_px < (size_t)n * N) return fail(CCT_E_CAP, "output holds %zu pixels, need %zu", images_cap_px, (size_t)n * N);
+	if (images_cap_px / N < (size_t)n) return fail(CCT_E_CAP, "output holds %zu pixels, need %zu", images_cap_px, (size_t)n * N);
 	const size_t stride = cct_payload_stride(h0.width, h0.height, block_size);
 	int zthreads = 1;
 	{  // the slot's own buffers; no device lock, encodes and the other decode slot may be in flight
@@ -2216,7 +2169,7 @@ int cct_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, i
 	const bool dev_inflate = h0.deflate && g_ctx.device_inflate;
 	std::vector<uint32_t> dst(n), zst(n, 0);
 	std::vector<uint64_t> rel(dev_inflate ? n + 1 : 0);
-	DrainOnExit drain(D.stream);  // copies into the vectors above / the caller's images must land before any return
+	StreamDrain drain(D.stream);  // copies into the vectors above / the caller's images must land before any return
 	if (dev_inflate) {
 		// INFLATE on the device (inflate_kernels.hip): the archive goes up as it is, payloads never touch the host
 		const uint64_t a0 = h_offsets[0], a1 = h_offsets[n];
@@ -2230,11 +2183,7 @@ int cct_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, i
 		const double t_inf0 = now_ms();
 		HIP_TRY(hipMemcpyAsync(D.d_arch.p, h_files + a0, abytes, hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemcpyAsync(D.d_archoffs.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-		InflateArgs ia{};
-		ia.in = (const uint8_t *)D.d_arch.p; ia.in_total = apad;
-		ia.offsets = (const uint64_t *)D.d_archoffs.p; ia.skip = 13;
-		ia.out = (uint8_t *)D.d_payload.p; ia.out_stride = stride;
-		ia.out_sizes = (uint32_t *)D.d_sizes.p; ia.status = (uint32_t *)D.d_zstatus.p;
+		const InflateArgs ia = inflate_args(D, D.d_arch, apad, 13, stride);
 		// A decode issued while an encode batch is on the device is part of a pipeline (the bench: the decode of step k next to
 		// the encode of step k+1, with slack): its kernels are released when the next transform+pack stage has ended, so that
 		// they run next to that batch's sort and match kernels and not next to a tree or transform+pack kernel

@@ -1,7 +1,7 @@
 // DICOM RLE Lossless frames behind the C ABI: host side of dicom_rle_kernels.hip.  Encode takes the encode slot (g_mu, the
-// main stream) like the PNG writer, decode a decode slot like the PNG reader; the workspaces are this file's own, one set
-// for the encode slot and one per decode slot.  The host parses the 64-byte frame headers, as the PNG reader's host walks
-// the chunk heads; everything behind the header is the device's.
+// main stream), decode a decode slot (lease_decode_slot); passes, copies and timing are the scaffold of host.h.  The
+// workspaces are this file's own, one for the encode slot and one per decode slot.  The host parses the 64-byte frame
+// headers; everything behind the header is the device's.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -17,15 +17,10 @@ namespace {
 constexpr size_t RLE_MAX_PIXELS = (size_t)1 << 26;   // rows * cols: a 16-bit frame of that many stays below 2^28 + 64 bytes
 constexpr size_t RLE_PASS_BYTES = (size_t)512 << 20;  // frames on the device at a time (one frame at least)
 
-struct EncWs { DevBuf img, rowinfo, out, sizes; hipEvent_t ev0 = nullptr, ev1 = nullptr; } g_enc_ws;  // under g_mu
-struct DecWs { DevBuf frames, segs, table, tinfo, short_seg, img; hipEvent_t ev0 = nullptr, ev1 = nullptr; } g_dec_ws[DEC_SLOTS];  // under the slot's lock
-
-int ensure_events(hipEvent_t &a, hipEvent_t &b)
-{
-	if (!a) HIP_TRY(hipEventCreate(&a));
-	if (!b) HIP_TRY(hipEventCreate(&b));
-	return CCT_OK;
-}
+enum { E_IMG, E_ROWINFO, E_OUT, E_SIZES, E_NBUF };
+enum { D_FRAMES, D_SEGS, D_TABLE, D_TINFO, D_SHORT_SEG, D_IMG, D_NBUF };
+Workspace<E_NBUF> g_enc_ws;             // under g_mu
+Workspace<D_NBUF> g_dec_ws[DEC_SLOTS];  // under the slot's lock
 
 int check_shape(int n, int rows, int cols, int bits)
 {
@@ -61,14 +56,8 @@ int parse_frame(const uint8_t *f, size_t len, int nseg, uint32_t seg_off[2], uin
 
 void cct::dicom_rle_release()
 {
-	DevBuf *e[] = {&g_enc_ws.img, &g_enc_ws.rowinfo, &g_enc_ws.out, &g_enc_ws.sizes};
-	for (DevBuf *b : e) b->release();
-	hipEvent_t *ev[] = {&g_enc_ws.ev0, &g_enc_ws.ev1, &g_dec_ws[0].ev0, &g_dec_ws[0].ev1, &g_dec_ws[1].ev0, &g_dec_ws[1].ev1};
-	for (hipEvent_t *x : ev) { if (*x) (void)hipEventDestroy(*x); *x = nullptr; }
-	for (DecWs &w : g_dec_ws) {
-		DevBuf *d[] = {&w.frames, &w.segs, &w.table, &w.tinfo, &w.short_seg, &w.img};
-		for (DevBuf *b : d) b->release();
-	}
+	g_enc_ws.release();
+	for (auto &w : g_dec_ws) w.release();
 }
 
 extern "C" {
@@ -92,38 +81,28 @@ int cct_dicom_rle_encode_batch(const void *images, int images_on_device, int n, 
 	ApiCall in_call;
 	if ((rc = ensure_ctx())) return rc;
 	hipStream_t st = main_stream();
-	EncWs &W = g_enc_ws;
-	if ((rc = ensure_events(W.ev0, W.ev1))) return rc;
+	DevBuf *W = g_enc_ws.buf;
+	EventPair &ev = g_enc_ws.ev;
 	const int planes = bits / 8;
 	const size_t N = (size_t)rows * cols, img_bytes = N * planes, dstride = (bound + 3) & ~(size_t)3;  // the header is written in words
 	const int per_pass = (int)std::max<size_t>(1, RLE_PASS_BYTES / dstride);
 	float ms_sum = 0;
-	struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};  // copies into caller memory land before any return
+	StreamDrain drain(st);  // copies into caller memory land before any return
 	for (int c0 = 0; c0 < n; c0 += per_pass) {
 		const int nc = std::min(per_pass, n - c0);
-		const void *d_img = (const uint8_t *)images + (size_t)c0 * img_bytes;
-		if (!images_on_device) {
-			if ((rc = W.img.ensure((size_t)nc * img_bytes))) return rc;
-			HIP_TRY(hipMemcpyAsync(W.img.p, d_img, (size_t)nc * img_bytes, hipMemcpyHostToDevice, st));
-			d_img = W.img.p;
-		}
-		if ((rc = W.rowinfo.ensure((size_t)nc * planes * rows * 4))) return rc;
-		if ((rc = W.out.ensure((size_t)nc * dstride))) return rc;
-		if ((rc = W.sizes.ensure((size_t)nc * 4))) return rc;
-		HIP_TRY(hipEventRecord(W.ev0, st));
-		HIP_TRY(launch_dicom_rle_encode(d_img, nc, rows, cols, planes, (uint32_t *)W.rowinfo.p, (uint8_t *)W.out.p, dstride, (uint32_t *)W.sizes.p, st));
-		HIP_TRY(hipEventRecord(W.ev1, st));
-		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, W.sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+		const void *d_img;
+		if ((rc = rasters_to_device(images, images_on_device, c0, nc, img_bytes, W[E_IMG], st, &d_img))) return rc;
+		if ((rc = W[E_ROWINFO].ensure((size_t)nc * planes * rows * 4))) return rc;
+		if ((rc = W[E_OUT].ensure((size_t)nc * dstride))) return rc;
+		if ((rc = W[E_SIZES].ensure((size_t)nc * 4))) return rc;
+		if ((rc = ev.begin(st))) return rc;
+		HIP_TRY(launch_dicom_rle_encode(d_img, nc, rows, cols, planes, (uint32_t *)W[E_ROWINFO].p, (uint8_t *)W[E_OUT].p, dstride, (uint32_t *)W[E_SIZES].p, st));
+		if ((rc = ev.end(st))) return rc;
+		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, W[E_SIZES].p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
-		float ms = 0;
-		HIP_TRY(hipEventElapsedTime(&ms, W.ev0, W.ev1));
-		ms_sum += ms;
-		for (int i = 0; i < nc; i++) {
-			if (h_out_sizes[c0 + i] > dstride) return fail(CCT_E_DEVICE, "frame %d: size %u beyond its bound", c0 + i, h_out_sizes[c0 + i]);
-			HIP_TRY(hipMemcpyAsync(h_out + (size_t)(c0 + i) * out_stride, (const uint8_t *)W.out.p + (size_t)i * dstride, h_out_sizes[c0 + i],
-			                       hipMemcpyDeviceToHost, st));
-		}
-		HIP_TRY(hipStreamSynchronize(st));
+		if ((rc = ev.add_ms(ms_sum))) return rc;
+		if ((rc = files_to_host(h_out + (size_t)c0 * out_stride, out_stride, h_out_sizes + c0, nc, W[E_OUT].p, dstride, 0, dstride, "frame", c0, "bound", st)))
+			return rc;
 	}
 	set_last_kernel_ms(true, ms_sum);
 	return CCT_OK;
@@ -137,23 +116,20 @@ int cct_dicom_rle_decode_batch(const uint8_t *h_frames, const uint64_t *h_offset
 	const size_t N = (size_t)rows * cols;
 	if (images_cap_px / N < (size_t)n) return fail(CCT_E_CAP, "output holds %zu pixels, need %zu", images_cap_px, (size_t)n * N);
 	if (n > 0 && (!h_frames || !h_offsets || !images || !h_status)) return fail(CCT_E_ARG, "null argument");
-	for (int i = 0; i < n; i++)
-		if (h_offsets[i + 1] < h_offsets[i]) return fail(CCT_E_ARG, "frame offsets must not decrease");
+	if ((rc = check_offsets(h_offsets, n, "frame"))) return rc;
 	if (n == 0) return CCT_OK;
 	DecLease L;
 	if ((rc = lease_decode_slot(L))) return rc;
-	ApiCall in_call;
-	HIP_TRY(hipSetDevice(bound_device()));
 	hipStream_t st = L.stream;
-	DecWs &W = g_dec_ws[L.slot];
-	if ((rc = ensure_events(W.ev0, W.ev1))) return rc;
+	DevBuf *W = g_dec_ws[L.slot].buf;
+	EventPair &ev = g_dec_ws[L.slot].ev;
 	const int nseg_frame = bits / 8;
 	const size_t px_bytes = (size_t)nseg_frame;
 	float ms_sum = 0;
 	std::vector<RleSegment> segs;
 	std::vector<int> seg_frame;
 	std::vector<uint32_t> short_seg;
-	struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};  // declared after the vectors the copies land in
+	StreamDrain drain(st);  // declared after the vectors the copies land in
 	for (int c0 = 0; c0 < n;) {
 		// a pass: frames c0 .. c1 - 1, RLE_PASS_BYTES of them at most
 		int c1 = c0 + 1;
@@ -180,44 +156,32 @@ int cct_dicom_rle_decode_batch(const uint8_t *h_frames, const uint64_t *h_offset
 			const size_t abytes = (size_t)(a1 - a0), nseg = segs.size();
 			uint8_t *d_img = images_on_device ? (uint8_t *)images + (size_t)c0 * N * px_bytes : nullptr;
 			if (!images_on_device) {
-				if ((rc = W.img.ensure((size_t)(c1 - c0) * N * px_bytes))) return rc;
-				d_img = (uint8_t *)W.img.p;
+				if ((rc = W[D_IMG].ensure((size_t)(c1 - c0) * N * px_bytes))) return rc;
+				d_img = (uint8_t *)W[D_IMG].p;
 			}
-			if ((rc = W.frames.ensure(abytes + 16))) return rc;
-			if ((rc = W.segs.ensure(nseg * sizeof(RleSegment)))) return rc;
-			if ((rc = W.table.ensure((size_t)ntiles * RLE_ENTRIES * 4))) return rc;
-			if ((rc = W.tinfo.ensure((size_t)ntiles * sizeof(uint2)))) return rc;
-			if ((rc = W.short_seg.ensure(nseg * 4))) return rc;
-			HIP_TRY(hipMemcpyAsync(W.frames.p, h_frames + a0, abytes, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(W.segs.p, segs.data(), nseg * sizeof(RleSegment), hipMemcpyHostToDevice, st));
+			if ((rc = W[D_FRAMES].ensure(abytes + 16))) return rc;
+			if ((rc = W[D_SEGS].ensure(nseg * sizeof(RleSegment)))) return rc;
+			if ((rc = W[D_TABLE].ensure((size_t)ntiles * RLE_ENTRIES * 4))) return rc;
+			if ((rc = W[D_TINFO].ensure((size_t)ntiles * sizeof(uint2)))) return rc;
+			if ((rc = W[D_SHORT_SEG].ensure(nseg * 4))) return rc;
+			HIP_TRY(hipMemcpyAsync(W[D_FRAMES].p, h_frames + a0, abytes, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(W[D_SEGS].p, segs.data(), nseg * sizeof(RleSegment), hipMemcpyHostToDevice, st));
 			RleDecodeArgs a{};
-			a.frames = (const uint8_t *)W.frames.p; a.segs = (const RleSegment *)W.segs.p;
+			a.frames = (const uint8_t *)W[D_FRAMES].p; a.segs = (const RleSegment *)W[D_SEGS].p;
 			a.nseg = (uint32_t)nseg; a.ntiles = (uint32_t)ntiles;
 			a.want = (uint32_t)N; a.step = (uint32_t)px_bytes;
-			a.table = (uint32_t *)W.table.p; a.tinfo = (uint2 *)W.tinfo.p; a.short_seg = (uint32_t *)W.short_seg.p;
+			a.table = (uint32_t *)W[D_TABLE].p; a.tinfo = (uint2 *)W[D_TINFO].p; a.short_seg = (uint32_t *)W[D_SHORT_SEG].p;
 			a.images = d_img;
-			HIP_TRY(hipEventRecord(W.ev0, st));
+			if ((rc = ev.begin(st))) return rc;
 			HIP_TRY(launch_dicom_rle_decode(a, st));
-			HIP_TRY(hipEventRecord(W.ev1, st));
+			if ((rc = ev.end(st))) return rc;
 			short_seg.assign(nseg, 0);
-			HIP_TRY(hipMemcpyAsync(short_seg.data(), W.short_seg.p, nseg * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(short_seg.data(), W[D_SHORT_SEG].p, nseg * 4, hipMemcpyDeviceToHost, st));
 			HIP_TRY(hipStreamSynchronize(st));
-			float ms = 0;
-			HIP_TRY(hipEventElapsedTime(&ms, W.ev0, W.ev1));
-			ms_sum += ms;
+			if ((rc = ev.add_ms(ms_sum))) return rc;
 			for (size_t s = 0; s < nseg; s++)
 				if (short_seg[s]) h_status[seg_frame[s]] = CCT_E_STREAM;
-			if (!images_on_device) {  // the good frames, in runs: a refused frame leaves its slot in host memory alone
-				for (int i = c0; i < c1;) {
-					if (h_status[i] != CCT_OK) { i++; continue; }
-					int j = i + 1;
-					while (j < c1 && h_status[j] == CCT_OK) j++;
-					HIP_TRY(hipMemcpyAsync((uint8_t *)images + (size_t)i * N * px_bytes, d_img + (size_t)(i - c0) * N * px_bytes,
-					                       (size_t)(j - i) * N * px_bytes, hipMemcpyDeviceToHost, st));
-					i = j;
-				}
-				HIP_TRY(hipStreamSynchronize(st));
-			}
+			if (!images_on_device && (rc = good_rasters_to_host(images, d_img, N * px_bytes, h_status, c0, c1, st))) return rc;
 		}
 		c0 = c1;
 	}

@@ -1,7 +1,8 @@
 // JPEG Lossless (SOF3) frames behind the C ABI: host side of jpeg_lossless_kernels.hip.  Encode takes the encode slot (g_mu,
-// the main stream) like the RLE codec, decode a decode slot; the workspaces are this file's own, one set for the encode slot
-// and one per decode slot.  The host walks the markers of every file and decides every structural refusal before anything is
-// uploaded; the device sees the entropy-coded segment, the decoding table and the scan parameters.
+// the main stream), decode a decode slot (lease_decode_slot); passes, copies and timing are the scaffold of host.h.  The
+// workspaces are this file's own, one for the encode slot and one per decode slot.  The host walks the markers of every file
+// and decides every structural refusal before anything is uploaded; the device sees the entropy-coded segment, the decoding
+// table and the scan parameters.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -17,15 +18,10 @@ namespace {
 constexpr size_t JPL_MAX_PIXELS = (size_t)1 << 26;
 constexpr size_t JPL_PASS_BYTES = (size_t)512 << 20;  // device bytes of the frames of one pass (one frame at least)
 
-struct EncWs { DevBuf img, hist, codes, bitbuf, ints, out, sizes; hipEvent_t ev0 = nullptr, ev1 = nullptr; } g_enc_ws;  // under g_mu
-struct DecWs { DevBuf files, frames, int_frame, ubuf, istart, sub, diff, status, img; hipEvent_t ev0 = nullptr, ev1 = nullptr; } g_dec_ws[DEC_SLOTS];
-
-int ensure_events(hipEvent_t &a, hipEvent_t &b)
-{
-	if (!a) HIP_TRY(hipEventCreate(&a));
-	if (!b) HIP_TRY(hipEventCreate(&b));
-	return CCT_OK;
-}
+enum { E_IMG, E_HIST, E_CODES, E_BITBUF, E_INTS, E_OUT, E_SIZES, E_NBUF };
+enum { D_FILES, D_FRAMES, D_INT_FRAME, D_UBUF, D_ISTART, D_SUB, D_DIFF, D_STATUS, D_IMG, D_NBUF };
+Workspace<E_NBUF> g_enc_ws;             // under g_mu
+Workspace<D_NBUF> g_dec_ws[DEC_SLOTS];  // under the slot's lock
 
 bool shape_ok(int rows, int cols) { return rows >= 1 && cols >= 1 && rows <= 65535 && cols <= 65535 && (size_t)rows * (size_t)cols <= JPL_MAX_PIXELS; }
 
@@ -126,15 +122,8 @@ const char *refusal(int code)
 
 void cct::jpegll_release()
 {
-	DevBuf *e[] = {&g_enc_ws.img, &g_enc_ws.hist, &g_enc_ws.codes, &g_enc_ws.bitbuf, &g_enc_ws.ints, &g_enc_ws.out, &g_enc_ws.sizes};
-	for (DevBuf *b : e) b->release();
-	auto drop = [](hipEvent_t &x) { if (x) (void)hipEventDestroy(x); x = nullptr; };
-	drop(g_enc_ws.ev0); drop(g_enc_ws.ev1);
-	for (DecWs &w : g_dec_ws) {
-		DevBuf *d[] = {&w.files, &w.frames, &w.int_frame, &w.ubuf, &w.istart, &w.sub, &w.diff, &w.status, &w.img};
-		for (DevBuf *b : d) b->release();
-		drop(w.ev0); drop(w.ev1);
-	}
+	g_enc_ws.release();
+	for (auto &w : g_dec_ws) w.release();
 }
 
 extern "C" {
@@ -177,55 +166,44 @@ int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int
 	ApiCall in_call;
 	if ((rc = ensure_ctx())) return rc;
 	hipStream_t st = main_stream();
-	EncWs &W = g_enc_ws;
-	if ((rc = ensure_events(W.ev0, W.ev1))) return rc;
+	DevBuf *W = g_enc_ws.buf;
+	EventPair &ev = g_enc_ws.ev;
 	const size_t N = (size_t)rows * cols, img_bytes = N * (src_bits / 8), dstride = (bound + 3) & ~(size_t)3;
 	const uint32_t rpi = restart_rows ? (uint32_t)restart_rows : (uint32_t)rows, n_int = ((uint32_t)rows + rpi - 1) / rpi;
 	const int per_pass = (int)std::max<size_t>(1, JPL_PASS_BYTES / (dstride + 4 * N));
 	float ms_sum = 0;
 	std::vector<uint32_t> status;
-	struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};  // copies into caller memory land before any return
+	StreamDrain drain(st);  // copies into caller memory land before any return
 	for (int c0 = 0; c0 < n; c0 += per_pass) {
 		const int nc = std::min(per_pass, n - c0);
-		const void *d_img = (const uint8_t *)images + (size_t)c0 * img_bytes;
-		if (!images_on_device) {
-			if ((rc = W.img.ensure((size_t)nc * img_bytes))) return rc;
-			HIP_TRY(hipMemcpyAsync(W.img.p, d_img, (size_t)nc * img_bytes, hipMemcpyHostToDevice, st));
-			d_img = W.img.p;
-		}
+		const void *d_img;
+		if ((rc = rasters_to_device(images, images_on_device, c0, nc, img_bytes, W[E_IMG], st, &d_img))) return rc;
 		const size_t hist_bytes = (size_t)nc * 18 * 4;  // 17 bins and the status word of every frame
-		if ((rc = W.hist.ensure(hist_bytes))) return rc;
-		if ((rc = W.codes.ensure((size_t)nc * sizeof(JplCode)))) return rc;
-		if ((rc = W.bitbuf.ensure((size_t)nc * N * 4))) return rc;
-		if ((rc = W.ints.ensure((size_t)nc * n_int * 3 * 4))) return rc;
-		if ((rc = W.out.ensure((size_t)nc * dstride))) return rc;
-		if ((rc = W.sizes.ensure((size_t)nc * 4))) return rc;
+		if ((rc = W[E_HIST].ensure(hist_bytes))) return rc;
+		if ((rc = W[E_CODES].ensure((size_t)nc * sizeof(JplCode)))) return rc;
+		if ((rc = W[E_BITBUF].ensure((size_t)nc * N * 4))) return rc;
+		if ((rc = W[E_INTS].ensure((size_t)nc * n_int * 3 * 4))) return rc;
+		if ((rc = W[E_OUT].ensure((size_t)nc * dstride))) return rc;
+		if ((rc = W[E_SIZES].ensure((size_t)nc * 4))) return rc;
 		JplEncArgs a{};
 		a.images = d_img; a.src_bits = (uint32_t)src_bits; a.n = (uint32_t)nc; a.rows = (uint32_t)rows; a.cols = (uint32_t)cols;
 		a.precision = (uint32_t)precision; a.rpi = rpi; a.n_int = n_int; a.restart = restart_rows > 0;
-		a.hist = (uint32_t *)W.hist.p; a.status = a.hist + (size_t)nc * 17;
-		a.codes = (JplCode *)W.codes.p; a.bitbuf = (uint32_t *)W.bitbuf.p;
-		a.ibytes = (uint32_t *)W.ints.p; a.iff = a.ibytes + (size_t)nc * n_int; a.ioff = a.iff + (size_t)nc * n_int;
-		a.out = (uint8_t *)W.out.p; a.out_stride = dstride; a.out_sizes = (uint32_t *)W.sizes.p;
-		HIP_TRY(hipEventRecord(W.ev0, st));
-		HIP_TRY(hipMemsetAsync(W.hist.p, 0, hist_bytes, st));
+		a.hist = (uint32_t *)W[E_HIST].p; a.status = a.hist + (size_t)nc * 17;
+		a.codes = (JplCode *)W[E_CODES].p; a.bitbuf = (uint32_t *)W[E_BITBUF].p;
+		a.ibytes = (uint32_t *)W[E_INTS].p; a.iff = a.ibytes + (size_t)nc * n_int; a.ioff = a.iff + (size_t)nc * n_int;
+		a.out = (uint8_t *)W[E_OUT].p; a.out_stride = dstride; a.out_sizes = (uint32_t *)W[E_SIZES].p;
+		if ((rc = ev.begin(st))) return rc;
+		HIP_TRY(hipMemsetAsync(W[E_HIST].p, 0, hist_bytes, st));
 		HIP_TRY(launch_jpl_encode(a, st));
-		HIP_TRY(hipEventRecord(W.ev1, st));
+		if ((rc = ev.end(st))) return rc;
 		status.assign(nc, 0);
-		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, W.sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, W[E_SIZES].p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(status.data(), a.status, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
-		float ms = 0;
-		HIP_TRY(hipEventElapsedTime(&ms, W.ev0, W.ev1));
-		ms_sum += ms;
-		for (int i = 0; i < nc; i++) {
-			h_status[c0 + i] = status[i] ? CCT_E_OVERFLOW : CCT_OK;
-			if (h_out_sizes[c0 + i] > bound) return fail(CCT_E_DEVICE, "frame %d: size %u beyond its bound", c0 + i, h_out_sizes[c0 + i]);
-			if (h_out_sizes[c0 + i])
-				HIP_TRY(hipMemcpyAsync(h_out + (size_t)(c0 + i) * out_stride, (const uint8_t *)W.out.p + (size_t)i * dstride, h_out_sizes[c0 + i],
-				                       hipMemcpyDeviceToHost, st));
-		}
-		HIP_TRY(hipStreamSynchronize(st));
+		if ((rc = ev.add_ms(ms_sum))) return rc;
+		for (int i = 0; i < nc; i++) h_status[c0 + i] = status[i] ? CCT_E_OVERFLOW : CCT_OK;
+		if ((rc = files_to_host(h_out + (size_t)c0 * out_stride, out_stride, h_out_sizes + c0, nc, W[E_OUT].p, dstride, 0, bound, "frame", c0, "bound", st)))
+			return rc;
 	}
 	set_last_kernel_ms(true, ms_sum);
 	for (int i = 0; i < n; i++)
@@ -242,8 +220,7 @@ int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, i
 	const size_t N = (size_t)rows * cols, px_bytes = (size_t)bits / 8;
 	if (images_cap_px / N < (size_t)n) return fail(CCT_E_CAP, "output holds %zu pixels, need %zu", images_cap_px, (size_t)n * N);
 	if (n > 0 && (!h_files || !h_offsets || !images || !h_status)) return fail(CCT_E_ARG, "null argument");
-	for (int i = 0; i < n; i++)
-		if (h_offsets[i + 1] < h_offsets[i]) return fail(CCT_E_ARG, "file offsets must not decrease");
+	if ((rc = check_offsets(h_offsets, n, "file"))) return rc;
 	if (n == 0) return CCT_OK;
 	// the marker walk: every structural refusal is decided here, before the device is touched
 	std::vector<Parsed> parsed(n);
@@ -257,16 +234,14 @@ int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, i
 		return fail((int)h_status[0], "frame 0: %s", refusal((int)h_status[0]));
 	DecLease L;
 	if ((rc = lease_decode_slot(L))) return rc;
-	ApiCall in_call;
-	HIP_TRY(hipSetDevice(bound_device()));
 	hipStream_t st = L.stream;
-	DecWs &W = g_dec_ws[L.slot];
-	if ((rc = ensure_events(W.ev0, W.ev1))) return rc;
+	DevBuf *W = g_dec_ws[L.slot].buf;
+	EventPair &ev = g_dec_ws[L.slot].ev;
 	float ms_sum = 0;
 	std::vector<JplFrame> frames;
 	std::vector<uint32_t> int_frame, status;
 	std::vector<int> frame_of;
-	struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{st};  // declared after the vectors the copies land in
+	StreamDrain drain(st);  // declared after the vectors the copies land in
 	for (int c0 = 0; c0 < n;) {
 		int c1 = c0 + 1;
 		while (c1 < n && h_offsets[c1 + 1] - h_offsets[c0] <= JPL_PASS_BYTES / 4 && (size_t)(c1 + 1 - c0) * N * (2 + px_bytes) <= JPL_PASS_BYTES) c1++;
@@ -306,50 +281,38 @@ int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, i
 			const size_t abytes = (size_t)(a1 - a0), nf = frames.size(), ni = int_frame.size();
 			uint8_t *d_img = images_on_device ? (uint8_t *)images + (size_t)c0 * N * px_bytes : nullptr;
 			if (!images_on_device) {
-				if ((rc = W.img.ensure((size_t)(c1 - c0) * N * px_bytes))) return rc;
-				d_img = (uint8_t *)W.img.p;
+				if ((rc = W[D_IMG].ensure((size_t)(c1 - c0) * N * px_bytes))) return rc;
+				d_img = (uint8_t *)W[D_IMG].p;
 			}
-			if ((rc = W.files.ensure(abytes + 16))) return rc;
-			if ((rc = W.ubuf.ensure(abytes + 16))) return rc;
-			if ((rc = W.frames.ensure(nf * sizeof(JplFrame)))) return rc;
-			if ((rc = W.int_frame.ensure(ni * 4))) return rc;
-			if ((rc = W.istart.ensure((ni + nf) * 4))) return rc;
-			if ((rc = W.sub.ensure((size_t)nsub * 3 * 4 + 16))) return rc;
-			if ((rc = W.diff.ensure((size_t)(c1 - c0) * N * 2))) return rc;
-			if ((rc = W.status.ensure(nf * 4))) return rc;
-			HIP_TRY(hipMemcpyAsync(W.files.p, h_files + a0, abytes, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(W.frames.p, frames.data(), nf * sizeof(JplFrame), hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(W.int_frame.p, int_frame.data(), ni * 4, hipMemcpyHostToDevice, st));
+			if ((rc = W[D_FILES].ensure(abytes + 16))) return rc;
+			if ((rc = W[D_UBUF].ensure(abytes + 16))) return rc;
+			if ((rc = W[D_FRAMES].ensure(nf * sizeof(JplFrame)))) return rc;
+			if ((rc = W[D_INT_FRAME].ensure(ni * 4))) return rc;
+			if ((rc = W[D_ISTART].ensure((ni + nf) * 4))) return rc;
+			if ((rc = W[D_SUB].ensure((size_t)nsub * 3 * 4 + 16))) return rc;
+			if ((rc = W[D_DIFF].ensure((size_t)(c1 - c0) * N * 2))) return rc;
+			if ((rc = W[D_STATUS].ensure(nf * 4))) return rc;
+			HIP_TRY(hipMemcpyAsync(W[D_FILES].p, h_files + a0, abytes, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(W[D_FRAMES].p, frames.data(), nf * sizeof(JplFrame), hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(W[D_INT_FRAME].p, int_frame.data(), ni * 4, hipMemcpyHostToDevice, st));
 			JplDecArgs a{};
-			a.files = (const uint8_t *)W.files.p; a.frames = (const JplFrame *)W.frames.p; a.nframes = (uint32_t)nf;
-			a.int_frame = (const uint32_t *)W.int_frame.p; a.total_int = (uint32_t)ni;
+			a.files = (const uint8_t *)W[D_FILES].p; a.frames = (const JplFrame *)W[D_FRAMES].p; a.nframes = (uint32_t)nf;
+			a.int_frame = (const uint32_t *)W[D_INT_FRAME].p; a.total_int = (uint32_t)ni;
 			a.rows = (uint32_t)rows; a.cols = (uint32_t)cols; a.out_bits = (uint32_t)bits;
-			a.ubuf = (uint8_t *)W.ubuf.p; a.istart = (uint32_t *)W.istart.p;
-			a.sub_start = (uint32_t *)W.sub.p; a.sub_land = a.sub_start + nsub; a.sub_cnt = a.sub_land + nsub;
-			a.diff = (uint16_t *)W.diff.p; a.status = (uint32_t *)W.status.p; a.images = d_img; a.any_generic = any_generic;
-			HIP_TRY(hipEventRecord(W.ev0, st));
-			HIP_TRY(hipMemsetAsync(W.status.p, 0, nf * 4, st));
+			a.ubuf = (uint8_t *)W[D_UBUF].p; a.istart = (uint32_t *)W[D_ISTART].p;
+			a.sub_start = (uint32_t *)W[D_SUB].p; a.sub_land = a.sub_start + nsub; a.sub_cnt = a.sub_land + nsub;
+			a.diff = (uint16_t *)W[D_DIFF].p; a.status = (uint32_t *)W[D_STATUS].p; a.images = d_img; a.any_generic = any_generic;
+			if ((rc = ev.begin(st))) return rc;
+			HIP_TRY(hipMemsetAsync(W[D_STATUS].p, 0, nf * 4, st));
 			HIP_TRY(launch_jpl_decode(a, st));
-			HIP_TRY(hipEventRecord(W.ev1, st));
+			if ((rc = ev.end(st))) return rc;
 			status.assign(nf, 0);
-			HIP_TRY(hipMemcpyAsync(status.data(), W.status.p, nf * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(status.data(), W[D_STATUS].p, nf * 4, hipMemcpyDeviceToHost, st));
 			HIP_TRY(hipStreamSynchronize(st));
-			float ms = 0;
-			HIP_TRY(hipEventElapsedTime(&ms, W.ev0, W.ev1));
-			ms_sum += ms;
+			if ((rc = ev.add_ms(ms_sum))) return rc;
 			for (size_t k = 0; k < nf; k++)
 				if (status[k]) h_status[frame_of[k]] = CCT_E_STREAM;
-			if (!images_on_device) {  // the good frames, in runs: a refused frame leaves its slot in host memory alone
-				for (int i = c0; i < c1;) {
-					if (h_status[i] != CCT_OK) { i++; continue; }
-					int j = i + 1;
-					while (j < c1 && h_status[j] == CCT_OK) j++;
-					HIP_TRY(hipMemcpyAsync((uint8_t *)images + (size_t)i * N * px_bytes, d_img + (size_t)(i - c0) * N * px_bytes,
-					                       (size_t)(j - i) * N * px_bytes, hipMemcpyDeviceToHost, st));
-					i = j;
-				}
-				HIP_TRY(hipStreamSynchronize(st));
-			}
+			if (!images_on_device && (rc = good_rasters_to_host(images, d_img, N * px_bytes, h_status, c0, c1, st))) return rc;
 		}
 		c0 = c1;
 	}

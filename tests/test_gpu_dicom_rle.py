@@ -228,3 +228,68 @@ def test_evaluate_tool_fills_the_rle_column(tmp_path):
         assert int(cell["RLE"]) == len(m.encapsulate([m.encode_frame(img)]))
     assert tool.main([str(tmp_path), "--results", str(out)]) == 0
     assert [ln.split(",")[head.index("RLE")] for ln in out.read_text().splitlines()[1:]] == ["NA", "NA"]
+
+
+PASS_BYTES = 512 << 20  # csrc/api_dicom_rle.cpp RLE_PASS_BYTES
+
+
+def test_encode_in_two_passes_equals_single_frames():
+    """9 uint8 rasters of 4096 x 8192: the device stride of a frame is 64 + 2 * 2^25 bytes rounded to words, so a pass takes 7
+    of them and the batch runs as 7 + 2.  Single frames are pinned to the model at small shapes; here the batch is pinned
+    to them on both sides of the pass border."""
+    import cct_hip
+    rows, cols, n = 4096, 8192, 9
+    dstride = (cct_hip._ffi.lib().cct_dicom_rle_bound(rows, cols, 8) + 3) & ~3
+    per_pass = PASS_BYTES // dstride
+    assert per_pass == 7 and per_pass < n <= 2 * per_pass
+    rng = np.random.default_rng(21)
+    imgs = np.empty((n, rows, cols), np.uint8)
+    for i in range(n):
+        imgs[i] = 10 + i  # a constant plane and i + 1 rows of noise: frames differ in content and in coded size
+        imgs[i, 17 * i:17 * i + i + 1] = rng.integers(0, 256, (i + 1, cols), dtype=np.uint8)
+    got = cct_hip.dicom_rle_encode_batch(imgs)
+    assert len(set(len(f) for f in got)) == n
+    for i in (0, 6, 7, 8):
+        assert got[i] == cct_hip.dicom_rle_encode_batch(imgs[i:i + 1])[0], i
+
+
+def test_decode_in_two_passes_keeps_refused_slots():
+    """9 frames of 8192 x 8192 uint16, one value each: a pass holds 2 * 2^29 bytes of rasters, 8 of them, so the batch runs
+    as 8 + 1.  A row of one value is 64 replicate packets of 128, a segment 1 MiB.  One frame of each pass ends two bytes
+    early: CCT_E_STREAM for those two, and their slots in host memory stay as they were."""
+    import cct_hip
+    from cct_hip import _ffi
+    rows = cols = 8192
+    n, N = 9, rows * cols
+    assert (2 * PASS_BYTES) // (2 * N) == 8
+    value = lambda i: ((i + 1) << 8) | (0x80 + i)  # noqa: E731
+
+    def frame(i, cut=0):
+        hi, lo = (np.tile(np.array([129, b], np.uint8), rows * cols // 128).tobytes() for b in (value(i) >> 8, value(i) & 0xFF))
+        return struct.pack("<16I", 2, 64, 64 + len(hi), *([0] * 13)) + hi + lo[:len(lo) - cut]
+
+    bad = (3, 8)
+    frames = [frame(i, 2 if i in bad else 0) for i in range(n)]
+    assert len(frames[0]) == 64 + (2 << 20)
+    want_status = [E_STREAM if i in bad else 0 for i in range(n)]
+
+    def check(res):
+        for i in range(n):
+            if i not in bad:
+                for r in (0, rows // 2, rows - 1):
+                    assert (res[i, r] == value(i)).all(), (i, r)
+
+    res, status = cct_hip.dicom_rle_decode_batch(frames, rows, cols, raise_errors=False)
+    assert list(status) == want_status
+    check(res)
+    # the C entry point, into a buffer that holds a sentinel
+    res[:] = 0xA5A5
+    blob = b"".join(frames)
+    offs = np.zeros(n + 1, np.uint64)
+    np.cumsum([len(f) for f in frames], out=offs[1:])
+    status = np.zeros(n, np.uint32)
+    rc = _ffi.lib().cct_dicom_rle_decode_batch(blob, offs.ctypes.data, n, rows, cols, 16, res.ctypes.data, 0, res.size, status.ctypes.data)
+    assert rc == E_STREAM and list(status) == want_status
+    check(res)
+    for i in bad:
+        assert (res[i] == 0xA5A5).all(), i

@@ -278,3 +278,37 @@ def test_evaluate_tool_appends_the_jpl_column(tmp_path):
     plain = out.read_text().splitlines()
     assert plain[0] == "File,Raw,ZIP,PNG,RLE,JP2,CCT"
     assert plain == [ln.rsplit(",", 1)[0] for ln in with_jpl]  # the other columns are what they were
+
+
+PASS_BYTES = 512 << 20  # csrc/api_jpeg_lossless.cpp JPL_PASS_BYTES
+
+
+def test_batches_of_several_passes_equal_single_frames():
+    """9 uint16 rasters of 4096 x 4096 at precision 16: the encoder holds cct_jpegll_bound + 4 bytes a sample per frame,
+    about 188 MiB, so it runs as 2 + 2 + 2 + 2 + 1; the decoder holds 4 bytes a sample, 8 frames a pass as long as their
+    files stay below a quarter of the pass, so it runs as 8 + 1.  Single frames are pinned to the model at small shapes."""
+    import cct_hip
+    from cct_hip import _ffi
+    rows = cols = 4096
+    n, N = 9, rows * cols
+    dstride = (_ffi.lib().cct_jpegll_bound(rows, cols, 0) + 3) & ~3
+    assert PASS_BYTES // (dstride + 4 * N) == 2
+    rng = np.random.default_rng(22)
+    ramp = (np.arange(rows, dtype=np.uint32)[:, None] * 3 + np.arange(cols, dtype=np.uint32)[None, :]).astype(np.uint16)
+    noise = rng.integers(0, 8, (rows, cols), dtype=np.uint16)
+    imgs = np.stack([ramp + (noise >> (i % 3)) + np.uint16(6000 * i) for i in range(n)])
+    imgs[8, 0, 0] = 65535
+    files = cct_hip.jpeg_lossless_encode_batch(imgs)
+    assert len(set(len(f) for f in files)) >= 3
+    for i in (0, 1, 2, 8):
+        assert files[i] == cct_hip.jpeg_lossless_encode_batch(imgs[i:i + 1])[0], i
+    assert sum(len(f) for f in files[:8]) <= PASS_BYTES // 4 and PASS_BYTES // (4 * N) == 8  # the decoder's first pass takes 8
+    assert np.array_equal(cct_hip.jpeg_lossless_decode_batch(files, rows, cols), imgs)
+    damaged = list(files)
+    for i in (3, 8):  # the entropy-coded data ends early
+        damaged[i] = files[i][:-1002] + files[i][-2:]
+    back, status = cct_hip.jpeg_lossless_decode_batch(damaged, rows, cols, raise_errors=False)
+    assert list(status) == [E_STREAM if i in (3, 8) else 0 for i in range(n)]
+    for i in range(n):
+        if i not in (3, 8):
+            assert np.array_equal(back[i], imgs[i]), i
