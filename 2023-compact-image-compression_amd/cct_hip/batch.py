@@ -867,3 +867,60 @@ def jpeg_lossless_decode_batch(files, rows, cols, bits=16, out_dev=None, raise_e
     blob, offs = _archive(files)
     return _decode_rasters(lambda *to: L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, *to), n, rows,
                            cols, dt, out_dev, raise_errors, (_ffi.E_JPEG, _ffi.E_MIXED, _ffi.E_STREAM))
+
+
+# ---- JPEG 2000 Part-1 lossless (T.800; DICOM 1.2.840.10008.1.2.4.90): files on the device --------------------------------
+
+def jpeg2000_encode_batch(images, precision=None, shift=0, levels=5, codeblock=64, jp2=False, shape=None, dtype=None):
+    """JPEG 2000 Part-1 lossless files (DICOM transfer syntax 1.2.840.10008.1.2.4.90) on the device: a uint16 or uint8 array
+    of shape (n, rows, cols) or (rows, cols), or a DeviceBuffer with shape= given (dtype= np.uint16 unless np.uint8 is
+    named), -> a list of n `bytes`, each one raw codestream (SOC .. EOC) or, with jp2=True, one JP2 file.  precision is
+    2 .. 16 and defaults to the sample width; the sample coded is value << shift (shift=4 reproduces the 16-bit PNG preview
+    of a 12-bit slice).  levels (0 .. 8) decompositions of the reversible 5/3 transform, code-blocks of codeblock (32 or 64)
+    squared, one tile, one layer, LRCP, every coding pass kept; tests/jpeg2000_model.py states the file byte for byte.  A
+    sample that does not fit the precision raises OverflowError.  dicom_encapsulate wraps the codestreams as PixelData.
+    Arguments are checked (TypeError / ValueError) before any device call.
+    Memory: the call reserves cct_j2k_bound(rows, cols, levels, codeblock, jp2) bytes per frame on the host, about 5 bytes
+    a sample (1.4 MB for 512 x 512; pages a file does not reach are never touched), and on the device that plus the slabs of
+    the same size and 8 bytes a sample, at most 512 MB at a time."""
+    src, shape, dt = _raster_batch(images, shape, dtype, "jpeg2000_encode_batch", "frame")
+    n, rows, cols = shape
+    if dt != np.uint8 and dt != np.uint16:
+        raise TypeError(f"JPEG 2000 frames take uint8 or uint16 samples, got {dt}")
+    src_bits = 8 * dt.itemsize
+    precision, shift, levels, codeblock = _ints(precision=src_bits if precision is None else precision, shift=shift, levels=levels,
+                                                codeblock=codeblock)
+    if not 2 <= precision <= 16:
+        raise ValueError(f"JPEG 2000 precision {precision}: 2 to 16")
+    if precision > src_bits:
+        raise ValueError(f"precision {precision} for {dt} samples: at most {src_bits}")
+    if not 0 <= shift <= 15 or precision - shift < 1:
+        raise ValueError(f"shift {shift} at precision {precision}: 0 to 15 and below the precision")
+    if not 0 <= levels <= 8:
+        raise ValueError(f"{levels} decomposition levels: 0 to 8")
+    if codeblock not in (32, 64):
+        raise ValueError(f"code-blocks of {codeblock}: 32 or 64")
+    if n == 0:
+        return []
+    if not 1 <= rows <= 65535 or not 1 <= cols <= 65535 or rows * cols > _JPL_MAX_PIXELS:
+        raise ValueError(f"JPEG 2000 frame of {rows} x {cols} samples: rows and cols are 1 to 65535, at most {_JPL_MAX_PIXELS} pixels")
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"frame batch shape {shape} of {dt}")
+    L = _ffi.lib()
+    out_stride = L.cct_j2k_bound(rows, cols, levels, codeblock, int(bool(jp2)))
+    out, sizes = _files_out(n, out_stride)
+    status = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_j2k_encode_batch(ptr, on_device, n, rows, cols, src_bits, precision, shift, levels, codeblock, int(bool(jp2)),
+                                      out.ctypes.data, out_stride, sizes.ctypes.data, status.ctypes.data))
+    del keep
+    return _files_of(out, sizes)
+
+
+def jpeg2000_info(file):
+    """(rows, cols, precision) of one JPEG 2000 raw codestream or JP2 file (`bytes`) from its SIZ; host only.  ValueError
+    for anything else (CCT_E_J2K in include/compact_hip.h)."""
+    if not isinstance(file, (bytes, bytearray, memoryview)):
+        raise TypeError(f"a JPEG 2000 file is a bytes object, got {type(file).__name__}")
+    file = bytes(file)
+    rows, cols, prec = C.c_int(0), C.c_int(0), C.c_int(0)
+    _ffi.check(_ffi.lib().cct_j2k_info(file, len(file), C.byref(rows), C.byref(cols), C.byref(prec)))
+    return rows.value, cols.value, prec.value

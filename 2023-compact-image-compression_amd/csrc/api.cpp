@@ -930,6 +930,7 @@ int cct_shutdown(void)
 	comm_release();
 	dicom_rle_release();
 	jpegll_release();
+	j2k_release();
 	if (g_gate) { (void)hipFree(g_gate); g_gate = nullptr; }
 	for (auto &kv : g_ctx.luts) {
 		ShapeTables &t = kv.second;

@@ -3,6 +3,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -364,5 +367,129 @@ struct JplDecArgs {
 	uint32_t any_generic;      // some frame has a predictor other than 1
 };
 hipError_t launch_jpl_decode(const JplDecArgs &a, hipStream_t st);
+
+// ---- JPEG 2000 Part-1 lossless encoder (jpeg2000_kernels.hip) -------------------------------------
+// tests/jpeg2000_model.py states the file.  The host lays the image out once per call (j2k_layout): the coefficients of all
+// subbands share one rows x cols int32 plane in the Mallat arrangement (after a stage the LL band is the top left corner),
+// every code-block is a rectangle of that plane, and the subbands are listed in packet order.
+constexpr uint32_t J2K_ST_OVERFLOW = 1u;  // a sample >= 2^precision after the shift (the convert kernel sets it)
+constexpr uint32_t J2K_ST_CAP = 2u;       // a code-block's bytes or a packet header would leave its space
+constexpr uint32_t J2K_ST_GUARD = 4u;     // a coefficient needs more bit-planes than the guard bits allow (Tier-1 sets it)
+constexpr uint32_t J2K_HDR_MAX = 192;     // JP2 boxes 85, SOC 2, SIZ 43, COD 14, QCD 5 + 25, SOT 12, SOD 2 = 188 at 8 levels
+constexpr uint32_t J2K_GUARD_BITS = 2;
+constexpr uint32_t J2K_PKT_BYTES = 512;   // packet header bytes granted per packet ..
+constexpr uint32_t J2K_CB_HDR_BYTES = 32; // .. and per code-block (cct_j2k_bound derives both)
+constexpr uint32_t J2K_TT_LEVELS = 13;    // tag tree levels: at most 65535 / 32 + 1 = 2048 code-blocks a side, 2^11 -> 12 levels
+struct J2kBlock {          // one code-block: where it lies in the plane, and its slab in the workspace of a frame
+	uint16_t x0, y0, w, h;   // w, h <= 64
+	uint32_t orient;         // 0 LL, 1 HL, 2 LH, 3 HH
+	uint32_t mb;             // magnitude bit-planes of its subband: guard bits + exponent - 1 = precision + gain + 1
+	uint32_t slab_off, slab_cap;
+};
+struct J2kBand { uint32_t cb0, ncw, nch, mb; };  // a subband in packet order: its first code-block, the grid (0 x 0: empty)
+struct J2kBlockOut { uint32_t passes, bytes, zero_planes, dst; };  // Tier-1's result; dst: Tier-2's offset of the bytes in the file
+struct J2kArgs {
+	const void *images;        // n * rows * cols samples of src_bits (8 or 16)
+	uint32_t src_bits, n, rows, cols, precision, shift, levels, codeblock;
+	uint32_t stages;           // 7: all; tuning runs (CCT_J2K_STAGES) stop early: 1 convert and transform, 2 Tier-1, 4 Tier-2
+	int32_t *plane_a, *plane_b;  // n * rows * cols each: the coefficients end up in plane_a
+	const J2kBlock *blocks; uint32_t nblocks;
+	const J2kBand *bands; uint32_t nbands;  // 1 + 3 * levels: LL, then HL, LH, HH of every resolution
+	uint8_t *slabs; size_t slab_stride;     // a frame's code-block bytes: block b at slabs + frame * slab_stride + slab_off
+	J2kBlockOut *cbout;        // n * nblocks
+	uint8_t *tt; uint32_t tt_nodes;  // tag tree nodes: per frame 2 trees of 3 byte arrays (value, low, known) of tt_nodes
+	uint32_t *status;          // n, zero on entry: J2K_ST_*
+	uint32_t hdr_len, psot_at, jp2c_at;  // bytes of hdr; where Psot and (0: raw codestream) the jp2c box length are patched
+	uint8_t hdr[J2K_HDR_MAX];  // everything up to and including SOD
+	uint8_t *out; size_t out_stride; uint32_t *out_sizes;  // a frame with a status gets size 0
+};
+hipError_t launch_j2k_encode(const J2kArgs &a, hipStream_t st);
+
+// The slab rule.  A sample takes part in at most mb magnitude decisions (one per bit-plane, in one of the three passes), one
+// sign decision, and the run-length decisions of the cleanup pass, which replace the zero-coding decisions of the samples they
+// cover or add two position bits to one of four samples: at most mb + 2 decisions a sample.  The MQ coder's estimates adapt,
+// so a run of decisions against the estimate drives the state to Qe ~ 0.5, where a decision costs about one bit; the rule
+// grants two bits a decision, (mb + 2) / 4 bytes a sample (5.25 for HH at precision 16, where uniform noise, the costliest
+// content there is in practice, takes about 2.2), plus 64 bytes for the flush.  It is a rule, not a proof: Tier-1 checks
+// every byte against it and refuses the frame (CCT_E_CAP) rather than write past the slab.
+inline uint32_t j2k_slab_cap(uint32_t w, uint32_t h, uint32_t mb) { return (w * h * (mb + 2) + 3) / 4 + 64; }
+
+struct J2kLayout {
+	std::vector<J2kBlock> blocks;
+	std::vector<J2kBand> bands;
+	uint32_t tt_nodes = 1;   // nodes of the largest tag tree
+	size_t slab_bytes = 0;   // a frame's slabs
+	size_t bound = 0;        // cct_j2k_bound's expression for this layout
+};
+// Subbands in packet order and their code-blocks in raster order (tests/jpeg2000_model.py resolutions()); caller-checked
+// arguments: rows, cols 1 .. 65535, precision 2 .. 16, levels 0 .. 8, codeblock 32 or 64.
+inline void j2k_layout(uint32_t rows, uint32_t cols, uint32_t precision, uint32_t levels, uint32_t codeblock, J2kLayout &L)
+{
+	uint32_t dw[10], dh[10];
+	dw[0] = cols; dh[0] = rows;
+	for (uint32_t d = 1; d <= levels; d++) { dw[d] = (dw[d - 1] + 1) / 2; dh[d] = (dh[d - 1] + 1) / 2; }
+	auto band = [&](uint32_t orient, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+		const uint32_t gain = orient == 0 ? 0 : orient == 3 ? 2 : 1, mb = J2K_GUARD_BITS + precision + gain - 1;
+		const uint32_t ncw = (w + codeblock - 1) / codeblock, nch = (h + codeblock - 1) / codeblock;
+		J2kBand bd{(uint32_t)L.blocks.size(), w && h ? ncw : 0, w && h ? nch : 0, mb};
+		L.bands.push_back(bd);
+		if (!bd.ncw) return;
+		uint32_t nodes = 0;
+		for (uint32_t pw = ncw, ph = nch;; pw = (pw + 1) / 2, ph = (ph + 1) / 2) { nodes += pw * ph; if (pw == 1 && ph == 1) break; }
+		L.tt_nodes = nodes > L.tt_nodes ? nodes : L.tt_nodes;
+		for (uint32_t by = 0; by < h; by += codeblock)
+			for (uint32_t bx = 0; bx < w; bx += codeblock) {
+				J2kBlock b{};
+				b.x0 = (uint16_t)(x0 + bx); b.y0 = (uint16_t)(y0 + by);
+				b.w = (uint16_t)(w - bx < codeblock ? w - bx : codeblock); b.h = (uint16_t)(h - by < codeblock ? h - by : codeblock);
+				b.orient = orient; b.mb = mb;
+				b.slab_off = (uint32_t)L.slab_bytes; b.slab_cap = j2k_slab_cap(b.w, b.h, mb);
+				L.slab_bytes += b.slab_cap;
+				L.blocks.push_back(b);
+			}
+	};
+	L.blocks.clear(); L.bands.clear(); L.tt_nodes = 1; L.slab_bytes = 0;
+	band(0, 0, 0, dw[levels], dh[levels]);
+	for (uint32_t r = 1; r <= levels; r++) {
+		const uint32_t d = levels - r + 1, pw = dw[d - 1], ph = dh[d - 1], wl = dw[d], hl = dh[d];
+		band(1, wl, 0, pw - wl, hl);
+		band(2, 0, hl, wl, ph - hl);
+		band(3, wl, hl, pw - wl, ph - hl);
+	}
+	L.bound = J2K_HDR_MAX + 2 + (size_t)(levels + 1) * J2K_PKT_BYTES + L.blocks.size() * J2K_CB_HDR_BYTES + L.slab_bytes;
+}
+
+// Everything up to and including SOD (the JP2 boxes in front with jp2): -> its length; *psot_at and *jp2c_at (0 without
+// jp2) are where Tier-2 patches Psot and the length of the jp2c box.  hdr holds J2K_HDR_MAX bytes.
+inline uint32_t j2k_headers(uint32_t rows, uint32_t cols, uint32_t precision, uint32_t levels, uint32_t codeblock, bool jp2, uint8_t *hdr,
+                            uint32_t *psot_at, uint32_t *jp2c_at)
+{
+	uint32_t n = 0;
+	auto u8 = [&](uint32_t v) { hdr[n++] = (uint8_t)v; };
+	auto u16 = [&](uint32_t v) { u8(v >> 8); u8(v); };
+	auto u32 = [&](uint32_t v) { u16(v >> 16); u16(v & 0xFFFF); };
+	auto tag = [&](const char *t) { for (int k = 0; k < 4; k++) u8((uint8_t)t[k]); };
+	*jp2c_at = 0;
+	if (jp2) {
+		u32(12); tag("jP  "); u32(0x0D0A870A);
+		u32(20); tag("ftyp"); tag("jp2 "); u32(0); tag("jp2 ");
+		u32(45); tag("jp2h");
+		u32(22); tag("ihdr"); u32(rows); u32(cols); u16(1); u8(precision - 1); u8(7); u8(0); u8(0);
+		u32(15); tag("colr"); u8(1); u8(0); u8(0); u32(17);
+		*jp2c_at = n;
+		u32(0); tag("jp2c");
+	}
+	u16(0xFF4F);
+	u16(0xFF51); u16(41); u16(0); u32(cols); u32(rows); u32(0); u32(0); u32(cols); u32(rows); u32(0); u32(0); u16(1); u8(precision - 1); u8(1); u8(1);
+	const uint32_t cbe = codeblock == 64 ? 4 : 3;
+	u16(0xFF52); u16(12); u8(0); u8(0); u16(1); u8(0); u8(levels); u8(cbe); u8(cbe); u8(0); u8(1);
+	u16(0xFF5C); u16(3 + 1 + 3 * levels); u8(J2K_GUARD_BITS << 5); u8(precision << 3);
+	for (uint32_t l = 0; l < levels; l++) { u8((precision + 1) << 3); u8((precision + 1) << 3); u8((precision + 2) << 3); }
+	u16(0xFF90); u16(10); u16(0);
+	*psot_at = n;
+	u32(0); u8(0); u8(1);
+	u16(0xFF93);
+	return n;
+}
 
 }  // namespace cct

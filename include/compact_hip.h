@@ -64,6 +64,7 @@ extern "C" {
 #define CCT_E_PNG 11      /* cct_png_read_batch / cct_png_info: not a PNG this reader takes -> ValueError */
 #define CCT_E_CRC 12      /* cct_png_read_batch: a chunk's CRC-32 does not match           -> ValueError */
 #define CCT_E_JPEG 13     /* cct_jpegll_decode_batch / cct_jpegll_info: not a JPEG this reader takes -> ValueError */
+#define CCT_E_J2K 14      /* cct_j2k_info: not a JPEG 2000 codestream or JP2 file it reads          -> ValueError */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
 #define CCT_FLAG_FRACTAL 1u       /* transforms.fractal      (core.py:234) */
@@ -398,6 +399,35 @@ int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int
 int cct_jpegll_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
 int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits, void *images,
                             int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
+
+/* ---- JPEG 2000 Part-1 lossless encoder (T.800; DICOM transfer syntax 1.2.840.10008.1.2.4.90) ----
+ * cct_j2k_encode_batch: n rasters of shape (rows, cols), C order, uint16 (src_bits 16) or uint8 (src_bits 8), on the
+ * host or (images_on_device) the device, -> n files at h_out + i*out_stride with their sizes in h_out_sizes[i]; every
+ * stage runs on the device (level shift and reversible 5/3 transform, Tier-1, Tier-2).  The sample coded is value << shift
+ * (shift 4 reproduces the 16-bit PNG preview) at `precision` bits, unsigned.  The file is fixed, so the output is
+ * deterministic (tests/jpeg2000_model.py states it byte for byte): SOC, SIZ (Rsiz 0, one component, one tile), COD (no
+ * SOP/EPH, maximal precincts, LRCP, one layer, `levels` decompositions, code-blocks of `codeblock` squared, style 0, 5/3),
+ * QCD (no quantization, 2 guard bits), one SOT with Psot, SOD, levels + 1 packets with every coding pass of every
+ * code-block, EOC; no COM.  jp2 != 0 puts the minimal JP2 container in front (signature, ftyp, jp2h with ihdr and an
+ * enumerated greyscale colr, jp2c: 85 bytes); the default raw codestream is what DICOM encapsulates.
+ * Per frame, h_status[i]: CCT_OK; CCT_E_OVERFLOW (a sample << shift >= 2^precision, or a coefficient that needs more
+ * bit-planes than the guard bits allow) or CCT_E_CAP (a code-block's bytes beyond its slab, see cct_j2k_bound) with size 0;
+ * the other frames are encoded, and the call returns the first status that is not CCT_OK.
+ * cct_j2k_bound(rows, cols, levels, codeblock, jp2): a sufficient out_stride: 192 bytes of headers, 512 bytes of packet
+ * header per packet and 32 per code-block (their worst case), and per code-block of w x h samples in a subband of mb
+ * bit-planes at precision 16 (17 LL, 18 HL / LH, 19 HH) a slab of w h (mb + 2) / 4 + 64 bytes: two bits for every decision
+ * of the arithmetic coder, about 5 bytes a sample where uniform noise takes 2.2.  0 for refused arguments.
+ * cct_j2k_info: (rows, cols, precision) of a raw codestream or a JP2 file (the boxes are walked to jp2c) from its SIZ;
+ * host only; CCT_E_J2K for anything else: no SOC + SIZ, a SIZ that leaves the file, more than one component, signed or
+ * deeper than 16 bits, a JP2 without jp2c.
+ * Whole-call errors of the encoder, before the device is touched: CCT_E_ARG for rows or cols outside 1 .. 65535, rows*cols
+ * above 2^26, n < 0, src_bits other than 8 or 16, precision outside 2 .. 16 or above src_bits, shift outside 0 .. 15 or
+ * precision - shift < 1, levels outside 0 .. 8, codeblock other than 32 or 64; CCT_E_CAP for out_stride below the bound. */
+size_t cct_j2k_bound(int rows, int cols, int levels, int codeblock, int jp2);
+int cct_j2k_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int src_bits /* 8 or 16 */, int precision,
+                         int shift, int levels, int codeblock, int jp2, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes,
+                         uint32_t *h_status /* CCT_E_* per frame */);
+int cct_j2k_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
 
 /* ---- tuning / introspection (bench.py) --------------------------------------------- */
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per

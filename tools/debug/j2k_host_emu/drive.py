@@ -1,0 +1,68 @@
+"""Feeds ./emu (see emu.cpp) the rasters of tests/jpeg2000_model.py and compares the files: python drive.py [quick]"""
+import os
+import struct
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "..", "..", "..", "tests"))
+sys.path.insert(0, os.path.join(HERE, "..", "..", "..", "2023-compact-image-compression_amd"))
+import jpeg2000_model as m  # noqa: E402
+
+EMU = os.path.join(HERE, "emu")
+
+
+def encode(imgs, precision, shift, levels, codeblock, jp2, tmp, slab_div=1):
+    n, rows, cols = imgs.shape
+    src, dst = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+    imgs.tofile(src)
+    args = [8 * imgs.dtype.itemsize, precision, shift, levels, codeblock, int(jp2), rows, cols, n, slab_div, src, dst]
+    r = subprocess.run([EMU, *map(str, args)], capture_output=True, text=True)
+    assert r.returncode == 0, (args, r.stdout[-2000:], r.stderr[-4000:])
+    d, out, pos = open(dst, "rb").read(), [], 0
+    for _ in range(n):
+        size, status = struct.unpack_from("<II", d, pos)
+        out.append((status, d[pos + 8:pos + 8 + size]))
+        pos += 8 + size
+    return out
+
+
+def main(quick):
+    from cct_hip.synth import ct_phantom
+    rng = np.random.default_rng(2)
+    shapes = [(1, 1, 64), (1, 7, 64), (7, 1, 32), (5, 3, 64), (33, 65, 32), (65, 33, 64), (130, 70, 32)]
+    with tempfile.TemporaryDirectory() as tmp:
+        for rows, cols, cb in shapes:
+            for dt, p in ((np.uint8, 8), (np.uint16, 12), (np.uint16, 16)):
+                c = m.raster_cases(rows, cols, p, dt)
+                imgs = np.stack(list(c.values()))
+                for levels in (0, 1, 5):
+                    if quick and (levels == 1 or p == 12):
+                        continue
+                    got = encode(imgs, p, 0, levels, cb, False, tmp)
+                    for name, (st, g), x in zip(c, got, imgs):
+                        assert st == 0 and g == m.encode(x, p, 0, levels, cb), (rows, cols, p, levels, cb, name, st)
+            print("ok", rows, cols, cb, flush=True)
+        ph = np.stack([ct_phantom(0, n=128), rng.integers(0, 4096, (128, 128)).astype(np.uint16)])
+        for cb, jp2 in ((64, True), (32, False)):
+            got = encode(ph, 16, 4, 5, cb, jp2, tmp)
+            for (st, g), x in zip(got, ph):
+                assert st == 0 and g == m.encode(x, 16, 4, 5, cb, jp2), (cb, jp2, st)
+        print("ok phantom, shift 4, jp2", flush=True)
+        over = rng.integers(0, 4096, (4, 9, 11)).astype(np.uint16)
+        over[1, 2, 3], over[3, 0, 0] = 4096, 65535
+        got = encode(over, 12, 0, 2, 32, False, tmp)
+        assert [s for s, _ in got] == [0, 1, 0, 1] and got[1][1] == b"" and got[2][1] == m.encode(over[2], 12, 0, 2, 32)
+        # slabs an eighth of the rule: noise does not fit, the frame is refused (status 2) and the guards stay whole
+        noise = rng.integers(0, 65536, (2, 40, 40)).astype(np.uint16)
+        noise[1] = 32768
+        got = encode(noise, 16, 0, 1, 32, False, tmp, slab_div=8)
+        assert got[0] == (2, b"") and got[1] == (0, m.encode(noise[1], 16, 0, 1, 32)), [(s, len(g)) for s, g in got]
+        print("encode ok")
+
+
+if __name__ == "__main__":
+    main(len(sys.argv) > 1 and sys.argv[1] == "quick")

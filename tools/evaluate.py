@@ -2,7 +2,7 @@
 """Corpus size comparison: the counterpart of the reference's scripts/evaluate.py:52-136 without pydicom.
 
     python tools/evaluate.py DIRECTORY [--results FILE.csv] [--batch 256] [--zip host|device] [--png host|device]
-                             [--png-input host|device] [--rle device] [--jpl device]
+                             [--png-input host|device] [--rle device] [--jpl device] [--jp2 device|device-native]
 
 Every slice under DIRECTORY (.npy, .u16/.raw, .u16.zz, 16-bit .png) gets one CSV row `File,Raw,ZIP,PNG,RLE,JP2,CCT` as
 in results/encoder-comparisons.csv: Raw = bytes of the pixel array, ZIP = zlib.compress at the default level
@@ -24,7 +24,11 @@ behind CCT: the length of the encapsulated PixelData of the slice's JPEG Lossles
 len(cct_hip.dicom_encapsulate([frame])) with the frame from cct_hip.jpeg_lossless_encode_batch; without the flag the CSV has
 no such column.  Like the RLE column it takes 2-byte slices as uint16 whatever their dtype (int16 slices are reinterpreted,
 not offset); 1-byte slices are widened to uint16 and coded at precision 16 too, so that the column means one thing, which
-costs them the longer codes of a 16-bit table and is not what precision 8 would give.
+costs them the longer codes of a 16-bit table and is not what precision 8 would give.  --jp2 device fills the JP2 column
+with len(cct_hip.jpeg2000_encode_batch(image, precision=16, shift=4, jp2=True)): a lossless .jp2 file of the 16-bit preview
+value << 4, which is what the reference measured (lib/jpeg2000.py compresses the PNG; OpenJPEG's defaults: 6 resolutions,
+64 x 64 code-blocks).  --jp2 device-native is the same call at shift=0, the .jp2 file of the slice itself, about 38 % smaller
+on real CT slices.  Slices are taken as uint16 the way the JPL column takes them; the default stays NA.
 """
 import argparse
 import io
@@ -98,6 +102,9 @@ def main(argv=None):
     ap.add_argument("--jpl", choices=("na", "device"), default="na",
                     help="device: append a JPL column, the encapsulated JPEG Lossless frame from cct_hip.jpeg_lossless_encode_batch at "
                          "precision 16 (2-byte slices viewed as uint16, 1-byte slices widened to uint16)")
+    ap.add_argument("--jp2", choices=("na", "device", "device-native"), default="na",
+                    help="the JP2 column: NA, the lossless .jp2 file of value << 4 at precision 16 from cct_hip.jpeg2000_encode_batch (device: the "
+                         "reference's measure), or the same of the slice itself (device-native)")
     args = ap.parse_args(argv)
     import cct_hip
     with open(os.path.join(ROOT, "2023-compact-image-compression_amd", "config.json")) as f:
@@ -145,8 +152,14 @@ def main(argv=None):
                                                                 precision=16)
                     for (name, _), fr in zip(chunk, frames):
                         rows[name][JPL] = len(cct_hip.dicom_encapsulate([fr]))
+                if args.jp2 != "na":
+                    stack = np.stack([img for _, img in chunk])
+                    files = cct_hip.jpeg2000_encode_batch(stack.view(np.uint16) if stack.dtype.itemsize == 2 else stack.astype(np.uint16),
+                                                          precision=16, shift=4 if args.jp2 == "device" else 0, jp2=True)
+                    for (name, _), f in zip(chunk, files):
+                        rows[name][JP2] = len(f)
         for name, fut in futures.items():
-            rows[name].update(fut.result())
+            rows[name].update({k: v for k, v in fut.result().items() if k not in rows[name]})
     outputs = sorted(rows.values(), key=lambda r: r[FILE])  # evaluate.py:130
     cols = [FILE, RAW, ZIP, PNG, RLE, JP2, CCT] + ([JPL] if args.jpl == "device" else [])
     os.makedirs(os.path.dirname(os.path.abspath(args.results)), exist_ok=True)
