@@ -924,3 +924,34 @@ def jpeg2000_info(file):
     rows, cols, prec = C.c_int(0), C.c_int(0), C.c_int(0)
     _ffi.check(_ffi.lib().cct_j2k_info(file, len(file), C.byref(rows), C.byref(cols), C.byref(prec)))
     return rows.value, cols.value, prec.value
+
+
+def jpeg2000_decode_batch(files, rows, cols, bits=16, shift=0, out_dev=None, raise_errors=True):
+    """JPEG 2000 Part-1 lossless files (a list of `bytes`: raw codestreams or JP2 files of one unsigned component, precision
+    <= `bits` = 8 or 16 allocated) -> an (n, rows, cols) uint8 / uint16 array, decoded on the device; the sample returned is
+    value >> shift, so jpeg2000_decode_batch(jpeg2000_encode_batch(x, shift=s), ..., shift=s) is x.  Files of any encoder are
+    taken within these limits: one tile and one tile-part, origins 0, maximal precincts, no SOP / EPH, any progression order,
+    1 to 32 layers, 0 to 8 levels, code-blocks of 4 to 64 by 4 to 64, code-block style 0, the reversible 5/3 transform, no
+    quantization, at most 19 magnitude bit-planes a subband; COM, TLM, PLM, PLT and CRG are skipped.  The rest (the 9/7
+    transform, precincts, tiles, components, code-block styles, COC / QCC / RGN / POC / PPM / PPT) is refused as CCT_E_J2K: a
+    decision about scope, so a caller may fall back on a host decoder for exactly those.  With out_dev it fills that
+    DeviceBuffer and returns the shape, like decode_batch.  With raise_errors=False it returns (array or shape, status) with
+    status[i] 0, CCT_E_J2K (14: the structure), CCT_E_MIXED (10: not rows x cols, or a precision above bits) or CCT_E_STREAM
+    (4: the packets); include/compact_hip.h lists the cases.  The raster of a refused file is unspecified.  Arguments are
+    checked before any device call."""
+    rows, cols, bits, shift = _ints(rows=rows, cols=cols, bits=bits, shift=shift)
+    if bits not in (8, 16):
+        raise ValueError(f"JPEG 2000 rasters of {bits} bits allocated: 8 or 16")
+    if not 0 <= shift <= 15:
+        raise ValueError(f"shift {shift}: 0 to 15")
+    if not 1 <= rows <= 65535 or not 1 <= cols <= 65535 or rows * cols > _JPL_MAX_PIXELS:
+        raise ValueError(f"JPEG 2000 frame of {rows} x {cols} samples: rows and cols are 1 to 65535, at most {_JPL_MAX_PIXELS} pixels")
+    files = _file_list(files, "jpeg2000_decode_batch", "file", "a JPEG 2000 file")
+    _check_out_dev(out_dev)
+    n, dt = len(files), np.dtype(np.uint8 if bits == 8 else np.uint16)
+    if n == 0:
+        return _no_rasters((0, rows, cols), dt, out_dev, raise_errors)
+    L = _ffi.lib()
+    blob, offs = _archive(files)
+    return _decode_rasters(lambda *to: L.cct_j2k_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, shift, *to), n, rows,
+                           cols, dt, out_dev, raise_errors, (_ffi.E_J2K, _ffi.E_MIXED, _ffi.E_STREAM))

@@ -492,4 +492,89 @@ inline uint32_t j2k_headers(uint32_t rows, uint32_t cols, uint32_t precision, ui
 	return n;
 }
 
+// ---- JPEG 2000 Part-1 lossless decoder (jpeg2000_decode_kernels.hip) ------------------------------
+// tests/jpeg2000_decode_model.py states it.  The host walks the markers (api_jpeg2000.cpp) and lays every distinct coding
+// (levels, code-block exponents, Mb per subband) out once per call (j2k_dec_layout): subbands in packet order, code-blocks in
+// raster order, in the plane layout of the encoder.  A file reaches the device as the byte range of its tile data and a
+// J2kDecFile; its state on the device is one J2kDecCb per code-block, the nodes of two tag trees per subband, a list of
+// the chunks its packets hold, and the codeword segments the chunks are gathered into.
+constexpr uint32_t J2K_DEC_MB_MAX = 19;     // magnitude bit-planes the Tier-1 word holds: bits 12 .. 30, the encoder's layout
+constexpr uint32_t J2K_DEC_TT_LEVELS = 16;  // 65535 / 4 + 1 = 16384 code-blocks a side: 15 levels
+constexpr uint32_t J2K_DEC_ST_STREAM = 1u;
+struct J2kDecBlock { uint16_t x0, y0, w, h; uint32_t orient, mb; };  // w, h <= 64
+struct J2kDecBand { uint32_t cb0, ncw, nch, mb, tt0; };  // cb0, tt0: its first block and tag-tree node within the layout
+struct J2kDecFile {
+	uint64_t src;              // offset of the tile data (behind SOD) in the upload; its segments go to the same offset of segs
+	uint32_t len;              // bytes of tile data
+	uint32_t slot;             // the raster it fills: images + slot * rows * cols
+	uint32_t precision, levels, layers, seq;  // seq 0: layer-major packets (LRCP), 1: resolution-major (the other four orders)
+	uint32_t blk0, nblocks;    // its layout's blocks in the block table
+	uint32_t band0;            // its layout's 1 + 3 * levels subbands in the band table
+	uint32_t cb0;              // its first J2kDecCb among the pass's
+	uint64_t tt0; uint32_t tt_nodes;  // its tag-tree bytes: 4 arrays of tt_nodes (inclusion low, value; zero planes low, value)
+	uint64_t chunk0; uint32_t chunk_cap;  // its chunk list
+	uint32_t xcb, ycb;         // code-block exponents: the LDS a block of this file takes
+};
+struct J2kDecCb {            // a code-block across the layers; its index minus the file's cb0 is its block in the layout
+	uint32_t file;             // whose it is
+	uint32_t passes, planes;   // coding passes so far; Mb - zero bit-planes
+	uint32_t bytes, seg;       // bytes so far; where its segment begins (relative to the file's src)
+	uint32_t lblock, included; // included: in some packet so far
+	uint32_t pend;             // the bytes it has in the current packet; while the chunks are placed, the bytes placed so far
+};
+struct J2kDecChunk { uint32_t cb, src, len, dst; };  // cb within the file; src in the tile data, dst in the segments, both relative to the file's src
+struct J2kDecArgs {
+	const uint8_t *files; uint8_t *segs;
+	const J2kDecFile *flist; uint32_t nfiles;
+	const J2kDecBlock *blocks; const J2kDecBand *bands;
+	J2kDecCb *cbs; uint32_t ncbs;
+	uint8_t *tt; J2kDecChunk *chunks;
+	uint32_t *status;          // nfiles, zero on entry: J2K_DEC_ST_STREAM
+	int32_t *plane_a, *plane_b;  // one rows x cols plane per slot each
+	uint32_t nslots, rows, cols, max_levels, out_bits, shift, stages;  // stages: 15 all; 1 parse, 2 Tier-1, 4 transform, 8 finish
+	void *images;
+};
+struct J2kDecRun { uint32_t cb0, ncbs, xcb, ycb; };  // consecutive files with the same code-block exponents: one Tier-1 launch
+hipError_t launch_j2k_decode(const J2kDecArgs &a, const J2kDecRun *runs, size_t nruns, hipStream_t st);
+inline size_t j2k_dec_lds_bytes(uint32_t xcb, uint32_t ycb) { return 776 + (size_t)((1u << xcb) + 2) * ((1u << ycb) + 2) * 4; }
+
+struct J2kDecLayout {
+	uint32_t levels, xcb, ycb, mb[25];
+	std::vector<J2kDecBlock> blocks;
+	std::vector<J2kDecBand> bands;
+	uint32_t tt_nodes = 0;
+};
+// caller-checked: rows, cols 1 .. 65535, levels 0 .. 8, xcb, ycb 2 .. 6, mb[] <= J2K_DEC_MB_MAX
+inline void j2k_dec_layout(uint32_t rows, uint32_t cols, J2kDecLayout &L)
+{
+	uint32_t dw[10], dh[10], nb = 0;
+	dw[0] = cols; dh[0] = rows;
+	for (uint32_t d = 1; d <= L.levels; d++) { dw[d] = (dw[d - 1] + 1) / 2; dh[d] = (dh[d - 1] + 1) / 2; }
+	const uint32_t cw = 1u << L.xcb, ch = 1u << L.ycb;
+	auto band = [&](uint32_t orient, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+		const uint32_t mb = L.mb[nb++], ncw = (w + cw - 1) / cw, nch = (h + ch - 1) / ch;
+		J2kDecBand bd{(uint32_t)L.blocks.size(), w && h ? ncw : 0, w && h ? nch : 0, mb, L.tt_nodes};
+		L.bands.push_back(bd);
+		if (!bd.ncw) return;
+		for (uint32_t pw = ncw, ph = nch;; pw = (pw + 1) / 2, ph = (ph + 1) / 2) { L.tt_nodes += pw * ph; if (pw == 1 && ph == 1) break; }
+		for (uint32_t by = 0; by < h; by += ch)
+			for (uint32_t bx = 0; bx < w; bx += cw) {
+				J2kDecBlock b{};
+				b.x0 = (uint16_t)(x0 + bx); b.y0 = (uint16_t)(y0 + by);
+				b.w = (uint16_t)(w - bx < cw ? w - bx : cw); b.h = (uint16_t)(h - by < ch ? h - by : ch);
+				b.orient = orient; b.mb = mb;
+				L.blocks.push_back(b);
+			}
+	};
+	L.blocks.clear(); L.bands.clear(); L.tt_nodes = 0;
+	band(0, 0, 0, dw[L.levels], dh[L.levels]);
+	for (uint32_t r = 1; r <= L.levels; r++) {
+		const uint32_t d = L.levels - r + 1, pw = dw[d - 1], ph = dh[d - 1], wl = dw[d], hl = dh[d];
+		band(1, wl, 0, pw - wl, hl);
+		band(2, 0, hl, wl, ph - hl);
+		band(3, wl, hl, pw - wl, ph - hl);
+	}
+	if (!L.tt_nodes) L.tt_nodes = 1;
+}
+
 }  // namespace cct

@@ -1,5 +1,5 @@
 // Host-side declarations shared by the translation units of libcompact_hip.so (api.cpp: context, encode, decode;
-// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec; api_jpeg2000.cpp: JPEG 2000 encoder),
+// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec; api_jpeg2000.cpp: JPEG 2000 codec),
 // and the scaffold every batch entry point is built from: StreamDrain, EventPair, Workspace, the decode slot lease, and the
 // copies of a pass (rasters_to_device, files_to_host, good_rasters_to_host).  Not part of the C ABI.
 #pragma once
@@ -141,7 +141,7 @@ int lease_decode_slot(DecLease &l);
 void set_last_kernel_ms(bool encode, float ms);  // cct_last_timings [0] / [4] of the calling thread
 void dicom_rle_release();        // cct_shutdown: workspaces and events of api_dicom_rle.cpp
 void jpegll_release();           // cct_shutdown: workspaces and events of api_jpeg_lossless.cpp
-void j2k_release();              // cct_shutdown: workspace and events of api_jpeg2000.cpp
+void j2k_release();              // cct_shutdown: workspaces and events of api_jpeg2000.cpp
 
 // h_offsets[0 .. n] of an archive must not decrease; `noun` is what the caller's message calls an entry ("frame", "file")
 inline int check_offsets(const uint64_t *h_offsets, int n, const char *noun)

@@ -64,7 +64,7 @@ extern "C" {
 #define CCT_E_PNG 11      /* cct_png_read_batch / cct_png_info: not a PNG this reader takes -> ValueError */
 #define CCT_E_CRC 12      /* cct_png_read_batch: a chunk's CRC-32 does not match           -> ValueError */
 #define CCT_E_JPEG 13     /* cct_jpegll_decode_batch / cct_jpegll_info: not a JPEG this reader takes -> ValueError */
-#define CCT_E_J2K 14      /* cct_j2k_info: not a JPEG 2000 codestream or JP2 file it reads          -> ValueError */
+#define CCT_E_J2K 14      /* cct_j2k_info / cct_j2k_decode_batch: not a JPEG 2000 codestream or JP2 file they read -> ValueError */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
 #define CCT_FLAG_FRACTAL 1u       /* transforms.fractal      (core.py:234) */
@@ -400,7 +400,7 @@ int cct_jpegll_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int
 int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits, void *images,
                             int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
 
-/* ---- JPEG 2000 Part-1 lossless encoder (T.800; DICOM transfer syntax 1.2.840.10008.1.2.4.90) ----
+/* ---- JPEG 2000 Part-1 lossless codec (T.800; DICOM transfer syntax 1.2.840.10008.1.2.4.90) ----
  * cct_j2k_encode_batch: n rasters of shape (rows, cols), C order, uint16 (src_bits 16) or uint8 (src_bits 8), on the
  * host or (images_on_device) the device, -> n files at h_out + i*out_stride with their sizes in h_out_sizes[i]; every
  * stage runs on the device (level shift and reversible 5/3 transform, Tier-1, Tier-2).  The sample coded is value << shift
@@ -428,6 +428,36 @@ int cct_j2k_encode_batch(const void *images, int images_on_device, int n, int ro
                          int shift, int levels, int codeblock, int jp2, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes,
                          uint32_t *h_status /* CCT_E_* per frame */);
 int cct_j2k_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
+
+/* ---- JPEG 2000 Part-1 lossless decoder ----
+ * cct_j2k_decode_batch: n files laid out back to back -> n*rows*cols uint16 (bits 16) or uint8 (bits 8) at `images`
+ * (host or device), images_cap_px counted in pixels; a decode slot; every stage on the device (packet parse, Tier-1, inverse
+ * 5/3 transform, level shift) in passes of at most 512 MB of device memory.  The sample written is value >> shift, so a
+ * file of cct_j2k_encode_batch at the same shift gives the raster back.  tests/jpeg2000_decode_model.py states the decoder.
+ * The host walks the boxes and markers and takes a file of any encoder within these limits: a raw codestream or a JP2 file
+ * (other boxes are skipped); SIZ with one unsigned component of 2 .. 16 bits, image and tile origins 0, one tile, subsampling
+ * 1; one tile-part (TPsot 0, TNsot 0 or 1; Psot 0: to the end of the codestream); COD with maximal precincts, no SOP, no
+ * EPH, any of the five progression orders, 1 .. 32 layers, no MCT, 0 .. 8 decomposition levels, code-blocks of 4 .. 64 by
+ * 4 .. 64, code-block style 0, the reversible 5/3 transform; QCD without quantization, any guard bits and exponents as long as
+ * no subband has more than 19 magnitude bit-planes (Mb = guard bits + exponent - 1; what the Tier-1 word holds: 16-bit data
+ * with two guard bits reaches 19 in HH); COM, TLM, PLM, PLT and CRG in either header (skipped); bytes behind EOC, and a
+ * missing EOC.  Y = rows, X = cols and a precision <= bits, or the file is CCT_E_MIXED.
+ * CCT_E_J2K, decided before upload (scope, not damage: a caller may hand these to a host decoder): the 9/7 transform or
+ * quantization style 1 or 2; user-defined precincts, SOP or EPH; a code-block style other than 0; COC, QCC, RGN, POC, PPM or
+ * PPT; more than one tile, tile-part or component, a signed component, an origin, subsampling; more than 8 levels or 32
+ * layers, a code-block side above 64; a marker segment whose length leaves the file, a marker this list does not name; COD
+ * or QCD missing, a QCD with too few exponents for the levels, no SOT or SOD; a subband of more than 19 bit-planes.
+ * CCT_E_STREAM, found on the device while it parses the packets: a packet header that runs past the end of the tile data,
+ * code-block lengths that sum past it, more zero bit-planes than Mb, more coding passes for a code-block over the layers
+ * than 3 (Mb - zero bit-planes) - 2, an Lblock above 32.  Damage inside the MQ-coded bytes cannot be detected by any decoder;
+ * the result is defined: 0xFF is read beyond a code-block's last byte, coefficients and lifting are two's complement modulo
+ * 2^32, the sample is clamped to 0 .. 2^precision - 1 after the level shift.  Refused files leave the others decoded,
+ * nothing is written outside a refused file's own rows*cols slot, and the call returns the first non-OK status.
+ * Whole-call errors, before the device is touched: CCT_E_ARG for rows or cols outside 1 .. 65535, rows*cols above 2^26,
+ * n < 0, bits other than 8 or 16, shift outside 0 .. 15; CCT_E_CAP for images_cap_px below n*rows*cols.
+ * cct_last_timings: [4] the decode kernels, HIP events, summed over the passes. */
+int cct_j2k_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits /* 8 or 16 */, int shift,
+                         void *images, int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
 
 /* ---- tuning / introspection (bench.py) --------------------------------------------- */
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per
