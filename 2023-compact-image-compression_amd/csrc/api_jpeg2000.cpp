@@ -57,18 +57,31 @@ int codestream_range(const uint8_t *f, size_t len, size_t *pos, size_t *end)
 	}
 }
 
-// tests/jpeg2000_model.py info(): CCT_OK or CCT_E_J2K.  Every read is checked against len first.
+// SOC and SIZ at the head of the codestream codestream_range finds: the raw fields of a SIZ of one component (Lsiz 41) for the
+// caller's own rules.  The segment lies inside the file, or (to_jp2c_end) inside the jp2c box, which ends at end <= len.
+struct Siz { uint32_t xs, ys, xo, yo, xt, yt, xto, yto, nc, ssiz, xr, yr; size_t next, end; };  // next: the marker behind SIZ; end: of the codestream
+int read_siz(const uint8_t *f, size_t len, bool to_jp2c_end, Siz &z)
+{
+	size_t pos;
+	if (codestream_range(f, len, &pos, &z.end)) return CCT_E_J2K;
+	const size_t room = (to_jp2c_end ? z.end : len) - pos;
+	if (room < 6 || f[pos] != 0xFF || f[pos + 1] != 0x4F || f[pos + 2] != 0xFF || f[pos + 3] != 0x51) return CCT_E_J2K;
+	const size_t lsiz = be16(f + pos + 4);
+	if (lsiz != 41 || room - 4 < lsiz) return CCT_E_J2K;
+	const uint8_t *s = f + pos + 6;  // Rsiz 2, Xsiz, Ysiz, XOsiz, YOsiz, XTsiz, YTsiz, XTOsiz, YTOsiz 4 each, Csiz 2, Ssiz, XRsiz, YRsiz 1 each
+	z.xs = be32(s + 2); z.ys = be32(s + 6); z.xo = be32(s + 10); z.yo = be32(s + 14); z.xt = be32(s + 18); z.yt = be32(s + 22);
+	z.xto = be32(s + 26); z.yto = be32(s + 30); z.nc = be16(s + 34); z.ssiz = s[36]; z.xr = s[37]; z.yr = s[38];
+	z.next = pos + 4 + lsiz;
+	return CCT_OK;
+}
+
+// tests/jpeg2000_model.py info(): CCT_OK or CCT_E_J2K.  SIZ is bounded by the file; an image origin and a precision of 1 pass.
 int parse_file(const uint8_t *f, size_t len, int *rows, int *cols, int *precision)
 {
-	size_t pos, end;
-	if (codestream_range(f, len, &pos, &end)) return CCT_E_J2K;
-	if (len - pos < 6 || f[pos] != 0xFF || f[pos + 1] != 0x4F || f[pos + 2] != 0xFF || f[pos + 3] != 0x51) return CCT_E_J2K;
-	const size_t lsiz = be16(f + pos + 4);
-	if (lsiz != 41 || len - pos - 4 < lsiz) return CCT_E_J2K;  // one component; SIZ inside the file
-	const uint8_t *s = f + pos + 6;  // Rsiz 2, Xsiz, Ysiz, XOsiz, YOsiz, XTsiz, YTsiz, XTOsiz, YTOsiz 4 each, Csiz 2, Ssiz 1
-	const uint32_t xs = be32(s + 2), ys = be32(s + 6), xo = be32(s + 10), yo = be32(s + 14), nc = be16(s + 34), ssiz = s[36];
-	if (nc != 1 || (ssiz & 0x80) || ssiz + 1 > 16 || xs <= xo || ys <= yo || xs - xo > 0x7FFFFFFFu || ys - yo > 0x7FFFFFFFu) return CCT_E_J2K;
-	*rows = (int)(ys - yo); *cols = (int)(xs - xo); *precision = (int)ssiz + 1;
+	Siz z;
+	if (read_siz(f, len, false, z)) return CCT_E_J2K;
+	if (z.nc != 1 || (z.ssiz & 0x80) || z.ssiz + 1 > 16 || z.xs <= z.xo || z.ys <= z.yo || z.xs - z.xo > 0x7FFFFFFFu || z.ys - z.yo > 0x7FFFFFFFu) return CCT_E_J2K;
+	*rows = (int)(z.ys - z.yo); *cols = (int)(z.xs - z.xo); *precision = (int)z.ssiz + 1;
 	return CCT_OK;
 }
 
@@ -79,18 +92,12 @@ struct DecParsed {
 };
 int walk_file(const uint8_t *f, size_t len, DecParsed &o)
 {
-	size_t pos, end;
-	if (codestream_range(f, len, &pos, &end)) return CCT_E_J2K;
-	if (end - pos < 6 || f[pos] != 0xFF || f[pos + 1] != 0x4F || f[pos + 2] != 0xFF || f[pos + 3] != 0x51) return CCT_E_J2K;
-	const size_t lsiz = be16(f + pos + 4);
-	if (lsiz != 41 || end - pos - 4 < lsiz) return CCT_E_J2K;
-	const uint8_t *s = f + pos + 6;
-	const uint32_t xs = be32(s + 2), ys = be32(s + 6), nc = be16(s + 34), ssiz = s[36];
-	if (nc != 1 || (ssiz & 0x80) || ssiz + 1 < 2 || ssiz + 1 > 16 || !xs || !ys || xs > 0x7FFFFFFFu || ys > 0x7FFFFFFFu) return CCT_E_J2K;
-	if (be32(s + 10) || be32(s + 14) || be32(s + 26) || be32(s + 30) || be32(s + 18) < xs || be32(s + 22) < ys || s[37] != 1 || s[38] != 1)
-		return CCT_E_J2K;  // an origin, more than one tile, subsampling
-	o.rows = ys; o.cols = xs; o.precision = ssiz + 1;
-	pos += 4 + lsiz;
+	Siz z;
+	if (read_siz(f, len, true, z)) return CCT_E_J2K;
+	if (z.nc != 1 || (z.ssiz & 0x80) || z.ssiz + 1 < 2 || z.ssiz + 1 > 16 || !z.xs || !z.ys || z.xs > 0x7FFFFFFFu || z.ys > 0x7FFFFFFFu) return CCT_E_J2K;
+	if (z.xo || z.yo || z.xto || z.yto || z.xt < z.xs || z.yt < z.ys || z.xr != 1 || z.yr != 1) return CCT_E_J2K;  // an origin, more than one tile, subsampling
+	o.rows = z.ys; o.cols = z.xs; o.precision = z.ssiz + 1;
+	size_t pos = z.next, end = z.end;
 	bool have_sot = false, have_cod = false, have_qcd = false;
 	size_t sot = 0, nexp = 0;
 	uint32_t psot = 0, guard = 0;

@@ -368,10 +368,40 @@ struct JplDecArgs {
 };
 hipError_t launch_jpl_decode(const JplDecArgs &a, hipStream_t st);
 
+// ---- JPEG 2000 Part-1: what the layouts of the encoder and the decoder share -----------------------
+// The coefficients of all subbands share one rows x cols int32 plane in the Mallat arrangement (after a stage the LL band is
+// the top left corner), every code-block is a rectangle of it, the subbands are listed in packet order.  Device side: jpeg2000_device.h.
+struct J2kSizes { uint32_t w[10], h[10]; };  // [d]: the LL band after d decompositions, d <= levels <= 8
+inline J2kSizes j2k_level_sizes(uint32_t rows, uint32_t cols, uint32_t levels)
+{
+	J2kSizes z; z.w[0] = cols; z.h[0] = rows;
+	for (uint32_t d = 1; d <= levels; d++) { z.w[d] = (z.w[d - 1] + 1) / 2; z.h[d] = (z.h[d - 1] + 1) / 2; }
+	return z;
+}
+// band(orient, x0, y0, w, h) for every subband in packet order (tests/jpeg2000_model.py resolutions()): LL, then HL, LH, HH
+// of every resolution from the coarsest; orient 0 LL, 1 HL, 2 LH, 3 HH; a band may be empty (w or h 0)
+template <class F>
+inline void j2k_for_each_band(uint32_t rows, uint32_t cols, uint32_t levels, F &&band)
+{
+	const J2kSizes z = j2k_level_sizes(rows, cols, levels);
+	band(0u, 0u, 0u, z.w[levels], z.h[levels]);
+	for (uint32_t r = 1; r <= levels; r++) {
+		const uint32_t d = levels - r + 1, pw = z.w[d - 1], ph = z.h[d - 1], wl = z.w[d], hl = z.h[d];
+		band(1u, wl, 0u, pw - wl, hl);
+		band(2u, 0u, hl, wl, ph - hl);
+		band(3u, wl, hl, pw - wl, ph - hl);
+	}
+}
+// nodes of the tag tree (B.10.2) over ncw x nch >= 1 x 1 code-blocks
+inline uint32_t j2k_tt_nodes(uint32_t ncw, uint32_t nch)
+{
+	uint32_t nodes = 0;
+	for (uint32_t pw = ncw, ph = nch;; pw = (pw + 1) / 2, ph = (ph + 1) / 2) { nodes += pw * ph; if (pw == 1 && ph == 1) return nodes; }
+}
+
 // ---- JPEG 2000 Part-1 lossless encoder (jpeg2000_kernels.hip) -------------------------------------
-// tests/jpeg2000_model.py states the file.  The host lays the image out once per call (j2k_layout): the coefficients of all
-// subbands share one rows x cols int32 plane in the Mallat arrangement (after a stage the LL band is the top left corner),
-// every code-block is a rectangle of that plane, and the subbands are listed in packet order.
+// tests/jpeg2000_model.py states the file.  The host lays the image out once per call (j2k_layout): on top of the band walk
+// above, the Mb of every subband from its gain, the square code-blocks, and a slab of the workspace for each.
 constexpr uint32_t J2K_ST_OVERFLOW = 1u;  // a sample >= 2^precision after the shift (the convert kernel sets it)
 constexpr uint32_t J2K_ST_CAP = 2u;       // a code-block's bytes or a packet header would leave its space
 constexpr uint32_t J2K_ST_GUARD = 4u;     // a coefficient needs more bit-planes than the guard bits allow (Tier-1 sets it)
@@ -421,21 +451,18 @@ struct J2kLayout {
 	size_t slab_bytes = 0;   // a frame's slabs
 	size_t bound = 0;        // cct_j2k_bound's expression for this layout
 };
-// Subbands in packet order and their code-blocks in raster order (tests/jpeg2000_model.py resolutions()); caller-checked
-// arguments: rows, cols 1 .. 65535, precision 2 .. 16, levels 0 .. 8, codeblock 32 or 64.
+// Subbands in packet order and their code-blocks in raster order; caller-checked arguments: rows, cols 1 .. 65535,
+// precision 2 .. 16, levels 0 .. 8, codeblock 32 or 64.
 inline void j2k_layout(uint32_t rows, uint32_t cols, uint32_t precision, uint32_t levels, uint32_t codeblock, J2kLayout &L)
 {
-	uint32_t dw[10], dh[10];
-	dw[0] = cols; dh[0] = rows;
-	for (uint32_t d = 1; d <= levels; d++) { dw[d] = (dw[d - 1] + 1) / 2; dh[d] = (dh[d - 1] + 1) / 2; }
-	auto band = [&](uint32_t orient, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+	L.blocks.clear(); L.bands.clear(); L.tt_nodes = 1; L.slab_bytes = 0;
+	j2k_for_each_band(rows, cols, levels, [&](uint32_t orient, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
 		const uint32_t gain = orient == 0 ? 0 : orient == 3 ? 2 : 1, mb = J2K_GUARD_BITS + precision + gain - 1;
 		const uint32_t ncw = (w + codeblock - 1) / codeblock, nch = (h + codeblock - 1) / codeblock;
 		J2kBand bd{(uint32_t)L.blocks.size(), w && h ? ncw : 0, w && h ? nch : 0, mb};
 		L.bands.push_back(bd);
 		if (!bd.ncw) return;
-		uint32_t nodes = 0;
-		for (uint32_t pw = ncw, ph = nch;; pw = (pw + 1) / 2, ph = (ph + 1) / 2) { nodes += pw * ph; if (pw == 1 && ph == 1) break; }
+		const uint32_t nodes = j2k_tt_nodes(ncw, nch);
 		L.tt_nodes = nodes > L.tt_nodes ? nodes : L.tt_nodes;
 		for (uint32_t by = 0; by < h; by += codeblock)
 			for (uint32_t bx = 0; bx < w; bx += codeblock) {
@@ -447,15 +474,7 @@ inline void j2k_layout(uint32_t rows, uint32_t cols, uint32_t precision, uint32_
 				L.slab_bytes += b.slab_cap;
 				L.blocks.push_back(b);
 			}
-	};
-	L.blocks.clear(); L.bands.clear(); L.tt_nodes = 1; L.slab_bytes = 0;
-	band(0, 0, 0, dw[levels], dh[levels]);
-	for (uint32_t r = 1; r <= levels; r++) {
-		const uint32_t d = levels - r + 1, pw = dw[d - 1], ph = dh[d - 1], wl = dw[d], hl = dh[d];
-		band(1, wl, 0, pw - wl, hl);
-		band(2, 0, hl, wl, ph - hl);
-		band(3, wl, hl, pw - wl, ph - hl);
-	}
+	});
 	L.bound = J2K_HDR_MAX + 2 + (size_t)(levels + 1) * J2K_PKT_BYTES + L.blocks.size() * J2K_CB_HDR_BYTES + L.slab_bytes;
 }
 
@@ -494,11 +513,11 @@ inline uint32_t j2k_headers(uint32_t rows, uint32_t cols, uint32_t precision, ui
 
 // ---- JPEG 2000 Part-1 lossless decoder (jpeg2000_decode_kernels.hip) ------------------------------
 // tests/jpeg2000_decode_model.py states it.  The host walks the markers (api_jpeg2000.cpp) and lays every distinct coding
-// (levels, code-block exponents, Mb per subband) out once per call (j2k_dec_layout): subbands in packet order, code-blocks in
-// raster order, in the plane layout of the encoder.  A file reaches the device as the byte range of its tile data and a
-// J2kDecFile; its state on the device is one J2kDecCb per code-block, the nodes of two tag trees per subband, a list of
-// the chunks its packets hold, and the codeword segments the chunks are gathered into.
-constexpr uint32_t J2K_DEC_MB_MAX = 19;     // magnitude bit-planes the Tier-1 word holds: bits 12 .. 30, the encoder's layout
+// (levels, code-block exponents, Mb per subband) out once per call (j2k_dec_layout): on top of the same band walk, the Mb of
+// every subband from QCD, where its tag trees begin, and the rectangular code-blocks.  A file reaches the device as the byte
+// range of its tile data and a J2kDecFile; its state on the device is one J2kDecCb per code-block, the nodes of two tag trees
+// per subband, a list of the chunks its packets hold, and the codeword segments the chunks are gathered into.
+constexpr uint32_t J2K_DEC_MB_MAX = 19;     // magnitude bit-planes the Tier-1 word holds: bits 12 .. 30 (jpeg2000_device.h)
 constexpr uint32_t J2K_DEC_TT_LEVELS = 16;  // 65535 / 4 + 1 = 16384 code-blocks a side: 15 levels
 constexpr uint32_t J2K_DEC_ST_STREAM = 1u;
 struct J2kDecBlock { uint16_t x0, y0, w, h; uint32_t orient, mb; };  // w, h <= 64
@@ -547,16 +566,15 @@ struct J2kDecLayout {
 // caller-checked: rows, cols 1 .. 65535, levels 0 .. 8, xcb, ycb 2 .. 6, mb[] <= J2K_DEC_MB_MAX
 inline void j2k_dec_layout(uint32_t rows, uint32_t cols, J2kDecLayout &L)
 {
-	uint32_t dw[10], dh[10], nb = 0;
-	dw[0] = cols; dh[0] = rows;
-	for (uint32_t d = 1; d <= L.levels; d++) { dw[d] = (dw[d - 1] + 1) / 2; dh[d] = (dh[d - 1] + 1) / 2; }
 	const uint32_t cw = 1u << L.xcb, ch = 1u << L.ycb;
-	auto band = [&](uint32_t orient, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+	uint32_t nb = 0;
+	L.blocks.clear(); L.bands.clear(); L.tt_nodes = 0;
+	j2k_for_each_band(rows, cols, L.levels, [&](uint32_t orient, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
 		const uint32_t mb = L.mb[nb++], ncw = (w + cw - 1) / cw, nch = (h + ch - 1) / ch;
 		J2kDecBand bd{(uint32_t)L.blocks.size(), w && h ? ncw : 0, w && h ? nch : 0, mb, L.tt_nodes};
 		L.bands.push_back(bd);
 		if (!bd.ncw) return;
-		for (uint32_t pw = ncw, ph = nch;; pw = (pw + 1) / 2, ph = (ph + 1) / 2) { L.tt_nodes += pw * ph; if (pw == 1 && ph == 1) break; }
+		L.tt_nodes += j2k_tt_nodes(ncw, nch);
 		for (uint32_t by = 0; by < h; by += ch)
 			for (uint32_t bx = 0; bx < w; bx += cw) {
 				J2kDecBlock b{};
@@ -565,15 +583,7 @@ inline void j2k_dec_layout(uint32_t rows, uint32_t cols, J2kDecLayout &L)
 				b.orient = orient; b.mb = mb;
 				L.blocks.push_back(b);
 			}
-	};
-	L.blocks.clear(); L.bands.clear(); L.tt_nodes = 0;
-	band(0, 0, 0, dw[L.levels], dh[L.levels]);
-	for (uint32_t r = 1; r <= L.levels; r++) {
-		const uint32_t d = L.levels - r + 1, pw = dw[d - 1], ph = dh[d - 1], wl = dw[d], hl = dh[d];
-		band(1, wl, 0, pw - wl, hl);
-		band(2, 0, hl, wl, ph - hl);
-		band(3, wl, hl, pw - wl, ph - hl);
-	}
+	});
 	if (!L.tt_nodes) L.tt_nodes = 1;
 }
 

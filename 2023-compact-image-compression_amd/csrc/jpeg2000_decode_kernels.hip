@@ -6,10 +6,11 @@
 //              packet headers bit by bit (B.10: a stuffed bit behind every 0xFF, inclusion and zero-bit-plane tag trees,
 //              Table B.4, Lblock, lengths) in one of the two packet sequences, keeps per code-block what the layers add up to
 //              and lists the chunks of codeword bytes; then the waves gather every block's chunks into one segment.
-//   2 tier1    one wave per code-block (Annex D).  LDS as in the encoder: one word per sample with a one-sample border
-//              (neighbour significance, state, sign, magnitude), the two context tables, the MQ table and the contexts.  The
-//              lanes clear the block and build the tables, lane 0 runs exactly the passes the packets declared through the MQ
-//              decoder (C.3), the lanes write the signed coefficients into the plane.  A block no packet included is zeros.
+//   2 tier1    one wave per code-block (Annex D).  LDS holds what the encoder's holds, laid out by jpeg2000_device.h, which
+//              both include: one word per sample with a one-sample border (neighbour significance, state, sign, magnitude),
+//              the two context tables, the MQ table and the contexts.  The lanes clear the block and build the tables, lane 0
+//              runs exactly the passes the packets declared through the MQ decoder (C.3), the lanes write the signed
+//              coefficients into the plane.  A block no packet included is zeros.
 //   3 idwt     per level from the coarsest, rows and then columns, one lane per output sample, plane_a -> plane_b -> plane_a:
 //              x(2n) = s(n) - floor((d(n-1) + d(n) + 2) / 4), x(2n+1) = d(n) + floor((x(2n) + x(2n+2)) / 2), whole-sample
 //              symmetric extension, modulo 2^32.
@@ -27,6 +28,7 @@
 #include <algorithm>
 
 #include "cct_internal.h"
+#include "jpeg2000_device.h"
 #include "../../include/compact_hip.h"
 
 #ifndef J2K_DEC_DYNAMIC_LDS  // the host emulation supplies the launch's bytes its own way
@@ -59,24 +61,13 @@ struct DecBits {  // packet header bits (B.10.1); past the end: err, and zeros
 	}
 };
 
-struct DecTagTree {  // B.10.2: the shape of both trees of a subband; a value of 255 is not known yet
-	uint32_t nlev, off[J2K_DEC_TT_LEVELS], lw[J2K_DEC_TT_LEVELS];
-	__device__ void shape(uint32_t ncw, uint32_t nch)
-	{
-		uint32_t pw = ncw, ph = nch, o = 0;
-		nlev = 0;
-		for (;;) {
-			off[nlev] = o; lw[nlev] = pw;
-			nlev++;
-			if ((pw == 1 && ph == 1) || nlev == J2K_DEC_TT_LEVELS) break;
-			o += pw * ph; pw = (pw + 1) / 2; ph = (ph + 1) / 2;
-		}
-	}
+struct DecTagTree {
+	TagTreeShape<J2K_DEC_TT_LEVELS> at;  // the shape of both trees of a subband; a value of 255 is not known yet
 	__device__ bool decode(DecBits &br, uint8_t *low, uint8_t *val, uint32_t x, uint32_t y, uint32_t threshold) const  // threshold <= 33
 	{
 		uint32_t lo = 0, k = 0;
-		for (int lv = (int)nlev - 1; lv >= 0; lv--) {
-			k = off[lv] + (y >> lv) * lw[lv] + (x >> lv);
+		for (int lv = (int)at.nlev - 1; lv >= 0; lv--) {
+			k = at.node(lv, x, y);
 			lo = std::max<uint32_t>(lo, low[k]);
 			while (lo < threshold && lo < val[k]) {
 				if (br.get()) val[k] = (uint8_t)lo;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(256) void j2k_dec_parse_kernel(J2kDecArgs a)
 					const J2kDecBand bd = bands[b];
 					const uint32_t nb = bd.ncw * bd.nch;  // cb0 + nb <= nblocks, tt0 + nodes <= tt_nodes by the host's layout
 					if (!nb) continue;
-					tree.shape(bd.ncw, bd.nch);
+					tree.at.shape(bd.ncw, bd.nch);
 					uint8_t *il = tt + bd.tt0, *iv = il + T, *zl = iv + T, *zv = zl + T;
 					for (uint32_t k = 0; k < nb && !bad; k++) {
 						J2kDecCb c = cb[bd.cb0 + k];
@@ -192,58 +183,6 @@ __global__ __launch_bounds__(256) void j2k_dec_parse_kernel(J2kDecArgs a)
 }
 
 // ---- Tier-1 ---------------------------------------------------------------------------------------------------------
-
-// T.800 Table C.2 and the contexts, as in jpeg2000_kernels.hip: Qe | NMPS << 16 | NLPS << 22 | SWITCH << 28
-#define J2K_Q(qe, nm, nl, sw) ((uint32_t)(qe) | (uint32_t)(nm) << 16 | (uint32_t)(nl) << 22 | (uint32_t)(sw) << 28)
-__device__ const uint32_t J2K_DEC_MQ_TABLE[47] = {
-	J2K_Q(0x5601, 1, 1, 1), J2K_Q(0x3401, 2, 6, 0), J2K_Q(0x1801, 3, 9, 0), J2K_Q(0x0AC1, 4, 12, 0), J2K_Q(0x0521, 5, 29, 0), J2K_Q(0x0221, 38, 33, 0),
-	J2K_Q(0x5601, 7, 6, 1), J2K_Q(0x5401, 8, 14, 0), J2K_Q(0x4801, 9, 14, 0), J2K_Q(0x3801, 10, 14, 0), J2K_Q(0x3001, 11, 17, 0), J2K_Q(0x2401, 12, 18, 0),
-	J2K_Q(0x1C01, 13, 20, 0), J2K_Q(0x1601, 29, 21, 0), J2K_Q(0x5601, 15, 14, 1), J2K_Q(0x5401, 16, 14, 0), J2K_Q(0x5101, 17, 15, 0), J2K_Q(0x4801, 18, 16, 0),
-	J2K_Q(0x3801, 19, 17, 0), J2K_Q(0x3401, 20, 18, 0), J2K_Q(0x3001, 21, 19, 0), J2K_Q(0x2801, 22, 19, 0), J2K_Q(0x2401, 23, 20, 0), J2K_Q(0x2201, 24, 21, 0),
-	J2K_Q(0x1C01, 25, 22, 0), J2K_Q(0x1801, 26, 23, 0), J2K_Q(0x1601, 27, 24, 0), J2K_Q(0x1401, 28, 25, 0), J2K_Q(0x1201, 29, 26, 0), J2K_Q(0x1101, 30, 27, 0),
-	J2K_Q(0x0AC1, 31, 28, 0), J2K_Q(0x09C1, 32, 29, 0), J2K_Q(0x08A1, 33, 30, 0), J2K_Q(0x0521, 34, 31, 0), J2K_Q(0x0441, 35, 32, 0), J2K_Q(0x02A1, 36, 33, 0),
-	J2K_Q(0x0221, 37, 34, 0), J2K_Q(0x0141, 38, 35, 0), J2K_Q(0x0111, 39, 36, 0), J2K_Q(0x0085, 40, 37, 0), J2K_Q(0x0049, 41, 38, 0), J2K_Q(0x0025, 42, 39, 0),
-	J2K_Q(0x0015, 43, 40, 0), J2K_Q(0x0009, 44, 41, 0), J2K_Q(0x0005, 45, 42, 0), J2K_Q(0x0001, 45, 43, 0), J2K_Q(0x5601, 46, 46, 0),
-};
-#undef J2K_Q
-
-// the word of a sample: which of its eight neighbours are significant, its own state, its magnitude (19 bits at most)
-constexpr uint32_t D1_N = 1u, D1_S = 2u, D1_W = 4u, D1_E = 8u, D1_NW = 16u, D1_NE = 32u, D1_SW = 64u, D1_SE = 128u, D1_NBR = 255u;
-constexpr uint32_t D1_SIG = 1u << 8, D1_NEG = 1u << 9, D1_VISIT = 1u << 10, D1_REFINED = 1u << 11, D1_MAG_SHIFT = 12;
-constexpr uint32_t DCTX_SIGN = 9, DCTX_MAG = 14, DCTX_RL = 17, DCTX_UNI = 18, DN_CTX = 19;
-
-// Table D.1 from the neighbour bits of a state word
-__device__ __forceinline__ uint32_t dec_zc_context(uint32_t orient, uint32_t f)
-{
-	uint32_t hn = ((f >> 2) & 1) + ((f >> 3) & 1), vn = (f & 1) + ((f >> 1) & 1);
-	const uint32_t dn = ((f >> 4) & 1) + ((f >> 5) & 1) + ((f >> 6) & 1) + ((f >> 7) & 1);
-	if (orient == 1) { const uint32_t t = hn; hn = vn; vn = t; }
-	if (orient == 3) {
-		const uint32_t hv = hn + vn;
-		if (dn >= 3) return 8;
-		if (dn == 2) return hv >= 1 ? 7 : 6;
-		if (dn == 1) return hv >= 2 ? 5 : 3 + hv;
-		return hv >= 2 ? 2 : hv;
-	}
-	if (hn == 2) return 8;
-	if (hn == 1) return vn >= 1 ? 7 : (dn >= 1 ? 6 : 5);
-	if (vn == 2) return 4;
-	if (vn == 1) return 3;
-	return dn >= 2 ? 2 : dn;
-}
-
-// Table D.3 from (signs N S W E) << 4 | (significant N S W E): context | flip << 7
-__device__ __forceinline__ uint32_t dec_sc_context(uint32_t k)
-{
-	auto contrib = [&](uint32_t bit) { return !((k >> bit) & 1) ? 0 : ((k >> (4 + bit)) & 1) ? -1 : 1; };
-	int vc = std::max(-1, std::min(1, contrib(0) + contrib(1))), hc = std::max(-1, std::min(1, contrib(2) + contrib(3)));
-	uint32_t flip = 0;
-	if (hc < 0 || (hc == 0 && vc < 0)) { hc = -hc; vc = -vc; flip = 1; }
-	return (DCTX_SIGN + (uint32_t)(hc ? 3 + vc : vc)) | flip << 7;
-}
-
-__device__ __forceinline__ uint32_t dec_spp_candidate(uint32_t f) { return (uint32_t)(!(f & D1_SIG) && (f & D1_NBR)); }
-__device__ __forceinline__ uint32_t dec_mrp_candidate(uint32_t f) { return (uint32_t)((f & (D1_SIG | D1_VISIT)) == D1_SIG); }
 
 struct MqDecoder {  // Annex C.3; a byte at or beyond len reads as 0xFF, C is a 32-bit register
 	uint32_t a, c, ct, pos, len;
@@ -316,68 +255,65 @@ __global__ __launch_bounds__(64) void j2k_dec_tier1_kernel(J2kDecArgs a, uint32_
 		return;
 	}
 	for (uint32_t i = lane; i < FW * (h + 2); i += 64) s_w[i] = 0;
-	for (uint32_t i = lane; i < 256; i += 64) { s_zc[i] = (uint8_t)dec_zc_context(B.orient, i); s_sc[i] = (uint8_t)dec_sc_context(i); }
-	if (lane < 47) s_table[lane] = J2K_DEC_MQ_TABLE[lane];
-	if (lane < DN_CTX) s_ctx[lane] = J2K_DEC_MQ_TABLE[lane == 0 ? 4 : lane == DCTX_RL ? 3 : lane == DCTX_UNI ? 46 : 0];  // D.7, MPS 0
+	t1_load_tables(lane, B.orient, s_table, s_ctx, s_zc, s_sc);
 	__syncthreads();
 	if (lane == 0) {
 		MqDecoder mq;
 		mq.words = (const uint32_t *)a.segs; mq.base = (size_t)F.src + C.seg; mq.len = C.bytes; mq.table = s_table; mq.ctx = s_ctx;
 		mq.init();
-		auto significant = [&](uint32_t i) {  // decodes the sign of sample i and tells the eight neighbours -> D1_NEG or 0
+		auto significant = [&](uint32_t i) {  // decodes the sign of sample i and tells the eight neighbours -> T1_NEG or 0
 			const uint32_t n = s_w[i - FW], s = s_w[i + FW], wl = s_w[i - 1], e = s_w[i + 1];
-			const uint32_t k = ((n >> 8) & 1) | ((s >> 8) & 1) << 1 | ((wl >> 8) & 1) << 2 | ((e >> 8) & 1) << 3 | ((n >> 9) & 1) << 4 | ((s >> 9) & 1) << 5 |
-			                   ((wl >> 9) & 1) << 6 | ((e >> 9) & 1) << 7;
-			const uint32_t sc = s_sc[k];
+			const uint32_t sc = s_sc[t1_sign_key(n, s, wl, e)];
 			const uint32_t neg = mq.decode(sc & 127) ^ (sc >> 7);
-			s_w[i - FW] = n | D1_S; s_w[i + FW] = s | D1_N; s_w[i - 1] = wl | D1_E; s_w[i + 1] = e | D1_W;
-			s_w[i - FW - 1] |= D1_SE; s_w[i - FW + 1] |= D1_SW;
-			s_w[i + FW - 1] |= D1_NE; s_w[i + FW + 1] |= D1_NW;
-			return neg ? D1_NEG : 0u;
+			// t1_tell_neighbours, written out: through the helper this kernel measured 0.5 % slower at 64 x 64
+			s_w[i - FW] = n | T1_S; s_w[i + FW] = s | T1_N; s_w[i - 1] = wl | T1_E; s_w[i + 1] = e | T1_W;
+			s_w[i - FW - 1] |= T1_SE; s_w[i - FW + 1] |= T1_SW;
+			s_w[i + FW - 1] |= T1_NE; s_w[i + FW + 1] |= T1_NW;
+			return neg ? T1_NEG : 0u;
 		};
 		for (uint32_t k = 0; k < C.passes; k++) {  // passes <= 3 planes - 2 and planes <= 19: the plane's bit is 12 .. 30
-			const uint32_t kind = (k + 2) % 3, one = 1u << (D1_MAG_SHIFT + C.planes - 1 - (k + 2) / 3);
+			const uint32_t kind = (k + 2) % 3, one = 1u << (T1_MAG_SHIFT + C.planes - 1 - (k + 2) / 3);
 			for (uint32_t y0 = 0; y0 < h; y0 += 4)
 				for (uint32_t x = 0; x < w; x++) {
 					const uint32_t i0 = (y0 + 1) * FW + x + 1, y1 = std::min(y0 + 4, h);
 					if (kind == 0) {  // significance propagation
 						if (y0 + 4 <= h &&  // a column without a candidate decodes nothing, so nothing in it changes
-						    !(dec_spp_candidate(s_w[i0]) | dec_spp_candidate(s_w[i0 + FW]) | dec_spp_candidate(s_w[i0 + 2 * FW]) | dec_spp_candidate(s_w[i0 + 3 * FW])))
+						    !(spp_candidate(s_w[i0]) | spp_candidate(s_w[i0 + FW]) | spp_candidate(s_w[i0 + 2 * FW]) | spp_candidate(s_w[i0 + 3 * FW])))
 							continue;
 						for (uint32_t y = y0; y < y1; y++) {
 							const uint32_t i = (y + 1) * FW + x + 1, f = s_w[i];
-							if ((f & D1_SIG) || !(f & D1_NBR)) continue;
-							uint32_t nf = f | D1_VISIT;
-							if (mq.decode(s_zc[f & D1_NBR])) nf |= one | D1_SIG | significant(i);
+							if ((f & T1_SIG) || !(f & T1_NBR)) continue;
+							uint32_t nf = f | T1_VISIT;
+							if (mq.decode(s_zc[f & T1_NBR])) nf |= one | T1_SIG | significant(i);
 							s_w[i] = nf;  // its own word is not among the eight
 						}
 					} else if (kind == 1) {  // magnitude refinement
 						if (y0 + 4 <= h &&
-						    !(dec_mrp_candidate(s_w[i0]) | dec_mrp_candidate(s_w[i0 + FW]) | dec_mrp_candidate(s_w[i0 + 2 * FW]) | dec_mrp_candidate(s_w[i0 + 3 * FW])))
+						    !(mrp_candidate(s_w[i0]) | mrp_candidate(s_w[i0 + FW]) | mrp_candidate(s_w[i0 + 2 * FW]) | mrp_candidate(s_w[i0 + 3 * FW])))
 							continue;
 						for (uint32_t y = y0; y < y1; y++) {
 							const uint32_t i = (y + 1) * FW + x + 1, f = s_w[i];
-							if ((f & (D1_SIG | D1_VISIT)) != D1_SIG) continue;
-							const uint32_t bit = mq.decode(f & D1_REFINED ? DCTX_MAG + 2 : DCTX_MAG + ((f & D1_NBR) ? 1 : 0));
-							s_w[i] = f | D1_REFINED | (bit ? one : 0);
+							if ((f & (T1_SIG | T1_VISIT)) != T1_SIG) continue;
+							const uint32_t bit = mq.decode(f & T1_REFINED ? CTX_MAG + 2 : CTX_MAG + ((f & T1_NBR) ? 1 : 0));
+							s_w[i] = f | T1_REFINED | (bit ? one : 0);
 						}
 					} else {  // cleanup; it takes the visit marks back
 						uint32_t first = y0;
 						if (y0 + 4 <= h) {
 							const uint32_t f0 = s_w[i0], f1 = s_w[i0 + FW], f2 = s_w[i0 + 2 * FW], f3 = s_w[i0 + 3 * FW];
-							if (!((f0 | f1 | f2 | f3) & (D1_SIG | D1_VISIT | D1_NBR))) {
-								if (!mq.decode(DCTX_RL)) continue;
-								uint32_t r = mq.decode(DCTX_UNI) << 1;
-								r |= mq.decode(DCTX_UNI);
+							if (!((f0 | f1 | f2 | f3) & (T1_SIG | T1_VISIT | T1_NBR))) {
+								if (!mq.decode(CTX_RL)) continue;
+								uint32_t r = mq.decode(CTX_UNI) << 1;
+								r |= mq.decode(CTX_UNI);
 								const uint32_t i = i0 + r * FW, f = r == 0 ? f0 : r == 1 ? f1 : r == 2 ? f2 : f3;
-								s_w[i] = f | one | D1_SIG | significant(i);
+								s_w[i] = f | one | T1_SIG | significant(i);
 								first = y0 + r + 1;
 							}
 						}
 						for (uint32_t y = first; y < y1; y++) {
 							const uint32_t i = (y + 1) * FW + x + 1, f = s_w[i];
-							if (f & (D1_SIG | D1_VISIT)) { s_w[i] = f & ~D1_VISIT; continue; }
-							if (mq.decode(s_zc[f & D1_NBR])) s_w[i] = f | one | D1_SIG | significant(i);
+							if (f & (T1_SIG | T1_VISIT)) { s_w[i] = f & ~T1_VISIT; continue; }
+							if (mq.decode(s_zc[f & T1_NBR])) s_w[i] = f | one | T1_SIG | significant(i);
 						}
 					}
 				}
@@ -385,8 +321,8 @@ __global__ __launch_bounds__(64) void j2k_dec_tier1_kernel(J2kDecArgs a, uint32_
 	}
 	__syncthreads();
 	for (uint32_t i = lane; i < w * h; i += 64) {
-		const uint32_t y = i / w, x = i % w, f = s_w[(y + 1) * FW + x + 1], m = f >> D1_MAG_SHIFT;
-		dst[(size_t)y * a.cols + x] = (int32_t)(f & D1_NEG ? 0u - m : m);
+		const uint32_t y = i / w, x = i % w, f = s_w[(y + 1) * FW + x + 1], m = f >> T1_MAG_SHIFT;
+		dst[(size_t)y * a.cols + x] = (int32_t)(f & T1_NEG ? 0u - m : m);
 	}
 }
 
@@ -442,11 +378,9 @@ hipError_t launch_j2k_decode(const J2kDecArgs &a, const J2kDecRun *runs, size_t 
 	for (size_t r = 0; r < nruns; r++)
 		hipLaunchKernelGGL(j2k_dec_tier1_kernel, dim3(runs[r].ncbs), dim3(64), j2k_dec_lds_bytes(runs[r].xcb, runs[r].ycb), st, a, runs[r].cb0);
 	if (!(a.stages & 4)) return hipGetLastError();
-	uint32_t dw[10], dh[10];
-	dw[0] = a.cols; dh[0] = a.rows;
-	for (uint32_t d = 1; d <= a.max_levels; d++) { dw[d] = (dw[d - 1] + 1) / 2; dh[d] = (dh[d - 1] + 1) / 2; }
+	const J2kSizes z = j2k_level_sizes(a.rows, a.cols, a.max_levels);
 	for (uint32_t d = a.max_levels; d >= 1; d--) {
-		const uint32_t w = dw[d - 1], h = dh[d - 1];
+		const uint32_t w = z.w[d - 1], h = z.h[d - 1];
 		const dim3 grid((unsigned)(((size_t)a.nfiles * w * h + 255) / 256));
 		hipLaunchKernelGGL(j2k_dec_idwt_kernel, grid, dim3(256), 0, st, a, (const int32_t *)a.plane_a, a.plane_b, d, w, h, 0u);
 		hipLaunchKernelGGL(j2k_dec_idwt_kernel, grid, dim3(256), 0, st, a, (const int32_t *)a.plane_b, a.plane_a, d, w, h, 1u);

@@ -18,11 +18,13 @@
 // LDS of tier1: 64 x 64 blocks take 66 * 66 * 4 = 17 424 B of words + 780 B of tables = 18 204 B, 9 waves on a CU's
 // 163 840 B with 4 bytes to spare (one more byte of LDS costs a wave); 32 x 32 blocks take 5 404 B, 30 waves.  The waves
 // in flight are what Tier-1's throughput follows: DESIGN.md 5e has the measurements.
+// The MQ state table, the word of a sample, its contexts and the tag-tree shape are jpeg2000_device.h, shared with the decoder.
 // Bounds: a block's rectangle comes from the host's layout (inside rows x cols); LDS indices from (w, h) <= CB; every slab
 // byte is checked against slab_cap and every header byte against out_stride before it is stored.
 #include <algorithm>
 
 #include "cct_internal.h"
+#include "jpeg2000_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
@@ -66,59 +68,6 @@ __global__ __launch_bounds__(256) void j2k_dwt_kernel(const int32_t *src, int32_
 }
 
 // ---- Tier-1 ---------------------------------------------------------------------------------------------------------
-
-// T.800 Table C.2: Qe | NMPS << 16 | NLPS << 22 | SWITCH << 28
-#define J2K_Q(qe, nm, nl, sw) ((uint32_t)(qe) | (uint32_t)(nm) << 16 | (uint32_t)(nl) << 22 | (uint32_t)(sw) << 28)
-__device__ const uint32_t J2K_MQ_TABLE[47] = {
-	J2K_Q(0x5601, 1, 1, 1), J2K_Q(0x3401, 2, 6, 0), J2K_Q(0x1801, 3, 9, 0), J2K_Q(0x0AC1, 4, 12, 0), J2K_Q(0x0521, 5, 29, 0), J2K_Q(0x0221, 38, 33, 0),
-	J2K_Q(0x5601, 7, 6, 1), J2K_Q(0x5401, 8, 14, 0), J2K_Q(0x4801, 9, 14, 0), J2K_Q(0x3801, 10, 14, 0), J2K_Q(0x3001, 11, 17, 0), J2K_Q(0x2401, 12, 18, 0),
-	J2K_Q(0x1C01, 13, 20, 0), J2K_Q(0x1601, 29, 21, 0), J2K_Q(0x5601, 15, 14, 1), J2K_Q(0x5401, 16, 14, 0), J2K_Q(0x5101, 17, 15, 0), J2K_Q(0x4801, 18, 16, 0),
-	J2K_Q(0x3801, 19, 17, 0), J2K_Q(0x3401, 20, 18, 0), J2K_Q(0x3001, 21, 19, 0), J2K_Q(0x2801, 22, 19, 0), J2K_Q(0x2401, 23, 20, 0), J2K_Q(0x2201, 24, 21, 0),
-	J2K_Q(0x1C01, 25, 22, 0), J2K_Q(0x1801, 26, 23, 0), J2K_Q(0x1601, 27, 24, 0), J2K_Q(0x1401, 28, 25, 0), J2K_Q(0x1201, 29, 26, 0), J2K_Q(0x1101, 30, 27, 0),
-	J2K_Q(0x0AC1, 31, 28, 0), J2K_Q(0x09C1, 32, 29, 0), J2K_Q(0x08A1, 33, 30, 0), J2K_Q(0x0521, 34, 31, 0), J2K_Q(0x0441, 35, 32, 0), J2K_Q(0x02A1, 36, 33, 0),
-	J2K_Q(0x0221, 37, 34, 0), J2K_Q(0x0141, 38, 35, 0), J2K_Q(0x0111, 39, 36, 0), J2K_Q(0x0085, 40, 37, 0), J2K_Q(0x0049, 41, 38, 0), J2K_Q(0x0025, 42, 39, 0),
-	J2K_Q(0x0015, 43, 40, 0), J2K_Q(0x0009, 44, 41, 0), J2K_Q(0x0005, 45, 42, 0), J2K_Q(0x0001, 45, 43, 0), J2K_Q(0x5601, 46, 46, 0),
-};
-#undef J2K_Q
-
-// the word of a sample: which of its eight neighbours are significant, its own state, its magnitude (19 bits at most)
-constexpr uint32_t T1_N = 1u, T1_S = 2u, T1_W = 4u, T1_E = 8u, T1_NW = 16u, T1_NE = 32u, T1_SW = 64u, T1_SE = 128u, T1_NBR = 255u;
-constexpr uint32_t T1_SIG = 1u << 8, T1_NEG = 1u << 9, T1_VISIT = 1u << 10, T1_REFINED = 1u << 11, T1_MAG_SHIFT = 12;
-constexpr uint32_t CTX_SIGN = 9, CTX_MAG = 14, CTX_RL = 17, CTX_UNI = 18, N_CTX = 19;
-
-// Table D.1 from the neighbour bits of a state word
-__device__ __forceinline__ uint32_t zc_context(uint32_t orient, uint32_t f)
-{
-	uint32_t hn = ((f >> 2) & 1) + ((f >> 3) & 1), vn = (f & 1) + ((f >> 1) & 1);
-	const uint32_t dn = ((f >> 4) & 1) + ((f >> 5) & 1) + ((f >> 6) & 1) + ((f >> 7) & 1);
-	if (orient == 1) { const uint32_t t = hn; hn = vn; vn = t; }
-	if (orient == 3) {
-		const uint32_t hv = hn + vn;
-		if (dn >= 3) return 8;
-		if (dn == 2) return hv >= 1 ? 7 : 6;
-		if (dn == 1) return hv >= 2 ? 5 : 3 + hv;
-		return hv >= 2 ? 2 : hv;
-	}
-	if (hn == 2) return 8;
-	if (hn == 1) return vn >= 1 ? 7 : (dn >= 1 ? 6 : 5);
-	if (vn == 2) return 4;
-	if (vn == 1) return 3;
-	return dn >= 2 ? 2 : dn;
-}
-
-// Table D.3 from (signs N S W E) << 4 | (significant N S W E): context | flip << 7
-__device__ __forceinline__ uint32_t sc_context(uint32_t k)
-{
-	auto contrib = [&](uint32_t bit) { return !((k >> bit) & 1) ? 0 : ((k >> (4 + bit)) & 1) ? -1 : 1; };
-	int vc = std::max(-1, std::min(1, contrib(0) + contrib(1))), hc = std::max(-1, std::min(1, contrib(2) + contrib(3)));
-	uint32_t flip = 0;
-	if (hc < 0 || (hc == 0 && vc < 0)) { hc = -hc; vc = -vc; flip = 1; }
-	return (CTX_SIGN + (uint32_t)(hc ? 3 + vc : vc)) | flip << 7;
-}
-
-// what a pass codes: an insignificant sample with a significant neighbour; a significant sample not visited in this plane
-__device__ __forceinline__ uint32_t spp_candidate(uint32_t f) { return (uint32_t)(!(f & T1_SIG) && (f & T1_NBR)); }
-__device__ __forceinline__ uint32_t mrp_candidate(uint32_t f) { return (uint32_t)((f & (T1_SIG | T1_VISIT)) == T1_SIG); }
 
 struct MqCoder {  // Annex C.2; the byte before the first (pos -1) is imaginary
 	uint32_t a = 0x8000, c = 0, ct = 12, b = 0;
@@ -195,9 +144,7 @@ __global__ __launch_bounds__(64) void j2k_tier1_kernel(J2kArgs a)
 		}
 		s_w[i] = f;
 	}
-	for (uint32_t i = lane; i < 256; i += 64) { s_zc[i] = (uint8_t)zc_context(B.orient, i); s_sc[i] = (uint8_t)sc_context(i); }
-	if (lane < 47) s_table[lane] = J2K_MQ_TABLE[lane];
-	if (lane < N_CTX) s_ctx[lane] = J2K_MQ_TABLE[lane == 0 ? 4 : lane == CTX_RL ? 3 : lane == CTX_UNI ? 46 : 0];  // D.7, MPS 0
+	t1_load_tables(lane, B.orient, s_table, s_ctx, s_zc, s_sc);
 	for (int d = 32; d >= 1; d >>= 1) any |= (uint32_t)__shfl_xor((int)any, d);
 	__syncthreads();
 	if (lane != 0) return;
@@ -210,13 +157,9 @@ __global__ __launch_bounds__(64) void j2k_tier1_kernel(J2kArgs a)
 	mq.out = a.slabs + (size_t)frame * a.slab_stride + B.slab_off; mq.cap = B.slab_cap; mq.table = s_table; mq.ctx = s_ctx;
 	auto significant = [&](uint32_t i, uint32_t f) {  // codes the sign of sample i (word f) and tells the eight neighbours
 		const uint32_t n = s_w[i - FW], s = s_w[i + FW], wl = s_w[i - 1], e = s_w[i + 1];
-		const uint32_t k = ((n >> 8) & 1) | ((s >> 8) & 1) << 1 | ((wl >> 8) & 1) << 2 | ((e >> 8) & 1) << 3 | ((n >> 9) & 1) << 4 | ((s >> 9) & 1) << 5 |
-		                   ((wl >> 9) & 1) << 6 | ((e >> 9) & 1) << 7;
-		const uint32_t sc = s_sc[k];
+		const uint32_t sc = s_sc[t1_sign_key(n, s, wl, e)];
 		mq.encode(sc & 127, ((f >> 9) & 1) ^ (sc >> 7));
-		s_w[i - FW] = n | T1_S; s_w[i + FW] = s | T1_N; s_w[i - 1] = wl | T1_E; s_w[i + 1] = e | T1_W;
-		s_w[i - FW - 1] |= T1_SE; s_w[i - FW + 1] |= T1_SW;
-		s_w[i + FW - 1] |= T1_NE; s_w[i + FW + 1] |= T1_NW;
+		t1_tell_neighbours(s_w, i, FW, n, s, wl, e);
 	};
 	for (int p = (int)nplanes - 1; p >= 0; p--) {
 		const uint32_t pb = T1_MAG_SHIFT + (uint32_t)p;  // the plane's bit in a word
@@ -305,18 +248,15 @@ struct BitWriter {  // packet header bits (B.10.1): the byte behind a 0xFF carri
 	}
 };
 
-struct TagTree {  // B.10.2: level 0 the ncw x nch leaves, every further level half of it rounded up, down to 1 x 1
+struct TagTree {  // a node: its value, what the decoder knows to be a lower bound, whether it knows the value
 	uint8_t *val, *low, *known;
-	uint32_t nlev, off[J2K_TT_LEVELS], lw[J2K_TT_LEVELS];
-	__device__ void build(uint32_t ncw, uint32_t nch)  // leaves are in val[0 .. ncw * nch)
+	TagTreeShape<J2K_TT_LEVELS> at;
+	__device__ void build(uint32_t ncw, uint32_t nch)  // leaves are in val[0 .. ncw * nch); every other node is the minimum of its children
 	{
-		uint32_t pw = ncw, ph = nch, o = 0;
-		nlev = 0;
-		for (;;) {
-			off[nlev] = o; lw[nlev] = pw;
-			nlev++;
-			if ((pw == 1 && ph == 1) || nlev == J2K_TT_LEVELS) break;
-			const uint32_t cw = (pw + 1) / 2, ch = (ph + 1) / 2, co = o + pw * ph;
+		at.shape(ncw, nch);
+		uint32_t pw = ncw, ph = nch;
+		for (uint32_t lv = 0; lv + 1 < at.nlev; lv++) {
+			const uint32_t cw = (pw + 1) / 2, ch = (ph + 1) / 2, o = at.off[lv], co = at.off[lv + 1];
 			for (uint32_t y = 0; y < ch; y++)
 				for (uint32_t x = 0; x < cw; x++) {
 					uint32_t m = 255;
@@ -324,16 +264,16 @@ struct TagTree {  // B.10.2: level 0 the ncw x nch leaves, every further level h
 						for (uint32_t xx = 2 * x; xx < std::min(2 * x + 2, pw); xx++) m = std::min<uint32_t>(m, val[o + yy * pw + xx]);
 					val[co + y * cw + x] = (uint8_t)m;
 				}
-			o = co; pw = cw; ph = ch;
+			pw = cw; ph = ch;
 		}
-		const uint32_t total = o + pw * ph;
+		const uint32_t total = at.off[at.nlev - 1] + pw * ph;
 		for (uint32_t k = 0; k < total; k++) { low[k] = 0; known[k] = 0; }
 	}
 	__device__ void encode(BitWriter &bw, uint32_t x, uint32_t y, uint32_t threshold)
 	{
 		uint32_t lo = 0;
-		for (int lv = (int)nlev - 1; lv >= 0; lv--) {
-			const uint32_t k = off[lv] + (y >> lv) * lw[lv] + (x >> lv);
+		for (int lv = (int)at.nlev - 1; lv >= 0; lv--) {
+			const uint32_t k = at.node(lv, x, y);
 			lo = std::max<uint32_t>(lo, low[k]);
 			while (lo < threshold) {
 				if (lo >= val[k]) {
@@ -347,8 +287,6 @@ struct TagTree {  // B.10.2: level 0 the ncw x nch leaves, every further level h
 		}
 	}
 };
-
-__device__ __forceinline__ uint32_t bit_length(uint32_t v) { return v ? 32u - (uint32_t)__clz((int)v) : 0u; }
 
 __global__ __launch_bounds__(256) void j2k_tier2_kernel(J2kArgs a)
 {
@@ -440,12 +378,12 @@ hipError_t launch_j2k_encode(const J2kArgs &a, hipStream_t st)
 	const dim3 per_sample((unsigned)(((size_t)a.n * N + 255) / 256));
 	if (a.src_bits == 16) hipLaunchKernelGGL(j2k_convert_kernel<uint16_t>, per_sample, dim3(256), 0, st, a);
 	else hipLaunchKernelGGL(j2k_convert_kernel<uint8_t>, per_sample, dim3(256), 0, st, a);
-	uint32_t w = a.cols, h = a.rows;
+	const J2kSizes z = j2k_level_sizes(a.rows, a.cols, a.levels);
 	for (uint32_t l = 0; l < a.levels; l++) {
+		const uint32_t w = z.w[l], h = z.h[l];
 		const dim3 grid((unsigned)(((size_t)a.n * w * h + 255) / 256));
 		hipLaunchKernelGGL(j2k_dwt_kernel, grid, dim3(256), 0, st, (const int32_t *)a.plane_a, a.plane_b, a.n, a.rows, a.cols, w, h, 1u);
 		hipLaunchKernelGGL(j2k_dwt_kernel, grid, dim3(256), 0, st, (const int32_t *)a.plane_b, a.plane_a, a.n, a.rows, a.cols, w, h, 0u);
-		w = (w + 1) / 2; h = (h + 1) / 2;
 	}
 	if (!(a.stages & 2)) return hipGetLastError();
 	if (a.codeblock == 64) hipLaunchKernelGGL(j2k_tier1_kernel<64>, dim3(a.n * a.nblocks), dim3(64), 0, st, a);

@@ -7,11 +7,8 @@
 // Bounds: a device allocation is a malloc of its own, and what DevBuf::ensure adds on top of the bytes the caller asked for is
 // poisoned, so AddressSanitizer reports the first byte behind every buffer; the LDS of a launch is a malloc of exactly the
 // launch's bytes.  Slow (a thread per lane): small shapes.  It checks the algorithm and the bounds, not the timing.
-#include "hip/hip_runtime.h"
+#include "emu_common.h"
 #include <sanitizer/asan_interface.h>
-thread_local dim3 threadIdx, blockIdx, blockDim;
-BlockCtx *g_blk;
-static inline int __clz(int x) { return x ? __builtin_clz((unsigned)x) : 32; }
 static uint32_t *g_dyn_lds;
 #define J2K_DEC_DYNAMIC_LDS(name) uint32_t *name = g_dyn_lds
 #undef hipLaunchKernelGGL
@@ -62,8 +59,6 @@ void set_last_kernel_ms(bool, float) {}
 hipError_t launch_j2k_encode(const J2kArgs &, hipStream_t) { return hipSuccess; }  // the encoder has an emulation of its own
 }  // namespace cct
 
-#include <fstream>
-#include <iterator>
 // emu rows cols bits shift in.bin out.bin; in.bin: u32 n, n + 1 u64 offsets, the files; out.bin: i32 rc, n u32 statuses, n rasters
 int main(int argc, char **argv)
 {

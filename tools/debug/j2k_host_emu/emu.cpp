@@ -5,19 +5,9 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I../rle_host_emu -x c++ emu.cpp -o emu -lpthread && python drive.py
 // Slow (a thread per lane): small shapes.  It checks the algorithm and the bounds, not the timing.  Every device buffer is
 // followed by a guard that must come back untouched; `slab_div` > 1 shrinks the slabs to exercise the capacity check.
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim;
-BlockCtx *g_blk;
-static inline uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-static inline int __clz(int x) { return x ? __builtin_clz((unsigned)x) : 32; }
-static inline int __shfl_xor(int v, int m) { return (int)wave_xchg((uint32_t)v, (int)(threadIdx.x & 63) ^ m); }
+#include "emu_common.h"
 #include "../../../2023-compact-image-compression_amd/csrc/jpeg2000_kernels.hip"
 using namespace cct;
-#include <fstream>
-#include <iterator>
-static std::vector<uint8_t> rd(const char *p) { std::ifstream f(p, std::ios::binary); return std::vector<uint8_t>(std::istreambuf_iterator<char>(f), {}); }
-constexpr size_t GUARD = 256;
-static bool guard_ok(const std::vector<uint8_t> &v, size_t used) { for (size_t k = used; k < v.size(); k++) if (v[k] != 0xEE) return false; return true; }
 // emu src_bits precision shift levels codeblock jp2 rows cols n slab_div in.bin out.bin
 int main(int argc, char **argv)
 {

@@ -4,20 +4,9 @@
 // files of tests/jpeg_lossless_model.py and compares.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I../rle_host_emu -x c++ emu.cpp -o emu -lpthread && python drive.py
 // Slow (a thread per lane): small shapes.  It checks the algorithm and the bounds, not the timing.
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim;
-BlockCtx *g_blk;
-static inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-static inline uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-static inline int __clz(int x) { return x ? __builtin_clz((unsigned)x) : 32; }
-static inline int __popc(unsigned x) { return __builtin_popcount(x); }
+#include "emu_common.h"
 #include "../../../2023-compact-image-compression_amd/csrc/jpeg_lossless_kernels.hip"
 using namespace cct;
-#include <fstream>
-#include <iterator>
-static std::vector<uint8_t> rd(const char *p) { std::ifstream f(p, std::ios::binary); return std::vector<uint8_t>(std::istreambuf_iterator<char>(f), {}); }
-constexpr size_t GUARD = 256;
-static bool guard_ok(const std::vector<uint8_t> &v, size_t used) { for (size_t k = used; k < v.size(); k++) if (v[k] != 0xEE) return false; return true; }
 // encode: e src_bits precision rows cols n restart_rows in.bin out.bin
 // decode: d rows cols out_bits nslots job.bin files.bin out.bin   (job.bin: per frame 13 uint32 -- src, len, slot, ss, pt, P, ri,
 //         nval, then 16 + 20 bytes BITS / HUFFVAL)

@@ -4,15 +4,10 @@
 // under AddressSanitizer / UBSan.  drive.py feeds it the rasters and frames of tests/dicom_rle_model.py and compares.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I. -x c++ emu.cpp -o emu -lpthread && python drive.py enc|dec|tile
 // Slow (a thread per lane): shapes of a few rows.  It checks the algorithm and the bounds, not the timing.
-#include "hip/hip_runtime.h"
-thread_local dim3 threadIdx, blockIdx, blockDim;
-BlockCtx *g_blk;
+#include "emu_common.h"
 #include "../../../2023-compact-image-compression_amd/csrc/dicom_rle_kernels.hip"
 using namespace cct;
 // encode: argv: e planes rows cols n in.bin out.bin ; decode: d N step nseg segs.bin frames.bin out.bin
-#include <fstream>
-#include <iterator>
-static std::vector<uint8_t> rd(const char *p) { std::ifstream f(p, std::ios::binary); return std::vector<uint8_t>(std::istreambuf_iterator<char>(f), {}); }
 int main(int argc, char **argv)
 {
 	if (argv[1][0] == 'e') {

@@ -57,6 +57,11 @@ static inline uint64_t __ballot(bool b)
 	pthread_barrier_wait(&g_blk->wbar[w]);
 	return r;
 }
+static inline int __shfl_xor(int v, int m) { return (int)wave_xchg((uint32_t)v, (int)(threadIdx.x & 63) ^ m); }
+static inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+static inline uint32_t atomicOr(uint32_t *p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
+static inline int __clz(int x) { return x ? __builtin_clz((unsigned)x) : 32; }
+static inline int __popc(unsigned x) { return __builtin_popcount(x); }
 static inline int __clzll(long long x) { return x ? __builtin_clzll((unsigned long long)x) : 64; }
 static inline int __ffsll(long long x) { return __builtin_ffsll(x); }
 static inline hipError_t hipGetLastError() { return 0; }
