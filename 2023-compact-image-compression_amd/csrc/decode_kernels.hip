@@ -18,6 +18,7 @@
 // has no defined result (a jump that is not at a block boundary, two jump bytes in a row, a jump onto a claimed
 // block, truncation) set CCT_ST_STREAM instead of replaying its accidental behaviour on them; see DESIGN.md.
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
@@ -124,23 +125,6 @@ __device__ __forceinline__ uint32_t map_compose(uint32_t later, uint32_t earlier
 	return map_apply(later, map_apply(earlier, 0)) | (map_apply(later, map_apply(earlier, 1)) << 1);
 }
 
-// cross-lane moves as DPP modifiers (VALU latency) instead of ds_bpermute (LDS latency); lanes without a source read OLD
-template <int CTRL, int OLD = 0, int ROW_MASK = 0xF>
-__device__ __forceinline__ uint32_t dpp_from(uint32_t v)
-{
-	return (uint32_t)__builtin_amdgcn_update_dpp(OLD, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
-{
-	v += dpp_from<0x111>(v);  // row_shr:1
-	v += dpp_from<0x112>(v);  // row_shr:2
-	v += dpp_from<0x114>(v);  // row_shr:4
-	v += dpp_from<0x118>(v);  // row_shr:8
-	v += dpp_from<0x142, 0, 0xA>(v);  // row_bcast:15 into rows 1 and 3
-	v += dpp_from<0x143, 0, 0xC>(v);  // row_bcast:31 into rows 2 and 3
-	return v;
-}
-
 struct Parse {  // what one lane knows about its segment after the workgroup scans
 	uint32_t entry;      // true entry state
 	uint32_t pix_base;   // pixel ordinal of its first pixel token (within the whole stream)
@@ -162,13 +146,13 @@ __device__ __forceinline__ Parse parse_step(const uint4 &w, uint32_t nxt, int nv
 	const SegStats s1 = seg_stats(w, nxt, sm, nvalid, 1);
 	// inclusive scan of state maps inside the wave (lanes without a source compose with the identity map, 2)
 	uint32_t m = s0.exit_state | (s1.exit_state << 1);
-	m = map_compose(m, dpp_from<0x111, 2>(m));
-	m = map_compose(m, dpp_from<0x112, 2>(m));
-	m = map_compose(m, dpp_from<0x114, 2>(m));
-	m = map_compose(m, dpp_from<0x118, 2>(m));
-	m = map_compose(m, dpp_from<0x142, 2, 0xA>(m));
-	m = map_compose(m, dpp_from<0x143, 2, 0xC>(m));
-	const uint32_t excl = dpp_from<0x138, 2>(m);  // wave_shr:1: the map of the lanes before this one
+	m = map_compose(m, dpp_move<DPP_ROW_SHR1>(m, 2));
+	m = map_compose(m, dpp_move<DPP_ROW_SHR2>(m, 2));
+	m = map_compose(m, dpp_move<DPP_ROW_SHR4>(m, 2));
+	m = map_compose(m, dpp_move<DPP_ROW_SHR8>(m, 2));
+	m = map_compose(m, dpp_move<DPP_ROW_BCAST15, 0xA>(m, 2));
+	m = map_compose(m, dpp_move<DPP_ROW_BCAST31, 0xC>(m, 2));
+	const uint32_t excl = dpp_move<DPP_WAVE_SHR1>(m, 2);  // the map of the lanes before this one
 	// scratch[0..15] holds the maps, scratch[16..47] the counts: a region is rewritten only after a barrier that every
 	// wave reaches after its reads of that region, so two barriers per step suffice
 	if (lane == 63) scratch[wave] = m;
@@ -183,8 +167,8 @@ __device__ __forceinline__ Parse parse_step(const uint4 &w, uint32_t nxt, int nv
 	p.entry = map_apply(excl, st_wave);
 	p.st = p.entry ? s1 : s0;
 	// scans of pixel count | jump count << 16 (both <= 16 per lane, <= 16384 per step) and of the delta sum
-	const uint32_t ipj = wave_incl_scan_u32(p.st.npix | (p.st.njump << 16));
-	const uint32_t iv = wave_incl_scan_u32((uint32_t)p.st.sdelta);
+	const uint32_t ipj = wave_incl_scan(p.st.npix | (p.st.njump << 16));
+	const uint32_t iv = wave_incl_scan((uint32_t)p.st.sdelta);
 	const uint32_t ip = ipj & 0xFFFFu, ij = ipj >> 16;
 	if (lane == 63) { scratch[16 + wave] = ipj; scratch[32 + wave] = iv; }
 	__syncthreads();
@@ -395,7 +379,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 			uint32_t r = ROLE_PARTNER, cnt = 0;
 			if (b < NB) { r = role_rd((uint32_t)b); cnt = (r == ROLE_PARTNER) ? 0u : (r ? 2u : 1u); }
 			const int lane = tid & 63, wave = tid >> 6, nw = T >> 6;
-			const uint32_t inc = wave_incl_scan_u32(cnt);
+			const uint32_t inc = wave_incl_scan(cnt);
 			if (lane == 63) scratch[wave] = inc;
 			__syncthreads();
 			uint32_t bs_ = 0, tot = 0;

@@ -42,6 +42,7 @@
 #include <algorithm>
 
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
@@ -121,20 +122,7 @@ __device__ __forceinline__ MatchRec checked_match(MatchRec r, uint32_t gen, uint
 // Per tile: wave-level match-any gives each lane its rank among the equal digits of its wave, the 16 per-wave
 // counts are prefix-summed per digit, and lanes scatter to offset[digit] + wave prefix + rank.  All waves of a
 // slice write the same 256 (128) output streams tile after tile, which keeps the partially written lines in L2.
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, which would serialise the
-// scattered stores of a tile with its barriers
-__device__ __forceinline__ void lds_barrier()
-{
-	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-	return v;
-}
-
+// (The barriers between a tile's scattered stores are lds_barrier(): __syncthreads() would drain vmcnt and serialise them.)
 template <bool FIRST, int HB>
 __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 {
@@ -164,10 +152,7 @@ __global__ void __launch_bounds__(1024) dfl_sort_pass_kernel(DeflateArgs a)
 		uint32_t v[4], sum = 0;
 #pragma unroll
 		for (int k = 0; k < 4; k++) { v[k] = offs[lane * 4 + k]; sum += v[k]; }
-		uint32_t inc = sum;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64); if (lane >= d) inc += o; }
-		uint32_t run = inc - sum;
+		uint32_t run = wave_incl_scan(sum) - sum;
 #pragma unroll
 		for (int k = 0; k < 4; k++) { offs[lane * 4 + k] = run; run += v[k]; }
 	}
@@ -553,12 +538,6 @@ __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const
 	}
 }
 
-// v of the lane below; lane 0 takes `fill` (DPP wave_shr:1 -- every lane of the wave must be enabled where this is called)
-__device__ __forceinline__ uint32_t wave_shift_up(uint32_t v, uint32_t fill)
-{
-	return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
-}
-
 // QL: the quarter chain (max_chain >> 2) ends inside the light walk (levels 4 and 5), so the lane records it on its own;
 // otherwise the light walk never gets past it and the quarter record is the full one.
 template <bool CMP, bool QL>
@@ -777,7 +756,7 @@ __global__ void __launch_bounds__(256) dfl_match_heavy_kernel(DeflateArgs a, int
 // rank of every eighth position among the ends at [3/4, 1) (in_stride / 8 words).
 __global__ void __launch_bounds__(256) dfl_run_lists_kernel(DeflateArgs a)
 {
-	__shared__ uint32_t wsum_e[4], wsum_s[4], base_es[2];
+	__shared__ uint32_t wsum[4], base_es[2];
 	const int s = blockIdx.y;
 	const uint32_t L = a.in_sizes[s];
 	const uint32_t c = blockIdx.x;
@@ -810,21 +789,11 @@ __global__ void __launch_bounds__(256) dfl_run_lists_kernel(DeflateArgs a)
 		me |= (uint32_t)(pub && r == 3u && p + 3 < L) << k;
 		ms |= (uint32_t)(pub && r >= 3u && !prev_eq) << k;
 	}
-	const uint32_t ne = (uint32_t)__popc(me), ns = (uint32_t)__popc(ms);
-	uint32_t inc_e = ne, inc_s = ns;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t oe = __shfl_up(inc_e, d, 64), os = __shfl_up(inc_s, d, 64);
-		if (lane >= d) { inc_e += oe; inc_s += os; }
-	}
-	if (lane == 63) { wsum_e[wave] = inc_e; wsum_s[wave] = inc_s; }
-	__syncthreads();
-	uint32_t ie = base_es[0] + inc_e - ne, is = base_es[1] + inc_s - ns, tot_e = base_es[0];
-	for (int w2 = 0; w2 < 4; w2++) {
-		const uint32_t te = wsum_e[w2], ts = wsum_s[w2];
-		if (w2 < wave) { ie += te; is += ts; }
-		tot_e += te;
-	}
+	// both counts in one scan: a workgroup has at most 8 * 256 = 2048 of either (its first barrier also publishes base_es)
+	uint32_t tot;
+	const uint32_t ex = wg_excl_scan<4>((uint32_t)__popc(me) | (uint32_t)__popc(ms) << 16, wsum, tot);
+	uint32_t ie = base_es[0] + (ex & 0xFFFFu), is = base_es[1] + (ex >> 16);
+	const uint32_t tot_e = base_es[0] + (tot & 0xFFFFu);
 	// rank table for the run matcher: ends put on the list by the positions before g (last quarter of the slice's buffer): the
 	// "last run end <= p" of a position is then one lookup and a step or two instead of a binary search of twelve dependent loads
 	if ((uint32_t)tid * 8 < (uint32_t)RUNLEN_OUT && g < L) re[3 * (a.in_stride >> 2) + (g >> 3)] = ie;
@@ -1133,7 +1102,7 @@ __global__ void __launch_bounds__(WALK_T) dfl_walk_kernel(DeflateArgs a, int n)
 	const size_t base = (size_t)s * a.in_stride;
 	const size_t bbase = (size_t)s * (a.in_stride / 64);
 	const uint32_t *exit_rec = a.exit_pos + base;  // (offset of the exit past the entry's block) | symbols << 16
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int tid = threadIdx.x;
 	const uint32_t seg = (((L + WALK_T - 1) / WALK_T) + 63) & ~63u;
 	const uint32_t seg_end = min(L, (uint32_t)(tid + 1) * seg);
 	uint32_t start = min(L, (uint32_t)tid * seg), land = start, cnt = 0;
@@ -1153,14 +1122,9 @@ __global__ void __launch_bounds__(WALK_T) dfl_walk_kernel(DeflateArgs a, int n)
 		if (moved) { start = pl; hop_through(); }
 	}
 	// symbols before this lane's segment
-	uint32_t inc = cnt;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-	if (lane == 63) s_wsum[wave] = inc;
-	__syncthreads();
-	uint32_t syms = inc - cnt;
-	for (int w = 0; w < wave; w++) syms += s_wsum[w];
-	if (tid == WALK_T - 1) a.total_syms[s] = syms + cnt;
+	uint32_t total;
+	uint32_t syms = wg_excl_scan<WALK_T / 64>(cnt, s_wsum, total);
+	if (tid == 0) a.total_syms[s] = total;
 	for (uint32_t cur = start; cur < seg_end;) {
 		const uint32_t b = cur >> 6;
 		a.blk_entry[bbase + b] = cur;
@@ -1228,13 +1192,8 @@ __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 		if (nvalid < 64) visited &= (1ull << nvalid) - 1ull;
 		const bool mine = (visited >> lane) & 1ull;
 		// exclusive prefix of symbol counts over the visited lanes
-		uint32_t v = mine ? cnt : 0u, inc = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t t = __shfl_up(inc, d);
-			if (lane >= d) inc += t;
-		}
-		uint32_t off = symbase + inc - v;
+		const uint32_t v = mine ? cnt : 0u;
+		uint32_t off = symbase + wave_incl_scan(v) - v;
 		if (mine) {
 			if (p == L - 1) a.postloop_lit[s] = 1;  // the literal tallied after deflate_slow's main loop
 			for (uint32_t t = 0; t < (len ? k : 1u); t++, off++) {  // literals
@@ -1618,11 +1577,10 @@ __device__ void scan_tree_wave(TreeScratch &S, const TreeView &t, int max_code)
 			}
 		}
 		const uint32_t ntok = nlit_head + nrep6 + nbig + tail_lit + (tail_sym != 0xFFFFFFFFu ? 1u : 0u);
-		uint32_t inc = ntok;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64); if (lane >= d) inc += o; }
+		uint32_t chunk_tok;
+		const uint32_t ex = wave_excl_scan(ntok, chunk_tok);
 		if (start) {
-			uint32_t w = base + inc - ntok;
+			uint32_t w = base + ex;
 			for (uint32_t i = 0; i < nlit_head; i++) tk[w++] = (uint16_t)val;
 			for (uint32_t i = 0; i < nrep6; i++) tk[w++] = (uint16_t)(16u | (3u << 5));
 			for (uint32_t i = 0; i < nbig; i++) tk[w++] = (uint16_t)(18u | (127u << 5));
@@ -1633,7 +1591,7 @@ __device__ void scan_tree_wave(TreeScratch &S, const TreeView &t, int max_code)
 			if (nbig) atomicAdd(&S.hdr_bits[18], nbig);
 			if (tail_sym != 0xFFFFFFFFu) atomicAdd(&S.hdr_bits[tail_sym & 31u], 1u);
 		}
-		base += (uint32_t)__shfl((int)inc, 63, 64);
+		base += chunk_tok;
 	}
 	if (lane == 0) S.ntok = (int)base;
 }
@@ -1666,11 +1624,10 @@ __device__ void send_header(TreeScratch &S)
 			nbits = cl + S.extra_bl[sym];
 			val = (uint32_t)S.bcode[sym] | (ex << cl);
 		}
-		uint32_t inc = nbits;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d, 64); if (lane >= d) inc += o; }
-		if (nbits) hdr_or(S, base + inc - nbits, val, nbits);
-		base += (uint32_t)__shfl((int)inc, 63, 64);
+		uint32_t chunk_bits;
+		const uint32_t ex = wave_excl_scan(nbits, chunk_bits);
+		if (nbits) hdr_or(S, base + ex, val, nbits);
+		base += chunk_bits;
 	}
 	if (lane == 0) S.hdr_nbits = base;
 }
@@ -2113,13 +2070,9 @@ __global__ void __launch_bounds__(256) dfl_emit_kernel(DeflateArgs a)
 			}
 			ltot += (uint32_t)nb;
 		}
-		// exclusive scan of the lanes' bit counts over the workgroup
-		uint32_t inc = ltot;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t t = __shfl_up(inc, d);
-			if (lane >= d) inc += t;
-		}
+		// exclusive scan of the lanes' bit counts over the workgroup.  Not wg_excl_scan: the wave sums alternate between two rows
+		// like the word buffers, which saves its second barrier (see the end of the loop)
+		const uint32_t inc = wave_incl_scan(ltot);
 		if (lane == 63) wsum[par][wave] = inc;
 		__syncthreads();
 		uint32_t wb = 0, tot = 0;
@@ -2158,22 +2111,19 @@ __global__ void __launch_bounds__(256) dfl_emit_kernel(DeflateArgs a)
 // device->host copy
 __global__ void __launch_bounds__(256) dfl_pack_offsets_kernel(const uint32_t *sizes, int n, uint64_t *offsets, int exact)
 {
-	__shared__ unsigned long long wsum[4];
+	__shared__ uint64_t wsum[4];
 	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-	unsigned long long carry = 0;
+	uint64_t carry = 0;
 	for (int base = 0; base < n; base += 256) {
 		const int i = base + t;
 		const uint32_t sz = i < n ? sizes[i] : 0u;
-		const unsigned long long v = exact ? sz : (unsigned long long)((sz + 15u) & ~15u);
-		unsigned long long inc = v;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const unsigned long long u = __shfl_up(inc, d);
-			if (lane >= d) inc += u;
-		}
+		const uint64_t v = exact ? sz : (uint64_t)((sz + 15u) & ~15u);
+		// wg_excl_scan written out: no test reaches offsets past 2^32, so this kernel is checked by its instructions staying what
+		// they were, and the helper's second barrier in front of the store (here it follows it) changes them
+		const uint64_t inc = wave_incl_scan(v);
 		if (lane == 63) wsum[wave] = inc;
 		__syncthreads();
-		unsigned long long wb = 0, tot = 0;
+		uint64_t wb = 0, tot = 0;
 		for (int w = 0; w < 4; w++) { if (w < wave) wb += wsum[w]; tot += wsum[w]; }
 		if (i < n) offsets[i] = carry + wb + inc - v;
 		carry += tot;

@@ -29,21 +29,11 @@
 // A literal packet cut by the segment end yields what is there, a replicate header without its byte yields nothing, bytes
 // behind rows * cols are ignored; rows play no part, so packets of other encoders that cross row ends decode alike.
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
 namespace {
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane, uint32_t &total)
-{
-	uint32_t inc = v;
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = (uint32_t)__shfl_up((int)inc, d);
-		if ((int)lane >= d) inc += o;
-	}
-	total = (uint32_t)__shfl((int)inc, 63);
-	return inc - v;
-}
 
 // ---- encode ---------------------------------------------------------------------------------------------------------
 
@@ -78,7 +68,7 @@ __device__ __forceinline__ void plane_step(uint32_t b, uint32_t pb, uint32_t n1,
 		contrib = head ? 2u : 1u;
 	}
 	uint32_t tot;
-	const uint32_t off = s.out + wave_excl_scan(contrib, lane, tot);
+	const uint32_t off = s.out + wave_excl_scan(contrib, tot);
 	if (WRITE) {
 		if (in_run) { if (contrib) { dst[off] = (uint8_t)hdr; dst[off + 1] = (uint8_t)b; } }
 		else if (valid) {
@@ -145,7 +135,7 @@ __global__ void __launch_bounds__(64) rle_layout_kernel(uint32_t rows, int plane
 			const uint32_t r = base + lane;
 			const uint32_t v = r < rows ? ri[r] : 0u;
 			uint32_t tot;
-			const uint32_t ex = wave_excl_scan(v, lane, tot);
+			const uint32_t ex = wave_excl_scan(v, tot);
 			if (r < rows) ri[r] = pos + ex;
 			pos += tot;
 		}
@@ -297,7 +287,7 @@ __global__ void __launch_bounds__(256) rle_expand_kernel(RleDecodeArgs a)
 		sum += prod[q];
 	}
 	uint32_t ctot, stot;
-	uint32_t cex = wave_excl_scan(cnt, lane, ctot), sex = wave_excl_scan(sum, lane, stot);
+	uint32_t cex = wave_excl_scan(cnt, ctot), sex = wave_excl_scan(sum, stot);
 	__syncthreads();  // every read of buf[] by the loop above is done: it becomes hoff / hpos
 	if (lane == 0) { wsum[0][wv] = ctot; wsum[1][wv] = stot; }
 	__syncthreads();

@@ -19,60 +19,14 @@
 // Algorithmic HBM traffic per pixel: 2 B read (pass 1) + payload bytes written (~1.05 B on CT);
 // pass 2 re-reads the slice (L2 / Infinity Cache resident: it was streamed microseconds earlier).
 #include "cct_internal.h"
+#include "encode_device.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
 namespace {
 
 constexpr int RING_PX = ENC_RING * ENC_CH;  // 32768 pixels, 64 KiB
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-	const int lane = threadIdx.x & 63;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		uint32_t t = __shfl_up(v, d);
-		if (lane >= d) v += t;
-	}
-	return v;
-}
-
-// Exclusive scan of v over the workgroup (threads in tid order); total returned in `total`.
-// Contains two barriers; `scratch` needs blockDim.x/64 words.
-__device__ __forceinline__ uint32_t wg_excl_scan(uint32_t v, uint32_t *scratch, uint32_t &total)
-{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-	const uint32_t inc = wave_incl_scan(v);
-	if (lane == 63) scratch[wave] = inc;
-	__syncthreads();
-	uint32_t base = 0, tot = 0;
-	for (int w = 0; w < nw; w++) {
-		const uint32_t x = scratch[w];
-		if (w < wave) base += x;
-		tot += x;
-	}
-	__syncthreads();
-	total = tot;
-	return base + inc - v;
-}
-
-// difficult-block list: first ENC_LIST_CAP records in LDS, the rest in the HBM workspace
-struct DiffList {
-	uint32_t *l_idx; uint8_t *l_cur; uint64_t *l_mask;
-	uint32_t *g_idx; uint8_t *g_cur; uint64_t *g_mask;
-	__device__ __forceinline__ void set(uint32_t e, uint32_t idx, uint32_t cur) const
-	{
-		if (e < ENC_LIST_CAP) { l_idx[e] = idx; l_cur[e] = (uint8_t)cur; }
-		else { g_idx[e - ENC_LIST_CAP] = idx; g_cur[e - ENC_LIST_CAP] = (uint8_t)cur; }
-	}
-	__device__ __forceinline__ uint32_t idx(uint32_t e) const { return e < ENC_LIST_CAP ? l_idx[e] : g_idx[e - ENC_LIST_CAP]; }
-	__device__ __forceinline__ uint32_t cur(uint32_t e) const { return e < ENC_LIST_CAP ? l_cur[e] : g_cur[e - ENC_LIST_CAP]; }
-	__device__ __forceinline__ uint64_t mask(uint32_t e) const { return e < ENC_LIST_CAP ? l_mask[e] : g_mask[e - ENC_LIST_CAP]; }
-	__device__ __forceinline__ void set_mask(uint32_t e, uint64_t m) const
-	{
-		if (e < ENC_LIST_CAP) l_mask[e] = m; else g_mask[e - ENC_LIST_CAP] = m;
-	}
-};
 
 // BS == 0: the block size is a.bs (any size from 3 to 64; launch_encode picks it for the sizes that are not powers of two).
 // A chunk is then the CB = ENC_CH / bs whole blocks that fit, CHP = CB * bs <= ENC_CH pixels: four chunks still fit the ring
@@ -101,7 +55,7 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 	const uint16_t *img = a.images + (size_t)s * N;
 	const int32_t *lut = a.lut;
 	uint8_t *role = a.ws_role ? a.ws_role + (size_t)s * NB : role_lds;
-	DiffList dl{l_idx, l_cur, l_mask,
+	DiffList dl{(LDS(uint32_t) *)l_idx, (LDS(uint8_t) *)l_cur, (LDS(uint64_t) *)l_mask,
 	            a.ws_lidx + (size_t)s * NB, a.ws_lcur + (size_t)s * NB, a.ws_lmask + (size_t)s * NB};
 
 	const int bs = BS ? BS : a.bs;
@@ -159,7 +113,7 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 						for (int t = 1; t < bs; t++) {
 							const int v = Dseg(k0 + t);
 							const int d = v - prev;
-							chg += (d > 64 || d < -64) ? 1u : 0u;  // |d| > 64, cluster.py:38-39
+							chg += seg_large(d) ? 1u : 0u;
 							prev = v;
 						}
 						if (2 * chg >= (uint32_t)bs) {  // cluster.py:58 (changes >= block_size / 2, odd sizes included)
@@ -167,7 +121,7 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 							uint32_t enter = 0;
 							if (k0 > 0) {
 								const int d = Dseg(k0) - Dseg(k0 - 1);
-								enter = (d > 64 || d < -64) ? 1u : 0u;
+								enter = seg_large(d) ? 1u : 0u;
 							}
 							cur = chg + enter;  // cluster.py:110 for i > 0 (i == 0: Q4, handled below)
 						}
@@ -276,9 +230,9 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 						for (int t = 0; t < bs; t++) {
 							const int v = D(ka + t);
 							const int d = v - prev;
-							const bool two = (d < -63 || d > 64);  // core.py:316
+							const bool two = tok_two(d);
 							n2 += two ? 1u : 0u;
-							q7 |= (d < -2047 || d > 2048);
+							q7 |= out_of_q7(d);
 							prev = v;
 						}
 						nbytes = bs + n2;
@@ -289,9 +243,9 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 						for (int t = 0; t < bs; t++) {
 							const int va = D(ka + t), vb = D(kb + t);
 							const int d1 = va - prev, d2 = vb - va;
-							n2 += (d1 < -63 || d1 > 64) ? 1u : 0u;
-							n2 += (d2 < -63 || d2 > 64) ? 1u : 0u;
-							q7 |= (d1 < -2047 || d1 > 2048) || (d2 < -2047 || d2 > 2048);
+							n2 += tok_two(d1) ? 1u : 0u;
+							n2 += tok_two(d2) ? 1u : 0u;
+							q7 |= out_of_q7(d1) || out_of_q7(d2);
 							prev = vb;
 						}
 						nbytes = 2 * bs + n2 + 1;
@@ -308,7 +262,7 @@ __global__ void __launch_bounds__(1024) encode_kernel(EncArgs a)
 				const int ka = b * bs;
 				int prev = pv;
 				auto put = [&](int d) {
-					if (d < -63 || d > 64) {  // full delta, core.py:322-323
+					if (tok_two(d)) {  // full delta, core.py:322-323
 						*w++ = (uint8_t)(0xE0 | ((d >> 8) & 0x0F));
 						*w++ = (uint8_t)(d & 0xFF);
 					} else {                  // short delta, core.py:316-319

@@ -33,14 +33,14 @@
 #include <vector>
 
 #include "cct_internal.h"
+#include "encode_device.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-#define LDS(T) __attribute__((address_space(3))) T
 
 constexpr int HALO = 64;                // look-ahead blocks after the group
 constexpr int LCAP = 64;                // list entries per wave kept in LDS (the rest spill to HBM)
@@ -82,10 +82,6 @@ constexpr uint32_t WIDE_14 = 1u, WIDE_11 = 2u;   // a pixel >= 0x4000 / >= 0x080
 #define TILE_ORIENT(a, t) ((int)((a).tiles.orgo[t] >> 24))
 
 // ---- packed 16-bit arithmetic --------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b)
-{
-	return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
-}
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b)
 {
 	return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)));
@@ -101,18 +97,6 @@ template <class T>
 __device__ __forceinline__ T lds_add(LDS(T) *p, T v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_or(LDS(uint32_t) *p, uint32_t v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_max(LDS(uint32_t) *p, uint32_t v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-	v += dpp0<0x111>(v);
-	v += dpp0<0x112>(v);
-	v += dpp0<0x114>(v);
-	v += dpp0<0x118>(v);
-	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);
-	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);
-	return v;
-}
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 __device__ __forceinline__ uint64_t uniform64(uint64_t v)  // a value every lane holds, as a scalar
 {
@@ -146,9 +130,6 @@ __device__ __forceinline__ void deltas(const uint32_t d[NW], uint32_t pv, uint32
 	for (int j = 1; j < NW; j++) x[j] = pk_sub(d[j], __builtin_amdgcn_alignbit(d[j], d[j - 1], 16));
 }
 __device__ __forceinline__ int px16(const uint32_t *d, int i) { return (int)((d[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu); }
-__device__ __forceinline__ bool tok_two(int dlt) { return (uint32_t)(dlt + 63) > 127u; }      // core.py:316
-__device__ __forceinline__ bool seg_large(int dlt) { return (uint32_t)(dlt + 64) > 128u; }    // cluster.py:37-38
-__device__ __forceinline__ bool out_of_q7(int dlt) { return (uint32_t)(dlt + 2047) > 4095u; }
 
 // bit i <=> pixel i of the 16 takes two bytes (delta outside [-63, 64]); packed arithmetic: every pixel < 0x4000
 __device__ __forceinline__ uint32_t two_byte_bits(const uint32_t x[8])

@@ -27,15 +27,14 @@
 // Barriers are `s_waitcnt lgkmcnt(0); s_barrier` (LDS only), so the global loads stay in flight
 // across them; __syncthreads() is used only where HBM-resident lists/roles must be published.
 #include "cct_internal.h"
+#include "encode_device.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// LDS pointers carry their address space in the type: a generic pointer would turn every access
-// into a flat_* instruction, whose completion forces vmcnt(0) and drains the prefetch ring.
-#define LDS(T) __attribute__((address_space(3))) T
 
 constexpr int STP = 8192;                 // pixels per super-tile
 constexpr int TPX = 4096;                 // pixels per tile
@@ -55,76 +54,18 @@ constexpr int MISC_TORG = 320;                    // u32[TILE_MAX_TILES]
 constexpr int MISC_TORI = MISC_TORG + 4 * TILE_MAX_TILES;
 constexpr int L_ROLE = L_MISC + ((MISC_TORI + TILE_MAX_TILES + 15) & ~15);
 
-__device__ __forceinline__ void lds_barrier()
-{
-	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// cross-lane moves as DPP modifiers (VALU latency) instead of ds_bpermute (LDS latency)
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp0(uint32_t v)  // lanes without a source read 0
-{
-	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-constexpr int DPP_WAVE_SHR1 = 0x138;   // lane i <- lane i-1 across the whole wave
-constexpr int DPP_QUAD_SWAP1 = 0xB1;   // quad_perm [1,0,3,2]: lane i <- lane i^1
-constexpr int DPP_QUAD_EVEN = 0xA0;    // quad_perm [0,0,2,2]: lane i <- lane i&~1
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-	v += dpp0<0x111>(v);  // row_shr:1
-	v += dpp0<0x112>(v);  // row_shr:2
-	v += dpp0<0x114>(v);  // row_shr:4
-	v += dpp0<0x118>(v);  // row_shr:8
-	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15
-	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31
-	return v;
-}
-
 // base / total of 16 per-wave counts held in LDS: lanes 0..15 scan them, everyone reads the result
 __device__ __forceinline__ void wave_counts_prefix(const LDS(uint32_t) *cnt16, int lane, int wave_s, uint32_t &base, uint32_t &tot)
 {
 	uint32_t v = (lane < NW) ? cnt16[lane] : 0u;
-	v += dpp0<0x111>(v);
-	v += dpp0<0x112>(v);
-	v += dpp0<0x114>(v);
-	v += dpp0<0x118>(v);
+	v += dpp_move<DPP_ROW_SHR1>(v);  // (the 16 counts fill one row: wave_incl_scan's first four steps)
+	v += dpp_move<DPP_ROW_SHR2>(v);
+	v += dpp_move<DPP_ROW_SHR4>(v);
+	v += dpp_move<DPP_ROW_SHR8>(v);
 	tot = (uint32_t)__builtin_amdgcn_readlane((int)v, NW - 1);
 	const uint32_t below = (uint32_t)__builtin_amdgcn_readlane((int)v, wave_s > 0 ? wave_s - 1 : 0);
 	base = wave_s > 0 ? below : 0u;
 }
-
-struct DiffListT {
-	LDS(uint32_t) *l_idx; LDS(uint8_t) *l_cur; LDS(uint64_t) *l_mask;
-	uint32_t *g_idx; uint8_t *g_cur; uint64_t *g_mask;
-	__device__ __forceinline__ void set(uint32_t e, uint32_t idx, uint32_t cur) const
-	{
-		if (e < ENC_LIST_CAP) { l_idx[e] = idx; l_cur[e] = (uint8_t)cur; }
-		else { g_idx[e - ENC_LIST_CAP] = idx; g_cur[e - ENC_LIST_CAP] = (uint8_t)cur; }
-	}
-	__device__ __forceinline__ uint32_t idx(uint32_t e) const
-	{
-		uint32_t v;
-		if (e < ENC_LIST_CAP) v = l_idx[e]; else v = g_idx[e - ENC_LIST_CAP];
-		return v;
-	}
-	__device__ __forceinline__ uint32_t cur(uint32_t e) const
-	{
-		uint32_t v;
-		if (e < ENC_LIST_CAP) v = l_cur[e]; else v = g_cur[e - ENC_LIST_CAP];
-		return v;
-	}
-	__device__ __forceinline__ uint64_t mask(uint32_t e) const
-	{
-		uint64_t v;
-		if (e < ENC_LIST_CAP) v = l_mask[e]; else v = g_mask[e - ENC_LIST_CAP];
-		return v;
-	}
-	__device__ __forceinline__ void set_mask(uint32_t e, uint64_t m) const
-	{
-		if (e < ENC_LIST_CAP) l_mask[e] = m; else g_mask[e - ENC_LIST_CAP] = m;
-	}
-};
 
 // pixel i (0..7) of a packed half block
 __device__ __forceinline__ int px_of(const u32x4 &v, int i)
@@ -133,8 +74,11 @@ __device__ __forceinline__ int px_of(const u32x4 &v, int i)
 	return (int)((i & 1) ? (w >> 16) : (w & 0xFFFFu));
 }
 
-// packed 16-bit helpers (VOP3P): per-half a-b, logical >>15, add
-__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b)
+// packed 16-bit helpers (VOP3P): per-half a-b, logical >>15, add.
+// The subtract is encode_device.h's pk_sub written out as the instruction: through the shared helper (a vector subtract the
+// compiler sees into) the kernel computes the same but the compiler folds the 0x00410041 operand and renumbers registers over
+// ~2500 lines of the two unsigned variants, and this kernel's instruction stream is pinned ("Lane primitives").
+__device__ __forceinline__ uint32_t pk_sub_asm(uint32_t a, uint32_t b)
 {
 	uint32_t r;
 	asm("v_pk_sub_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -185,7 +129,7 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 	uint8_t *role_g = ROLE_LDS ? nullptr : a.ws_role + (size_t)sl * NB;
 	auto role_get = [&](int b) -> int { return ROLE_LDS ? (int)role_l[b] : (int)role_g[b]; };
 	auto role_set = [&](int b, int v) { if (ROLE_LDS) role_l[b] = (uint8_t)v; else role_g[b] = (uint8_t)v; };
-	DiffListT dl{l_idx, l_cur, l_mask,
+	DiffList dl{l_idx, l_cur, l_mask,
 	             a.ws_lidx + (size_t)sl * NB, a.ws_lcur + (size_t)sl * NB, a.ws_lmask + (size_t)sl * NB};
 
 	// ---- one-time LDS tables: patterns, tile origins / orientations
@@ -230,7 +174,7 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 		return out;
 	};
 	auto SX = [&](int v) -> int { return SGN ? (int)(int16_t)(uint16_t)v : v; };
-	auto large = [&](int d) -> uint32_t { return ((uint32_t)(d + 64) > 128u) ? 1u : 0u; };  // |d| > 64
+	auto large = [&](int d) -> uint32_t { return seg_large(d) ? 1u : 0u; };
 
 	uint32_t ndiff = 0;
 	// ================================================================== pass 1
@@ -260,7 +204,7 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 				int px[8];
 #pragma unroll
 				for (int i = 0; i < 8; i++) px[i] = SX(px_of(own, i));
-				int prev = (int)dpp0<DPP_WAVE_SHR1>((uint32_t)px[7]);
+				int prev = (int)dpp_move<DPP_WAVE_SHR1>((uint32_t)px[7]);
 				if (lane == 0) {
 					if (tid > 0) prev = SX((int)dlin[m * STP + tid * 8 - 1]);
 					else if (s > 0) prev = SX((int)dlin[m1 * STP + STP - 1]);
@@ -271,8 +215,8 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 #pragma unroll
 				for (int i = 1; i < 8; i++) cnt += large(px[i] - px[i - 1]);
 				if (hb) cnt += f0;  // the transition between the two halves is an inner one
-				const uint32_t chg = cnt + dpp0<DPP_QUAD_SWAP1>(cnt);
-				const uint32_t enter = dpp0<DPP_QUAD_EVEN>(f0);
+				const uint32_t chg = cnt + dpp_move<DPP_QUAD_SWAP1>(cnt);
+				const uint32_t enter = dpp_move<DPP_QUAD_EVEN>(f0);
 				c_diff = (chg >= 8u && hb == 0) ? 1u : 0u;                    // cluster.py:58
 				c_cur = chg + ((s > 0 || tid > 0) ? enter : 0u);              // cluster.py:110 (block 0: Q4)
 				if (hb == 0) role_set(s * 512 + (tid >> 1), 0);
@@ -316,12 +260,12 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 #pragma unroll
 						for (int q = 0; q < 8; q++) {
 							const uint32_t lo = aw[q] + 0x00410041u;                       // A[t] + 65 (no carry: < 16384)
-							neg = pk_neg_count(neg, pk_sub(bw[q], lo));                    // B[t] - (A[t]+65) < 0
+							neg = pk_neg_count(neg, pk_sub_asm(bw[q], lo));                    // B[t] - (A[t]+65) < 0
 							// A[t+1] pairs: (A[2q+1], A[2q+2]); the last pair's high half has no successor
 							const uint32_t an = (q < 7) ? __builtin_amdgcn_alignbit(aw[q + 1], aw[q], 16) : (aw[7] >> 16);
-							uint32_t hi = pk_sub(an, 0x00410041u);                         // A[t+1] - 65
+							uint32_t hi = pk_sub_asm(an, 0x00410041u);                         // A[t+1] - 65
 							if (q == 7) hi |= 0xFFFF0000u;  // t = 15 has no successor: -1 - B[15] is always negative
-							neg = pk_neg_count(neg, pk_sub(hi, bw[q]));                    // (A[t+1]-65) - B[t] < 0
+							neg = pk_neg_count(neg, pk_sub_asm(hi, bw[q]));                    // (A[t+1]-65) - B[t] < 0
 						}
 						up = 32u - ((neg & 0xFFFFu) + (neg >> 16));
 					} else {
@@ -408,15 +352,15 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 
 		// one token: first byte always stored, second byte only for a full delta (core.py:316-323)
 		auto put = [&](LDS(uint8_t) *&w, int d) __attribute__((always_inline)) {
-			const bool two = (uint32_t)(d + 63) > 127u;  // d < -63 || d > 64
+			const bool two = tok_two(d);
 			w[0] = two ? (uint8_t)(0xE0 | ((d >> 8) & 0x0F)) : (uint8_t)(d & 0x7F);
 			if (two) w[1] = (uint8_t)(d & 0xFF);
 			w += two ? 2 : 1;
 		};
 		auto cnt2 = [&](int d, uint32_t &n2) __attribute__((always_inline)) {
-			const bool two = (uint32_t)(d + 63) > 127u;
+			const bool two = tok_two(d);
 			n2 += two ? 1u : 0u;
-			if (two) my_q7 |= (uint32_t)(d + 2047) > 4095u;  // outside [-2047, 2048] (Q7)
+			if (two) my_q7 |= out_of_q7(d);
 		};
 
 		auto p2_iter = [&](const int s, u32x4 &rnext) __attribute__((always_inline)) {
@@ -487,7 +431,7 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 				t_r = seg ? role_get(b) : 0;
 				t_nbytes = 0;
 				// predecessor pixel: usually the previous lane's last pixel
-				int prev = (int)dpp0<DPP_WAVE_SHR1>((uint32_t)px_of(t_own, 7));
+				int prev = (int)dpp_move<DPP_WAVE_SHR1>((uint32_t)px_of(t_own, 7));
 				if (lane == 0) {
 					if (tid > 0) prev = (int)dlin[m1 * STP + tid * 8 - 1];
 					else if (e > 0) prev = (int)dlin[m2 * STP + STP - 1];

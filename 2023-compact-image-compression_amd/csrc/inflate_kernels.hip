@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
@@ -613,6 +614,8 @@ __global__ void __launch_bounds__(G::NT) inflate_kernel(InflateArgs a, uint64_t 
 				}
 				*reinterpret_cast<uint4 *>(out + flushed + t) = v;
 			}
+			// wave_sum of both, written out: the two butterflies interleaved step by step.  Through the helper (one after the other, or
+			// both in one 64-bit sum) the PNG reader's INFLATE pass measured 1 % slower, 1.81 against 1.79 ms
 			for (int d = 32; d > 0; d >>= 1) { sa += __shfl_xor(sa, d); sb += __shfl_xor(sb, d); }
 			__syncthreads();
 			if (lane == 0) { S.wsum_b[wave] = sa; S.wsum_m[wave] = sb; }
@@ -775,8 +778,7 @@ __global__ void __launch_bounds__(G::NT) inflate_kernel(InflateArgs a, uint64_t 
 			walk_segment<false>(S, org_dword, start, seg_end, land, nb, nm, fl, 0, 0, PROF ? nsteps : nullptr);
 			if (PROF) {
 				const long long tw1 = clock64();
-				uint32_t mx = nsteps[0];
-				for (int d = 32; d > 0; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, d));
+				const uint32_t mx = wave_max(nsteps[0]);
 				PROF_C(C_W0CYC, tw1 - tw0); PROF_C(C_W0STEPS, mx);
 				if (tid == 0) { S.rres[0] = 0; S.rres[1] = 0; S.rres[2] = 0; }
 				__syncthreads();

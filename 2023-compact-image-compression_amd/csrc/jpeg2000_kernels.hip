@@ -25,6 +25,7 @@
 
 #include "cct_internal.h"
 #include "jpeg2000_device.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(64) void j2k_tier1_kernel(J2kArgs a)
 		s_w[i] = f;
 	}
 	t1_load_tables(lane, B.orient, s_table, s_ctx, s_zc, s_sc);
-	for (int d = 32; d >= 1; d >>= 1) any |= (uint32_t)__shfl_xor((int)any, d);
+	any = wave_or(any);
 	__syncthreads();
 	if (lane != 0) return;
 	J2kBlockOut &res = a.cbout[(size_t)frame * a.nblocks + blk];

@@ -30,28 +30,11 @@
 #include <algorithm>
 
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
 namespace {
-
-// exclusive scan over the 256 lanes of a workgroup; s: 256 words of LDS
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s, uint32_t &total)
-{
-	const uint32_t t = threadIdx.x;
-	s[t] = v;
-	__syncthreads();
-	for (uint32_t d = 1; d < 256; d <<= 1) {
-		const uint32_t x = t >= d ? s[t - d] : 0u;
-		__syncthreads();
-		s[t] += x;
-		__syncthreads();
-	}
-	total = s[255];
-	const uint32_t r = s[t] - v;
-	__syncthreads();
-	return r;
-}
 
 // ---- encode ---------------------------------------------------------------------------------------------------------
 
@@ -177,7 +160,7 @@ template <typename Px>
 __global__ void __launch_bounds__(256) jpl_emit_kernel(JplEncArgs a)
 {
 	__shared__ uint32_t w[JPL_CHUNK + 8];
-	__shared__ uint32_t scan[256];
+	__shared__ uint32_t scan[4];  // wg_excl_scan: a word per wave
 	__shared__ uint32_t s_ff;
 	__shared__ uint8_t l_size[17];
 	__shared__ uint16_t l_code[17];
@@ -208,7 +191,7 @@ __global__ void __launch_bounds__(256) jpl_emit_kernel(JplEncArgs a)
 			sum += nb[j];
 		}
 		uint32_t total;
-		uint32_t p = carry_bits + block_excl_scan(sum, scan, total);  // its barriers also put the clears before the ORs
+		uint32_t p = carry_bits + wg_excl_scan<4>(sum, scan, total);  // its barriers also put the clears before the ORs
 #pragma unroll
 		for (int j = 0; j < 4; j++) {
 			if (nb[j]) jpl_put(w, p, val[j], nb[j]);
@@ -271,7 +254,7 @@ __global__ void __launch_bounds__(64) jpl_layout_kernel(JplEncArgs a)
 // a workgroup per interval: 1024 bytes a step, a word per lane
 __global__ void __launch_bounds__(256) jpl_stuff_kernel(JplEncArgs a)
 {
-	__shared__ uint32_t scan[256];
+	__shared__ uint32_t scan[4];  // wg_excl_scan: a word per wave
 	const uint32_t t = threadIdx.x, frame = blockIdx.x / a.n_int, k = blockIdx.x % a.n_int;
 	const uint32_t N = a.rows * a.cols, nbytes = a.ibytes[blockIdx.x];
 	const uint32_t *src = a.bitbuf + (size_t)frame * N + k * a.rpi * a.cols;
@@ -282,7 +265,7 @@ __global__ void __launch_bounds__(256) jpl_stuff_kernel(JplEncArgs a)
 		const uint32_t j0 = base + t * 4u, nv = j0 < nbytes ? min(4u, nbytes - j0) : 0u;
 		const uint32_t v = nv ? src[j0 >> 2] : 0u;
 		uint32_t total;
-		uint32_t o = j0 + ff_before + block_excl_scan(jpl_ff_bytes(v, nv), scan, total);
+		uint32_t o = j0 + ff_before + wg_excl_scan<4>(jpl_ff_bytes(v, nv), scan, total);
 		for (uint32_t q = 0; q < nv; q++) {
 			const uint32_t b = (v >> (24u - 8u * q)) & 0xFFu;
 			dst[o++] = (uint8_t)b;
@@ -299,7 +282,7 @@ __global__ void __launch_bounds__(256) jpl_stuff_kernel(JplEncArgs a)
 // only at index 1 .. n_int - 1 of the frame's n_int + 1 entries.
 __global__ void __launch_bounds__(256) jpl_unstuff_kernel(JplDecArgs a)
 {
-	__shared__ uint32_t scan[256];
+	__shared__ uint32_t scan[4];  // wg_excl_scan: a word per wave
 	__shared__ uint32_t s_bad;
 	const uint32_t t = threadIdx.x, fi = blockIdx.x;
 	const JplFrame &f = a.frames[fi];
@@ -326,7 +309,7 @@ __global__ void __launch_bounds__(256) jpl_unstuff_kernel(JplDecArgs a)
 			rstm |= (uint32_t)is_rst << q;
 		}
 		uint32_t total;
-		const uint32_t ex = block_excl_scan((uint32_t)__popc(keepm) | (uint32_t)__popc(rstm) << 16, scan, total);
+		const uint32_t ex = wg_excl_scan<4>((uint32_t)__popc(keepm) | (uint32_t)__popc(rstm) << 16, scan, total);
 		uint32_t o = kept + (ex & 0xFFFFu), r = rsts + (ex >> 16);
 		for (uint32_t q = 0; q < nv; q++) {
 			if (keepm >> q & 1u) dst[o++] = (uint8_t)by[q + 1];
@@ -404,7 +387,7 @@ __device__ __forceinline__ void jpl_run(const JplLds &T, const uint8_t *data, ui
 __global__ void __launch_bounds__(256) jpl_huffman_kernel(JplDecArgs a)
 {
 	__shared__ JplLds T;
-	__shared__ uint32_t scan[256];
+	__shared__ uint32_t scan[4];  // wg_excl_scan: a word per wave
 	__shared__ uint32_t s_end, s_err;
 	const uint32_t t = threadIdx.x, fi = a.int_frame[blockIdx.x];
 	const JplFrame &f = a.frames[fi];
@@ -449,7 +432,7 @@ __global__ void __launch_bounds__(256) jpl_huffman_kernel(JplDecArgs a)
 	for (uint32_t base = 0; base < nsub; base += 256) {
 		const uint32_t s = base + t, c = s < nsub ? cn[s] : 0u;
 		uint32_t total;
-		const uint32_t ex = block_excl_scan(c, scan, total);
+		const uint32_t ex = wg_excl_scan<4>(c, scan, total);
 		if (s < nsub) la[s] = running + ex;
 		running += total;
 	}
@@ -470,7 +453,7 @@ __global__ void __launch_bounds__(256) jpl_huffman_kernel(JplDecArgs a)
 template <typename Out>
 __global__ void __launch_bounds__(256) jpl_rows_kernel(JplDecArgs a)
 {
-	__shared__ uint32_t scan[256];
+	__shared__ uint32_t scan[4];  // wg_excl_scan: a word per wave
 	__shared__ uint32_t s_base;
 	const uint32_t t = threadIdx.x, fi = blockIdx.x / a.rows, r = blockIdx.x % a.rows;
 	const JplFrame &f = a.frames[fi];
@@ -491,7 +474,7 @@ __global__ void __launch_bounds__(256) jpl_rows_kernel(JplDecArgs a)
 		uint32_t v[4], sum = 0;
 		for (uint32_t j = 0; j < 4; j++) { v[j] = i0 + j < cols ? (uint32_t)d[i0 + j] : 0u; sum += v[j]; }
 		uint32_t total;
-		uint32_t x = running + block_excl_scan(sum, scan, total);
+		uint32_t x = running + wg_excl_scan<4>(sum, scan, total);
 		for (uint32_t j = 0; j < 4; j++) {
 			x += v[j];
 			if (i0 + j < cols) out[i0 + j] = (Out)((x & 0xFFFFu) << f.pt);

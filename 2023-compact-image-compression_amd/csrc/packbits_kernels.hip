@@ -14,6 +14,7 @@
 // boundary at or after the lane), segment starts and offsets from a forward sweep.
 // Optional byte-delta transform (packbits.py:43-63): x[i] - x[i-1] mod 256 before encoding, prefix sum after decoding.
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "../../include/compact_hip.h"
 
 namespace cct {
@@ -36,17 +37,6 @@ struct Str {
 		return r0 != r1 || (r0 && at(i) != at(i + 1));
 	}
 };
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total)
-{
-	uint32_t inc = v;
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = (uint32_t)__shfl_up((int)inc, d);
-		if ((int)(threadIdx.x & 63) >= d) inc += o;
-	}
-	total = (uint32_t)__shfl((int)inc, 63);
-	return inc - v;
-}
 
 __global__ void __launch_bounds__(64) packbits_encode_kernel(const uint8_t *in, const uint64_t *offsets, int delta, uint32_t *segend_ws,
                                                             uint8_t *out, size_t out_stride, uint32_t *out_sizes)

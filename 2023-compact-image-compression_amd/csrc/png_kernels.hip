@@ -13,20 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include "cct_internal.h"
+#include "wave_device.h"
 #include "png_device.h"
 
 namespace cct {
 namespace {
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) {
-		const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-		v += ((uint64_t)hi << 32) | lo;
-	}
-	return v;
-}
 
 // ZipEncode.c: the distance of a filtered byte from zero
 __device__ __forceinline__ uint32_t png_cost(uint32_t v)
@@ -77,7 +68,7 @@ __global__ void __launch_bounds__(256) png_filter_kernel(const uint16_t *img, in
 			c_paeth += png_cost(xb - paeth(ab, bb, db));
 		}
 	}
-	const uint64_t s_none = wave_sum_u64(c_none), s_sub = wave_sum_u64(c_sub), s_up = wave_sum_u64(c_up), s_paeth = wave_sum_u64(c_paeth);
+	const uint64_t s_none = wave_sum((uint64_t)c_none), s_sub = wave_sum((uint64_t)c_sub), s_up = wave_sum((uint64_t)c_up), s_paeth = wave_sum((uint64_t)c_paeth);  // 64-bit sums
 	uint64_t best = s_none;
 	int f = 0;
 	if (best > 0 && s_up < best) { best = s_up; f = 2; }
@@ -166,7 +157,7 @@ __global__ void __launch_bounds__(256) png_filter8_kernel(const T *img, int rows
 			}
 		}
 	}
-	const uint64_t s_none = wave_sum_u64(c_none), s_sub = wave_sum_u64(c_sub), s_up = wave_sum_u64(c_up), s_paeth = wave_sum_u64(c_paeth);
+	const uint64_t s_none = wave_sum((uint64_t)c_none), s_sub = wave_sum((uint64_t)c_sub), s_up = wave_sum((uint64_t)c_up), s_paeth = wave_sum((uint64_t)c_paeth);  // 64-bit sums
 	uint64_t best = s_none;
 	int f = 0;
 	if (best > 0 && s_up < best) { best = s_up; f = 2; }

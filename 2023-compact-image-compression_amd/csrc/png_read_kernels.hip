@@ -66,8 +66,8 @@ __global__ void __launch_bounds__(256) png_unpack_kernel(PngUnpackArgs a)
 // Byte (r, i) of a row needs bytes (r, i - bpp), (r - 1, i) and (r - 1, i - bpp) (Average, Paeth), so a pixel needs its left,
 // upper and upper-left neighbours.  A wave takes a band of 64 rows, lane j row j, as a skewed wavefront: at step t lane j
 // reconstructs pixel t - j.  Its left neighbour is its own previous result; the pixel above is what lane j - 1 produced at step
-// t - 1 (one __shfl_up), the upper-left one what it produced at step t - 2, i.e. the previous "above".  Lane 0 reads the row
-// above the band.  Outside 0 <= t - j < cols a lane produces 0, which is what row and column -1 are.
+// t - 1 (one __shfl_up: a one-lane neighbour read, not one of the scans of wave_device.h), the upper-left one what it produced at
+// step t - 2, i.e. the previous "above".  Lane 0 reads the row above the band.  Outside 0 <= t - j < cols a lane produces 0, which is what row and column -1 are.
 //
 // Input and output go through LDS in tiles of 64 columns.  Superstep s (steps 64 s .. 64 s + 63) touches pixels
 // 64 s - 63 .. 64 s + 63, tiles s - 1 and s of a ring of two; it loads tile s first (row by row, the lanes across the columns),

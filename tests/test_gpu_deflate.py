@@ -132,6 +132,29 @@ def test_packed_archive_output_equals_strided_output(hip):
     pin.free()
 
 
+def test_packed_archive_offsets_of_more_files_than_a_wave(hip):
+    """70 files of unequal sizes: the offsets kernel's scan of the sizes crosses a wave boundary (64 files) with unequal sums on
+    both sides.  Every file and every offset against the oracle's files."""
+    from cct_hip import _ffi
+    from oracle import oracle
+    L = _ffi.lib()
+    cfg = hip.default_config()
+    imgs = np.stack([gi.ct_phantom(300 + i, 128) for i in range(70)])
+    n, w, h = imgs.shape
+    want = [oracle.encode(im) for im in imgs]
+    assert len(set(len(f) for f in want[:64])) > 8 and len(set(len(f) for f in want[64:])) > 1
+    flags, bs, eof, magic, ch, bpc = hip.codec_params(cfg, imgs.dtype)
+    cap = sum(len(f) for f in want) + 64
+    arch = np.zeros(cap, dtype=np.uint8)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    sizes = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_encode_batch_packed(imgs.ctypes.data, 0, n, w, h, bs, flags, eof, magic, ch, bpc, arch.ctypes.data, cap,
+                                         offs.ctypes.data, sizes.ctypes.data, status.ctypes.data, None, None))
+    assert offs.tolist() == np.concatenate([[0], np.cumsum([len(f) for f in want])]).tolist()
+    assert [arch[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)] == want
+
+
 def _decode_both(hip, files, cfg):
     """decode a batch with the device INFLATE and with libz on the host; both must agree"""
     from cct_hip import _ffi
