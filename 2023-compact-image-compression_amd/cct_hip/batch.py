@@ -450,7 +450,7 @@ def zlib_compress_batch(blobs, level=9, strategy=0, mem_level=8):
     data, offs = _archive(blobs)
     longest = max(len(b) for b in blobs)
     in_stride = (longest + 16 + 255) & ~255
-    # compressBound at memLevel 8, deflateBound's general bound at 9 (api.cpp zlib_bound), + slack
+    # compressBound at memLevel 8, deflateBound's general bound at 9 (deflate_workspace.h zlib_bound), + slack
     if mem_level == 8:
         bound = in_stride + (in_stride >> 12) + (in_stride >> 14) + (in_stride >> 25) + 13
     else:

@@ -81,12 +81,11 @@ struct EncSlot {
 	DevBuf e_pairrec, e_hand;  // streaming kernel: meshed-pair records, hand-off words and tickets
 	DevBuf h_stage;  // pinned host staging (payloads)
 	DevBuf h_small[2];  // pinned landing place of a call's sizes / status / statistics (a copy to pageable memory blocks the host until it has happened)
-	// device DEFLATE workspaces
-	DevBuf z_vals_in, z_vals_out, z_mr, z_rec, z_exitp, z_exitc, z_sym, z_bentry, z_bsym,
-	    z_small, z_bend, z_meta, z_tables, z_sorttmp, z_out, z_outsizes, z_in, z_insizes, z_packed, z_packoffs, z_gen, z_runs;
+	DevBuf z_ws[DFL_REGIONS];  // workspace of the device DEFLATE pass, one buffer per region of deflate_workspace.h
+	DevBuf z_out, z_outsizes, z_in, z_insizes, z_packed, z_packoffs;  // its input and output, and the packed files
 	DevBuf png_img, png_out, png_sizes;  // PNG writer: rasters from the host, files, their sizes (cct_png_encode_batch, cct_png_encode8_batch)
-	// match records are valid by tag (deflate_kernels.hip MatchRec): the device counter z_gen has run z_gen_passes times since
-	// the buffer z_mr_cleared (z_mr at that time) was last zeroed together with it
+	// match records are valid by tag (deflate_kernels.hip MatchRec): the device counter (region DFL_R_GEN) has run z_gen_passes
+	// times since the buffer z_mr_cleared (region DFL_R_MATCH at that time) was last zeroed together with it
 	const void *z_mr_cleared = nullptr;
 	size_t z_mr_cleared_cap = 0;
 	unsigned z_gen_passes = 0;
@@ -104,11 +103,10 @@ struct EncSlot {
 	EncSlot()
 	{
 		DevBuf *b[] = {&e_role, &e_lidx, &e_lmask, &e_lcur, &e_images, &e_payload, &e_sizes, &e_status, &e_stats, &e_pairrec,
-		               &e_hand, &h_stage, &z_vals_in, &z_vals_out, &z_mr, &z_rec, &z_exitp, &z_exitc,
-		               &z_sym, &z_bentry, &z_bsym, &z_small, &z_bend, &z_meta, &z_tables, &z_sorttmp, &z_out, &z_outsizes, &z_in,
-		               &z_insizes, &z_packed, &z_packoffs, &z_packed2[0], &z_packed2[1], &z_gen, &z_runs, &h_small[0], &h_small[1],
-		               &png_img, &png_out, &png_sizes};
+		               &e_hand, &h_stage, &z_out, &z_outsizes, &z_in, &z_insizes, &z_packed, &z_packoffs, &z_packed2[0], &z_packed2[1],
+		               &h_small[0], &h_small[1], &png_img, &png_out, &png_sizes};
 		for (DevBuf *p : b) all_bufs[n_bufs++] = p;
+		for (DevBuf &w : z_ws) all_bufs[n_bufs++] = &w;  // cct_shutdown releases them with the rest
 		h_stage.pinned_host = true;
 		h_small[0].pinned_host = h_small[1].pinned_host = true;
 	}
@@ -716,7 +714,7 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 	return CCT_OK;
 }
 
-// Payload bytes one DEFLATE pass takes (its workspaces need 40 bytes per payload byte: 43 GB at this bound, of 288).  2^28
+// Payload bytes one DEFLATE pass takes (its workspaces, deflate_workspace.h, need 44 bytes per payload byte: 47 GB at this bound, of 288).  2^28
 // in round 1; at 1024x1024 that made passes of 127 slices, and the kernels that give a slice one workgroup (both sort
 // passes, the run list, the block walk) left half of the 256 CUs idle.
 constexpr size_t DEFLATE_PASS_BYTES = (size_t)1 << 30;
@@ -732,38 +730,21 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 	if (!deflate_strategy_args(level, strategy, a))
 		return fail(CCT_E_ARG, "zlib level %d with strategy %d is not on the device", level, strategy);
 	if (!deflate_mem_level_args(mem_level, a)) return fail(CCT_E_ARG, "zlib memLevel %d: 8 and 9 are on the device", mem_level);
-	// Z_HUFFMAN_ONLY / Z_RLE: the short pass (launch_deflate) uses no sort records, match records, run lists or queues, and
-	// Z_HUFFMAN_ONLY no decision records or walk either: those workspaces are neither grown nor cleared for it
-	const bool chains = strategy != 2 && strategy != 3, walk = strategy != 2;
 	const size_t EB = (size_t)n * in_stride;
 	if (EB >= ((size_t)1 << 32)) return fail(CCT_E_ARG, "deflate batch of %zu bytes exceeds the 4 GiB sort limit; split the batch", EB);
-	const int max_blocks = (int)(in_stride / a.block_syms + 2);
+	// the regions this pass needs, each a buffer that grows on its own (deflate_workspace.h: why they are not one arena); a short
+	// pass (Z_HUFFMAN_ONLY / Z_RLE) neither grows nor clears the workspaces of the hash chains
+	const DflShape shape = dfl_shape(n, in_stride, a.block_syms);
 	int rc;
-	if (chains) {
-		if ((rc = E.z_vals_in.ensure(EB * 8))) return rc;   // records between the two sort passes, then run_ends + run_len
-		if ((rc = E.z_vals_out.ensure(EB * 8))) return rc;  // sorted records
-		if ((rc = E.z_mr.ensure(EB * 8))) return rc;
-		if ((rc = E.z_runs.ensure(EB * 4))) return rc;
-		if ((rc = E.z_rec.ensure(EB * 4))) return rc;
+	void *base[DFL_REGIONS];
+	for (int r = 0; r < DFL_REGIONS; r++) {
+		if (dfl_region_needed(r, strategy) && (rc = E.z_ws[r].ensure(dfl_region_bytes(r, shape)))) return rc;
+		base[r] = E.z_ws[r].p;
 	}
-	if ((rc = E.z_sym.ensure(EB * 4))) return rc;
-	if (walk) {
-		if ((rc = E.z_exitp.ensure(EB * 4))) return rc;
-		if ((rc = E.z_exitc.ensure(EB * 4))) return rc;
-		if ((rc = E.z_bentry.ensure(EB / 64 * 4))) return rc;
-		if ((rc = E.z_bsym.ensure(EB / 64 * 4))) return rc;
-	}
-	const int run_chunks = (int)(in_stride / 1784 + 1);  // chunks of dfl_run_len_kernel (RUNLEN_OUT positions) per slice
-	if ((rc = E.z_small.ensure((size_t)n * (9 + SORT_HIST + 2 * (size_t)run_chunks) * 4))) return rc;
-	if ((rc = E.z_bend.ensure((size_t)n * max_blocks * 8))) return rc;  // block ends, then the loop tops of their flushes
-	if ((rc = E.z_meta.ensure((size_t)n * max_blocks * sizeof(BlockMeta)))) return rc;
-	if ((rc = E.z_tables.ensure((size_t)n * max_blocks * sizeof(BlockTables)))) return rc;
 	if ((rc = E.z_out.ensure((size_t)n * out_stride))) return rc;
 	if ((rc = E.z_outsizes.ensure((size_t)n * 4))) return rc;
 	// (cutting the batch into slice ranges that run concurrently on streams of their own was tried and removed: the
 	// cross-stream dependencies cost more than the overlap returned, here as in the transform+pack stage)
-	const size_t tmp = (deflate_sort_temp_bytes((size_t)n * in_stride, n) + 511) & ~(size_t)255;
-	if ((rc = E.z_sorttmp.ensure(tmp + 256))) return rc;
 	const bool use_fork = g_ctx.deflate_fork != 0;
 	if (use_fork && !E.stream_side) {
 		// created on first use (see GPU_MAX_HW_QUEUES in ensure_ctx: streams are not free)
@@ -771,34 +752,23 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 		if (crc) return crc;
 	}
 	a.in = d_in; a.in_stride = in_stride; a.in_sizes = d_in_sizes;
-	a.rec_in = (uint64_t *)E.z_vals_in.p; a.rec_out = (uint64_t *)E.z_vals_out.p;
+	dfl_bind(a, base, shape);
 	// compact sort records hold a 15-bit hash: memLevel 8 only (deflate_kernels.hip "Sort records").  A compact record for the
 	// 16-bit hash would need a 20-bit position field.  memLevel 9 serves the PNG writer, and on filtered PNG rows compact records
 	// do not pay even at memLevel 8 (61.7 against 61.0 ms per 256 slices at level 6)
 	a.pos_mask = (g_ctx.compact_recs && mem_level == 8 && in_stride < ((size_t)1 << 22)) ? (1u << 22) - 1u : 0xFFFFFFFFu;
-	uint32_t *small = (uint32_t *)E.z_small.p;
-	a.seg_begin = small; a.seg_end = small + n; a.total_syms = small + 2 * n; a.postloop_lit = small + 3 * n;
-	a.n_blocks = small + 4 * n; a.adler = small + 5 * n; a.heavy_count = small + 6 * n; a.deep_count = small + 7 * n; a.run_end_count = small + 8 * n; a.sort_hist = small + 9 * n;
-	a.run_counts = small + (9 + SORT_HIST) * (size_t)n; a.run_chunks = run_chunks;
 	// the tag of a pass must not meet a record of 16383 passes ago: clear records and counter well before it comes round (and
 	// whenever the buffer is new); a pass that failed on the way may have left the two counts a few apart, hence the margin
 	// (a short pass neither reads match records nor advances the tag: it does not count)
-	if ((rc = E.z_gen.ensure(256))) return rc;
-	if (chains && (E.z_mr_cleared != E.z_mr.p || E.z_mr_cleared_cap != E.z_mr.cap || E.z_gen_passes >= 16000u)) {
-		HIP_TRY(hipMemsetAsync(E.z_mr.p, 0, E.z_mr.cap, E.stream));
-		HIP_TRY(hipMemsetAsync(E.z_gen.p, 0, 256, E.stream));
-		E.z_mr_cleared = E.z_mr.p; E.z_mr_cleared_cap = E.z_mr.cap; E.z_gen_passes = 0;
+	const DevBuf &mr = E.z_ws[DFL_R_MATCH];
+	if (dfl_uses_chains(strategy)) {
+		if (E.z_mr_cleared != mr.p || E.z_mr_cleared_cap != mr.cap || E.z_gen_passes >= 16000u) {
+			HIP_TRY(hipMemsetAsync(mr.p, 0, mr.cap, E.stream));
+			HIP_TRY(hipMemsetAsync(E.z_ws[DFL_R_GEN].p, 0, 256, E.stream));
+			E.z_mr_cleared = mr.p; E.z_mr_cleared_cap = mr.cap; E.z_gen_passes = 0;
+		}
+		E.z_gen_passes++;
 	}
-	if (chains) E.z_gen_passes++;
-	a.gen = (uint32_t *)E.z_gen.p;
-	a.mr = E.z_mr.p; a.heavy_list = (uint32_t *)E.z_rec.p; a.sym = (uint32_t *)E.z_sym.p;
-	a.run_ends = (uint32_t *)E.z_runs.p;  // 4 EB of their own: the lists are built while the sort runs (launch_deflate)
-	a.run_len = (uint16_t *)E.z_sym.p;  // 2 EB, written before the sort and dead before the symbols are
-	a.rec32 = (uint32_t *)E.z_exitp.p; a.exit_pos = (uint32_t *)E.z_exitc.p; a.exit_cnt = (uint32_t *)E.z_rec.p;  // the heavy/deep queues are dead once dfl_rec_kernel runs
-	a.blk_entry = (uint32_t *)E.z_bentry.p; a.blk_symbase = (uint32_t *)E.z_bsym.p;
-	a.blk_end = (uint32_t *)E.z_bend.p; a.blk_top = a.blk_end + (size_t)n * max_blocks;
-	a.block_meta = (BlockMeta *)E.z_meta.p; a.block_tables = (BlockTables *)E.z_tables.p;
-	a.max_blocks = max_blocks;
 	a.out = (uint8_t *)E.z_out.p; a.out_stride = out_stride; a.out_sizes = (uint32_t *)E.z_outsizes.p;
 	memcpy(a.header13, header13, 13);
 	if (g_ctx.use_graph) {
@@ -821,7 +791,7 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 				}
 				EncSlot::ZGraph g;
 				HIP_TRY(hipStreamBeginCapture(E.stream, hipStreamCaptureModeThreadLocal));
-				hipError_t le = launch_deflate(a, n, E.z_sorttmp.p, tmp, E.stream, use_fork ? E.stream_side : nullptr, E.ev_fork);
+				hipError_t le = launch_deflate(a, n, E.stream, use_fork ? E.stream_side : nullptr, E.ev_fork);
 				hipError_t ce = hipStreamEndCapture(E.stream, &g.graph);
 				if (le != hipSuccess) { if (g.graph) (void)hipGraphDestroy(g.graph); return fail(CCT_E_DEVICE, "DEFLATE capture: %s", hipGetErrorString(le)); }
 				HIP_TRY(ce);
@@ -838,7 +808,7 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 		HIP_TRY(hipGraphLaunch(zg->exec, E.stream));
 		return CCT_OK;
 	}
-	HIP_TRY(launch_deflate(a, n, E.z_sorttmp.p, tmp, E.stream, use_fork ? E.stream_side : nullptr, E.ev_fork));
+	HIP_TRY(launch_deflate(a, n, E.stream, use_fork ? E.stream_side : nullptr, E.ev_fork));
 	return CCT_OK;
 }
 
@@ -1113,7 +1083,7 @@ size_t cct_payload_stride(int width, int height, int block_size)
 size_t cct_file_bound(int width, int height, int block_size)
 {
 	const size_t p = cct_payload_stride(width, height, block_size);
-	return ((13 + compressBound((uLong)p) + 63) & ~(size_t)63);
+	return deflate_out_stride(p, 8);  // .cct files are memLevel 8 streams
 }
 
 int cct_encode_payload_dev(const uint16_t *d_images, int n, int width, int height, int block_size, uint32_t flags,
@@ -1555,15 +1525,6 @@ int cct_encode_batch_packed(const uint16_t *images, int images_on_device, int n,
 	                         bytes_per_channel, h_archive, archive_cap, h_out_sizes, h_status, h_payload_sizes, h_stats, h_offsets);
 }
 
-// Bytes a zlib stream of n input bytes can take: compressBound at memLevel 8 (deflateBound's tight bound for the default
-// parameters), deflateBound's general bound otherwise.  memLevel 9's 32767-symbol blocks can straddle a slide of the window,
-// where zlib may not store them: random bytes under Z_FILTERED come out 0.09 % above compressBound.
-static size_t zlib_bound(size_t n, int mem_level)
-{
-	if (mem_level == 8) return compressBound((uLong)n);
-	return n + ((n + 7) >> 3) + ((n + 63) >> 6) + 5 + 6;
-}
-
 static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offsets, int n, int level, int strategy, int mem_level,
                                     uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
 {
@@ -1576,8 +1537,7 @@ static int zlib_compress_batch_impl(const uint8_t *h_in, const uint64_t *h_offse
 	EncSlot &E = g_enc[0];
 	size_t longest = 0;
 	for (int i = 0; i < n; i++) longest = std::max(longest, (size_t)(h_offsets[i + 1] - h_offsets[i]));
-	const size_t in_stride = (longest + 16 + 255) & ~(size_t)255;
-	const size_t zstride = (13 + zlib_bound(in_stride, mem_level) + 63) & ~(size_t)63;
+	const size_t in_stride = deflate_in_stride(longest), zstride = deflate_out_stride(in_stride, mem_level);
 	if (out_stride < zstride - 13) return fail(CCT_E_CAP, "out_stride %zu too small (need %zu)", out_stride, zstride - 13);
 	if ((rc = E.z_in.ensure((size_t)n * in_stride))) return rc;
 	if ((rc = E.z_insizes.ensure((size_t)n * 4))) return rc;
@@ -1648,8 +1608,8 @@ constexpr int PNG_MEM_LEVEL = 9;
 constexpr size_t PNG_MAX_FILTERED = DEFLATE_PASS_BYTES - 512;
 // bps: bytes per sample, 2 in the 16-bit files and 1 in the 8-bit ones
 static size_t png_filtered_bytes(int rows, int cols, int bps = 2) { return (size_t)rows * (1 + (size_t)bps * (size_t)cols); }
-static size_t png_in_stride(size_t filtered) { return (filtered + 16 + 255) & ~(size_t)255; }
-static size_t png_zstride(size_t in_stride) { return (13 + zlib_bound(in_stride, PNG_MEM_LEVEL) + 63) & ~(size_t)63; }
+static size_t png_in_stride(size_t filtered) { return deflate_in_stride(filtered); }
+static size_t png_zstride(size_t in_stride) { return deflate_out_stride(in_stride, PNG_MEM_LEVEL); }
 static uint32_t png_chunk(int cols) { return (uint32_t)std::max<size_t>(65536, 4 * (size_t)cols); }
 // signature + IHDR (33), the stream, 12 bytes per IDAT chunk, IEND (12)
 static size_t png_file_bytes(size_t zlen, uint32_t chunk) { return 33 + zlen + 12 * ((zlen + chunk - 1) / chunk) + 12; }

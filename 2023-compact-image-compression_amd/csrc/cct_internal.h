@@ -9,6 +9,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "deflate_workspace.h"
+
 namespace cct {
 
 // ---- encode kernel geometry ----------------------------------------------------------
@@ -145,49 +147,7 @@ inline void bs_divider(int d, uint32_t *mul, uint32_t *shift)
 hipError_t launch_decode(const DecArgs &a, int n, int block_size, int threads, hipStream_t s, bool run_time);
 
 // ---- device DEFLATE (zlib 1.2.11 level 9 restatement, deflate_kernels.hip) ----------------
-struct BlockMeta {          // one DEFLATE block of a slice
-	uint64_t bit_off;         // absolute bit offset of the 3 header bits inside the slice's output
-	uint32_t type;            // 0 stored, 1 static trees, 2 dynamic trees
-	uint32_t last;
-	uint32_t first_sym, nsym;
-	uint32_t in_begin, stored_len;
-	uint32_t hdr_nbits, body_bits;
-};
-struct BlockTables {
-	uint16_t lcode[286]; uint8_t llen[286];
-	uint16_t dcode[30]; uint8_t dlen[30];
-	uint32_t hdr_bits[160];
-};
-struct DeflateArgs {
-	const uint8_t *in; size_t in_stride; const uint32_t *in_sizes;  // token payloads (device)
-	uint64_t *rec_in, *rec_out;                                      // n * in_stride each: sort records (deflate_kernels.hip, "Sort records"), between / after the sort passes
-	uint32_t pos_mask;                                               // position bits of a record's lower word: 2^22 - 1 (compact records, in_stride < 4 MiB) or all 32
-	uint32_t *seg_begin, *seg_end;                                   // n
-	void *mr;                                                        // n * in_stride * 8 bytes: match records, valid where they carry the tag *gen
-	uint32_t *gen;                                                   // device counter of the passes run on this mr buffer, 1 .. 16383 (deflate_kernels.hip MatchRec)
-	uint32_t *heavy_list, *sym, *run_ends;                           // n * in_stride each
-	uint32_t *run_counts; int run_chunks;                            // n * 2 * run_chunks right behind sort_hist: run ends / starts per chunk of 1784 positions (run_chunks = chunks per slice)
-	uint32_t *sort_hist;                                             // n * SORT_HIST: per slice the histograms of hash & 255 and of hash >> 8 (dfl_run_len_kernel -> sort passes)
-	uint16_t *run_len;                                               // n * in_stride: equal bytes ahead (<= 258) | has_prev << 15
-	uint32_t *rec32, *exit_pos, *exit_cnt;                           // n * in_stride each
-	uint32_t *blk_entry, *blk_symbase;                               // n * in_stride / 64
-	uint32_t *total_syms, *postloop_lit, *n_blocks, *adler, *heavy_count, *deep_count, *run_end_count;  // n
-	uint32_t *blk_end;                                               // n * max_blocks
-	uint32_t *blk_top;                                               // n * max_blocks: position at the top of the loop iteration that flushed the block (dfl_tree_kernel, window_base)
-	BlockMeta *block_meta; BlockTables *block_tables;                // n * max_blocks
-	int max_blocks;
-	uint8_t *out; size_t out_stride; uint32_t *out_sizes;            // whole .cct files (header + zlib stream)
-	uint8_t header13[16];
-	// the zlib level (4 .. 9, all deflate_slow): deflate.c configuration_table entries and the second header byte
-	uint32_t good, max_lazy, nice, max_chain, zlib_flg;
-	// the zlib strategy (0 .. 4, deflate_kernels.hip "zlib strategies") and the shortest match deflate_slow keeps:
-	// MIN_MATCH, or 6 under Z_FILTERED (matches of <= 5 bytes dropped)
-	uint32_t strategy, min_len;
-	// the zlib memLevel (8 or 9): hash bits (memLevel + 7) and symbols per block (lit_bufsize - 1)
-	uint32_t hash_bits, block_syms;
-};
-// sort histogram words per slice: 256 digits of hash & 255, then up to 256 of hash >> 8 (16-bit hash, memLevel 9)
-constexpr int SORT_HIST = 512;
+// BlockMeta, BlockTables, DeflateArgs, the shared constants and the workspace layout: deflate_workspace.h
 // a level's fields of DeflateArgs (deflate_kernels.hip); false for levels outside 4 .. 9
 bool deflate_level_args(int level, DeflateArgs &a);
 // a memLevel's fields of DeflateArgs; false for anything but 8 and 9
@@ -196,10 +156,9 @@ bool deflate_mem_level_args(int mem_level, DeflateArgs &a);
 // and 3 (deflate_huff / deflate_rle, which read no level table); false for anything else
 bool deflate_strategy_args(int level, int strategy, DeflateArgs &a);
 hipError_t deflate_init_tables();
-size_t deflate_sort_temp_bytes(size_t total, int n);
 hipError_t launch_pack(const uint8_t *src, size_t stride, const uint32_t *sizes, int n, uint64_t *offsets, uint8_t *dst,
                        int exact, hipStream_t st);
-hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t sort_temp_bytes, hipStream_t st, hipStream_t side = nullptr,
+hipError_t launch_deflate(const DeflateArgs &a, int n, hipStream_t st, hipStream_t side = nullptr,
                           const hipEvent_t *fork_join_events = nullptr);  // side + four events (no timing): independent kernels side by side
 
 // ---- PNG writer (png_kernels.hip) -----------------------------------------------------------------

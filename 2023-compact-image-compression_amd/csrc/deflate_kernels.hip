@@ -320,9 +320,8 @@ __device__ __forceinline__ uint32_t nil_candidate(uint32_t p, uint32_t lookahead
 // run_len[p] = number of bytes equal to in[p] starting at p, capped at MAX_MATCH (and by the end of the input),
 // with bit 15 = (p >= 2 && in[p-1] == in[p]).  The match kernels visit positions in hash order, where
 // scanning the bytes would be a chain of uncoalesced loads; here the input is read once, in order.
-// A workgroup scans 2048 positions (8 per lane) and publishes the first RUNLEN_OUT of them: for those the
-// scanned tail (>= 264 bytes) decides every length below the cap.
-constexpr int RUNLEN_OUT = 2048 - 264;
+// A workgroup scans 2048 positions (8 per lane) and publishes the first RUNLEN_OUT of them (deflate_workspace.h): for those
+// the scanned tail (>= 264 bytes) decides every length below the cap.
 
 // SORT = false (the Z_RLE pass): run-length words only, without the sort histograms and run-list counts nobody reads there.
 // HB: hash bits (15 or 16, memLevel 8 or 9)
@@ -644,7 +643,7 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 		}
 		base_h = (uint32_t)__shfl((int)base_h, 0, 64); base_r = (uint32_t)__shfl((int)base_r, 0, 64);
 		if (kind == 1) heavy[base_h + (uint32_t)__popcll(bh & lt_mask)] = i;
-		if (kind == 2) *(heavy + a.in_stride - 1 - (base_r + (uint32_t)__popcll(br & lt_mask))) = i;  // grows downwards from the end
+		if (kind == 2) *(dfl_deep_top(heavy, a.in_stride) - (base_r + (uint32_t)__popcll(br & lt_mask))) = i;  // grows downwards from the end
 	}
 }
 
@@ -752,8 +751,8 @@ __global__ void __launch_bounds__(256) dfl_match_heavy_kernel(DeflateArgs a, int
 // offset (a workgroup prefix sum places them, so both lists come out in position order); dfl_run_info_kernel pairs the k-th
 // start with the k-th end (run length without scanning).  Until round 3 one workgroup per slice walked its 8192-byte
 // chunks in a row, computing the flags byte by byte (0.18 ms per batch).
-// Buffer (in_stride words of its own, at most L/4 runs): ends at [0, 1/4), starts at [1/4, 1/2), length|byte<<16 at [1/2, 3/4),
-// rank of every eighth position among the ends at [3/4, 1) (in_stride / 8 words).
+// Buffer (in_stride words of its own, at most L/4 runs): ends, starts, length|byte<<16 and the rank of every eighth position
+// among the ends, a quarter each (deflate_workspace.h: dfl_run_starts, dfl_run_info, dfl_run_rank).
 __global__ void __launch_bounds__(256) dfl_run_lists_kernel(DeflateArgs a)
 {
 	__shared__ uint32_t wsum[4], base_es[2];
@@ -765,7 +764,7 @@ __global__ void __launch_bounds__(256) dfl_run_lists_kernel(DeflateArgs a)
 	const uint8_t *in = a.in + (size_t)s * a.in_stride;
 	const uint16_t *rl = a.run_len + (size_t)s * a.in_stride;
 	uint32_t *re = a.run_ends + (size_t)s * a.in_stride;
-	uint32_t *rs = re + (a.in_stride >> 2);
+	uint32_t *rs = dfl_run_starts(re, a.in_stride);
 	const uint32_t *cnt = a.run_counts + (size_t)s * 2 * a.run_chunks;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const uint32_t g = c0 + (uint32_t)tid * 8;
@@ -796,7 +795,7 @@ __global__ void __launch_bounds__(256) dfl_run_lists_kernel(DeflateArgs a)
 	const uint32_t tot_e = base_es[0] + (tot & 0xFFFFu);
 	// rank table for the run matcher: ends put on the list by the positions before g (last quarter of the slice's buffer): the
 	// "last run end <= p" of a position is then one lookup and a step or two instead of a binary search of twelve dependent loads
-	if ((uint32_t)tid * 8 < (uint32_t)RUNLEN_OUT && g < L) re[3 * (a.in_stride >> 2) + (g >> 3)] = ie;
+	if ((uint32_t)tid * 8 < (uint32_t)RUNLEN_OUT && g < L) re[dfl_run_rank(a.in_stride, g)] = ie;
 #pragma unroll
 	for (int k = 0; k < 8; k++) {
 		if ((me >> k) & 1u) re[ie++] = g + k + 3;
@@ -810,8 +809,8 @@ __global__ void __launch_bounds__(256) dfl_run_info_kernel(DeflateArgs a)
 	const int s = blockIdx.y;
 	const uint8_t *in = a.in + (size_t)s * a.in_stride;
 	const uint32_t *re = a.run_ends + (size_t)s * a.in_stride;
-	const uint32_t *rs = re + (a.in_stride >> 2);
-	uint32_t *rl = a.run_ends + (size_t)s * a.in_stride + (a.in_stride >> 1);
+	const uint32_t *rs = dfl_run_starts(re, a.in_stride);
+	uint32_t *rl = dfl_run_info(a.run_ends + (size_t)s * a.in_stride, a.in_stride);
 	const uint32_t nre = a.run_end_count[s];
 	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < nre; t += gridDim.x * blockDim.x) {
 		const uint32_t x = re[t], len = x - rs[t];
@@ -841,10 +840,10 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 	const size_t base = (size_t)s * a.in_stride;
 	const uint64_t *recs = a.rec_out + base;  // sorted (hash, position) records: position | hash << 32
 	uint2 *mr = reinterpret_cast<uint2 *>(a.mr) + base;
-	const uint32_t *deep = a.heavy_list + base + a.in_stride - 1;  // grows downwards from the end
+	const uint32_t *deep = dfl_deep_top(a.heavy_list + base, a.in_stride);  // grows downwards from the end
 	const uint32_t ndeep = a.deep_count[s];
 	const uint32_t *re = a.run_ends + base;
-	const uint32_t *rl = re + (a.in_stride >> 1);
+	const uint32_t *rl = dfl_run_info(re, a.in_stride);
 	const uint32_t nre = a.run_end_count[s];
 	const uint32_t gen = *a.gen;
 	const uint32_t quarter = a.max_chain >> 2;
@@ -887,7 +886,7 @@ __global__ void __launch_bounds__(256) dfl_match_run_kernel(DeflateArgs a, int n
 			// entries of the positions below p - 2 -- the rank table gives those below the 8-aligned part, the rest is a step or two
 			uint32_t lo = 0;
 			if (p >= 3) {
-				lo = re[3 * (a.in_stride >> 2) + ((p - 2) >> 3)];
+				lo = re[dfl_run_rank(a.in_stride, p - 2)];
 				while (lo < nre && re[lo] <= p) lo++;
 			}
 			// (the entry of the next step is requested before this one is evaluated: the loop is a chain of dependent lookups otherwise)
@@ -1100,7 +1099,7 @@ __global__ void __launch_bounds__(WALK_T) dfl_walk_kernel(DeflateArgs a, int n)
 	(void)n;
 	const uint32_t L = a.in_sizes[s];
 	const size_t base = (size_t)s * a.in_stride;
-	const size_t bbase = (size_t)s * (a.in_stride / 64);
+	const size_t bbase = (size_t)s * dfl_blk_words(a.in_stride);
 	const uint32_t *exit_rec = a.exit_pos + base;  // (offset of the exit past the entry's block) | symbols << 16
 	const int tid = threadIdx.x;
 	const uint32_t seg = (((L + WALK_T - 1) / WALK_T) + 63) & ~63u;
@@ -1147,7 +1146,7 @@ __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 	const uint32_t L = a.in_sizes[s];
 	const uint8_t *in = a.in + (size_t)s * a.in_stride;
 	const size_t base = (size_t)s * a.in_stride;
-	const size_t bbase = (size_t)s * (a.in_stride / 64);
+	const size_t bbase = (size_t)s * dfl_blk_words(a.in_stride);
 	const uint32_t nblk64 = (L + 63) / 64;
 	const int lane = threadIdx.x & 63;
 	uint32_t *sym = a.sym + base;
@@ -2144,7 +2143,7 @@ __global__ void __launch_bounds__(256) dfl_pack_kernel(const uint8_t *src, size_
 __global__ void dfl_offsets2_kernel(DeflateArgs a, int n)
 {
 	// blk_entry := "not entered" for the walk kernel
-	const size_t per = a.in_stride / 64;
+	const size_t per = dfl_blk_words(a.in_stride);
 	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)n * per; i += (size_t)gridDim.x * blockDim.x)
 		a.blk_entry[i] = 0xFFFFFFFFu;
 }
@@ -2155,22 +2154,24 @@ __global__ void dfl_offsets_kernel(DeflateArgs a, int n)
 		for (int s = threadIdx.x; s < n; s += blockDim.x) { a.postloop_lit[s] = 0; a.heavy_count[s] = 0; a.deep_count[s] = 0; a.run_end_count[s] = 0; }  // (run_end_count: an empty slice has no chunk that would write it)
 		if (threadIdx.x == 0) *a.gen = *a.gen % GEN_MAX + 1u;  // tag of this pass's match records (see MatchRec)
 	}
-	// sort histograms and, right behind them (DeflateArgs), the run-list counters of dfl_run_len_kernel (a memset node of a few
+	// sort histograms and, right behind them (dfl_bind), the run-list counters of dfl_run_len_kernel (a memset node of a few
 	// megabytes at the head of the graph waited for the copy engine: with the files of the pass before still on the wire a pass
 	// of 1024^2 slices started 3 ms late)
-	const size_t nrc = (size_t)n * (SORT_HIST + 2 * (size_t)a.run_chunks);
+	const size_t nrc = dfl_hist_words((size_t)n, (size_t)a.run_chunks);
 	for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < nrc; t += (size_t)gridDim.x * blockDim.x) a.sort_hist[t] = 0;
 }
 
 // Zeroes of the output, by need: dfl_layout_kernel's trailer and dfl_emit_kernel OR their bits into zeros, and nothing before
-// the layout kernel reads `out`.  A file is at most 13 + zlib_bound(in_size, memLevel) bytes (api.cpp); the slack covers the
+// the layout kernel reads `out`.  A file is at most 13 + zlib_bound(in_size, memLevel) bytes; the slack covers the
 // 32-bit words of or_bits / dfl_emit_kernel that straddle the end and the 16-byte units dfl_pack_kernel copies.  Beyond that the
 // stride keeps whatever the pass before left there: nobody reads it.  W: bytes per store, 16 when the stride allows it.
 constexpr uint32_t CLEAR_SLACK = 64;
 __device__ __forceinline__ size_t clear_bytes(const DeflateArgs &a, int s)
 {
+	// mirrors zlib_bound(L, memLevel == 8) of deflate_workspace.h, written out: through the call the compiler orders this kernel's
+	// scalar instructions differently (12 more bytes of code), and device code stays as it is
 	const size_t L = a.in_sizes[s];
-	const size_t bound = a.block_syms == (uint32_t)BLOCK_SYMS ? L + (L >> 12) + (L >> 14) + (L >> 25) + 13  // compressBound
+	const size_t bound = a.block_syms == (uint32_t)BLOCK_SYMS ? L + (L >> 12) + (L >> 14) + (L >> 25) + 13
 	                                                          : L + ((L + 7) >> 3) + ((L + 63) >> 6) + 5 + 6;
 	return min(a.out_stride, (13 + bound + CLEAR_SLACK + 15) & ~(size_t)15);
 }
@@ -2276,12 +2277,6 @@ hipError_t deflate_init_tables()
 	return hipSuccess;
 }
 
-size_t deflate_sort_temp_bytes(size_t total, int n)
-{
-	(void)total; (void)n;
-	return 0;  // the sort keeps its state in LDS (dfl_sort_pass_kernel)
-}
-
 // One DEFLATE pass.  `side` + `ev` (four events without timing), when given, let kernels that do not depend on each other share
 // the chip: the run lists are written while the match kernel runs (its waves fill the chip, so the side kernels mostly end
 // with it -- but they no longer come after it), and the two tail-bound matchers (long chains: a few waves walking thousands
@@ -2320,8 +2315,7 @@ static hipError_t launch_deflate_short(const DeflateArgs &a, int n, hipStream_t 
 	return hipGetLastError();
 }
 
-hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t sort_temp_bytes, hipStream_t st, hipStream_t side,
-                          const hipEvent_t *ev)
+hipError_t launch_deflate(const DeflateArgs &a, int n, hipStream_t st, hipStream_t side, const hipEvent_t *ev)
 {
 	hipError_t e;
 	const bool ml9 = a.hash_bits == 16;
@@ -2331,7 +2325,6 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, void *sort_temp, size_t s
 	if (short_pass(a.strategy)) return launch_deflate_short(a, n, st);
 	hipLaunchKernelGGL(dfl_offsets_kernel, dim3(64), dim3(256), 0, st, a, n);  // (also zeroes sort_hist and run_counts)
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
-	(void)sort_temp; (void)sort_temp_bytes;
 	if (ml9) {
 		hipLaunchKernelGGL((dfl_run_len_kernel<true, 16>), dim3(gx, n), dim3(256), 0, st, a);
 		hipLaunchKernelGGL((dfl_sort_pass_kernel<true, 16>), dim3(n), dim3(1024), 0, st, a);

@@ -333,3 +333,33 @@ def test_inflate_geometry_choice(hip):
         assert L.cct_set_option(b"inflate_lanes", 128) != 0
     finally:
         _ffi.check(L.cct_set_option(b"inflate_lanes", forced.value))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the pass's workspace (deflate_workspace.h) reused across layouts in one process
+def _workspace_batches():
+    rng = np.random.default_rng(20231)
+    small = [b"", b"a", rng.integers(0, 256, 255, dtype=np.uint8).tobytes()]  # in_stride 512, one run chunk, two blocks
+    medium = [rng.integers(0, 5, 3573, dtype=np.uint8).tobytes()]  # in_stride 3840: three run chunks, one block
+    runs = bytearray()
+    while len(runs) < 20000:  # runs of 3 .. 300 equal bytes: run lists and rank words
+        runs += bytes([int(rng.integers(0, 256))]) * int(rng.integers(3, 301))
+    large = [rng.integers(0, 256, 20000, dtype=np.uint8).tobytes()  # > 16383 literals: a second block at memLevel 8 only
+             + bytes(runs[:20000])
+             + rng.integers(0, 4, 30000, dtype=np.uint8).tobytes()]  # long chains past the 32 K window: heavy and deep queues
+    assert len(large[0]) == 70000
+    return small, medium, large
+
+
+def test_workspace_reuse_across_layouts(hip):
+    """One process, one slot: the regions grow, shrink in use, are skipped by the short passes (Z_HUFFMAN_ONLY touches neither
+    the chain nor the walk regions, Z_RLE the walk regions only) and are bound again under other strides, block counts and
+    memLevels; the sixth call finds the graph of the first after the buffers have regrown.  Every stream byte-equal to zlib's."""
+    small, medium, large = _workspace_batches()
+    calls = [(large, 9, 0, 8), (small, 6, 2, 8), (large, 6, 3, 8), (medium, 4, 0, 8), (large, 6, 1, 9), (large, 9, 0, 8),
+             (small, 9, 4, 8)]
+    for step, (blobs, level, strategy, mem_level) in enumerate(calls, 1):
+        got = hip.zlib_compress_batch(blobs, level=level, strategy=strategy, mem_level=mem_level)
+        for i, (b, g) in enumerate(zip(blobs, got)):
+            c = zlib.compressobj(level, zlib.DEFLATED, 15, mem_level, strategy)
+            assert g == c.compress(b) + c.flush(), f"call {step} (level {level}, strategy {strategy}, memLevel {mem_level}), blob {i}"
