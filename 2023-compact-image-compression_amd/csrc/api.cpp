@@ -23,6 +23,7 @@
 #include "../../include/compact_hip.h"
 #include "cct_internal.h"
 #include "host.h"
+#include "handoff.h"
 
 namespace cct {
 bool gilbert_table(int width, int height, int32_t *out);
@@ -58,6 +59,28 @@ struct ShapeTables {  // everything that depends on (width, height) only; lives 
 	StreamTiles tiles;                // host copy: travels in the kernel arguments
 };
 
+// What an encode call still uses after it has given its slot to the next call ("queue ahead", encode_batch_impl): the next
+// call records and copies into the slot's other set meanwhile.  Two per slot; handoff.h says who owns which, and until when.
+struct HandoffSet {
+	EventPair stage, pass;        // timing: around the transform+pack stage, around the device DEFLATE pass
+	hipEvent_t landed = nullptr;  // sizes and status have reached `landing`
+	DevBuf landing;               // pinned: a call's sizes / status / statistics (a copy to pageable memory blocks the host until it has happened)
+	DevBuf packed;                // the packed archive of a pass: it leaves the device on the copy stream, after the slot has been released
+	hipEvent_t ev_packed = nullptr, ev_copied = nullptr;  // created with the slot's copy stream (pack_enqueue)
+	HandoffSet() { landing.pinned_host = true; }
+	int create()  // ensure_ctx: no steady-state call creates an event
+	{
+		for (hipEvent_t *e : {&stage.e0, &stage.e1, &pass.e0, &pass.e1}) HIP_TRY(hipEventCreate(e));
+		HIP_TRY(hipEventCreateWithFlags(&landed, hipEventDisableTiming));
+		return CCT_OK;
+	}
+	void release()  // cct_shutdown, every stream drained
+	{
+		stage.release(); pass.release(); landing.release(); packed.release();
+		for (hipEvent_t *e : {&landed, &ev_packed, &ev_copied}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+	}
+};
+
 // Everything one encode batch in flight owns: stream, workspaces, the captured DEFLATE graph.  There are two of them.
 // Several kernels of the DEFLATE pass are latency-bound and leave most of the chip idle (the Huffman tree kernel runs one
 // serial heap replay per block for over a millisecond; the match kernel waits on scattered loads), so a second batch on a
@@ -70,17 +93,14 @@ struct EncSlot {
 	struct ZGraph { std::vector<uint8_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; uint64_t last_use = 0; };
 	std::vector<ZGraph> z_graphs;  // a batch deflated in several passes has one argument set per pass (round 2 kept ONE graph and
 	uint64_t z_clock = 0;          // captured it again for every pass of such a batch: 5 ms per step at 512 x 1024^2)
-	// packed archives leave the device on their own stream from one of two buffers, after the slot has been
-	// released: the next encode call may start its kernels while this one's files are still on the wire
+	// packed archives leave the device on their own stream from the packed buffer of a hand-off set, after the slot has
+	// been released: the next encode call may start its kernels while this one's files are still on the wire
 	hipStream_t stream_copy = nullptr;
-	hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-	DevBuf z_packed2[2];
-	unsigned pack_slot = 0;
+	HandoffSet sets[2];
 	// encode workspaces
 	DevBuf e_role, e_lidx, e_lmask, e_lcur, e_images, e_payload, e_sizes, e_status, e_stats;
 	DevBuf e_pairrec, e_hand;  // streaming kernel: meshed-pair records, hand-off words and tickets
 	DevBuf h_stage;  // pinned host staging (payloads)
-	DevBuf h_small[2];  // pinned landing place of a call's sizes / status / statistics (a copy to pageable memory blocks the host until it has happened)
 	DevBuf z_ws[DFL_REGIONS];  // workspace of the device DEFLATE pass, one buffer per region of deflate_workspace.h
 	DevBuf z_out, z_outsizes, z_in, z_insizes, z_packed, z_packoffs;  // its input and output, and the packed files
 	DevBuf png_img, png_out, png_sizes;  // PNG writer: rasters from the host, files, their sizes (cct_png_encode_batch, cct_png_encode8_batch)
@@ -89,26 +109,19 @@ struct EncSlot {
 	const void *z_mr_cleared = nullptr;
 	size_t z_mr_cleared_cap = 0;
 	unsigned z_gen_passes = 0;
-	// timing events of an encode call, two sets: with the slot handed on before the host has synchronised (encode_batch_impl,
-	// "queue ahead") the next call records its own while this one has not read its durations yet
-	hipEvent_t ev_k0s[2] = {nullptr, nullptr}, ev_k1s[2] = {nullptr, nullptr};  // around the transform+pack stage
-	hipEvent_t ev_z0s[2] = {nullptr, nullptr}, ev_z1s[2] = {nullptr, nullptr};  // around the device DEFLATE pass
-	hipEvent_t ev_small[2] = {nullptr, nullptr};                                // sizes and status have reached the host
-	hipStream_t stream_side = nullptr;                                          // side branch of the DEFLATE pass (launch_deflate)
+	hipStream_t stream_side = nullptr;  // side branch of the DEFLATE pass (launch_deflate)
 	hipEvent_t ev_fork[4] = {nullptr, nullptr, nullptr, nullptr};
 	EventPair ev_zlib;  // around the DEFLATE pass of cct_zlib_compress_batch*
-	unsigned call_parity = 0;
 	DevBuf *all_bufs[48];
 	int n_bufs = 0;
 	EncSlot()
 	{
 		DevBuf *b[] = {&e_role, &e_lidx, &e_lmask, &e_lcur, &e_images, &e_payload, &e_sizes, &e_status, &e_stats, &e_pairrec,
-		               &e_hand, &h_stage, &z_out, &z_outsizes, &z_in, &z_insizes, &z_packed, &z_packoffs, &z_packed2[0], &z_packed2[1],
-		               &h_small[0], &h_small[1], &png_img, &png_out, &png_sizes};
+		               &e_hand, &h_stage, &z_out, &z_outsizes, &z_in, &z_insizes, &z_packed, &z_packoffs,
+		               &png_img, &png_out, &png_sizes};
 		for (DevBuf *p : b) all_bufs[n_bufs++] = p;
 		for (DevBuf &w : z_ws) all_bufs[n_bufs++] = &w;  // cct_shutdown releases them with the rest
 		h_stage.pinned_host = true;
-		h_small[0].pinned_host = h_small[1].pinned_host = true;
 	}
 	EncSlot(const EncSlot &) = delete;
 	EncSlot &operator=(const EncSlot &) = delete;
@@ -134,6 +147,11 @@ struct DecSlot {
 		               &d_zstatus, &dh_stage, &d_png_z, &d_png_tab, &d_png_bpp};
 		for (DevBuf *p : b) all_bufs[n_bufs++] = p;
 		dh_stage.pinned_host = true;
+	}
+	void release()  // cct_shutdown, the stream drained
+	{
+		for (int i = 0; i < n_bufs; i++) all_bufs[i]->release();
+		for (hipEvent_t *e : {&ev_d0, &ev_d1, &ev_k_dec0, &ev_k_dec1, &ev_ws}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
 	}
 	DecSlot(const DecSlot &) = delete;
 	DecSlot &operator=(const DecSlot &) = delete;
@@ -214,11 +232,7 @@ void reset_ctx()
 // decode driven from two threads do not overwrite each other's numbers
 thread_local float tl_enc_kernel_ms = 0, tl_dec_kernel_ms = 0, tl_d2h_ms = 0, tl_deflate_ms = 0, tl_inflate_ms = 0, tl_h2d_ms = 0;
 std::mutex g_mu1;     // encode slot 1
-// A call that has handed its slot on before its files left the device ("queue ahead", encode_batch_impl) still owns one of the
-// slot's two packed-archive buffers until it has queued the copy out of it; the call after next waits here before packing into it.
-std::mutex g_pack_mu;
-std::condition_variable g_pack_cv;
-bool g_pack_busy[N_ENC_SLOTS][2] = {};
+HandoffRing g_handoff[N_ENC_SLOTS];  // who owns which of EncSlot::sets; like the slot mutexes they outlive reset_ctx()
 std::mutex g_mu_dec[N_DEC_SLOTS];  // the decode slots; like g_mu / g_mu1 they outlive reset_ctx(), which replaces the slot objects
 std::mutex g_mu_lut;  // the per-shape table cache (taken after g_mu by encode, alone by decode)
 
@@ -271,13 +285,8 @@ int ensure_ctx(int device)
 		E.mu = k == 0 ? &g_mu : &g_mu1;
 		if (k == 0) E.stream = g_ctx.stream;
 		else HIP_TRY(hipStreamCreateWithFlags(&E.stream, hipStreamNonBlocking));
-		for (int q = 0; q < 2; q++) {
-			HIP_TRY(hipEventCreate(&E.ev_k0s[q]));
-			HIP_TRY(hipEventCreate(&E.ev_k1s[q]));
-			HIP_TRY(hipEventCreate(&E.ev_z0s[q]));
-			HIP_TRY(hipEventCreate(&E.ev_z1s[q]));
-			HIP_TRY(hipEventCreateWithFlags(&E.ev_small[q], hipEventDisableTiming));
-		}
+		for (HandoffSet &S : E.sets)
+			if (int rc = S.create()) return rc;
 		for (int q = 0; q < 4; q++) HIP_TRY(hipEventCreateWithFlags(&E.ev_fork[q], hipEventDisableTiming));
 	}
 	for (int k = 0; k < N_DEC_SLOTS; k++) {
@@ -888,10 +897,8 @@ int cct_shutdown(void)
 		if (E.stream_copy) (void)hipStreamSynchronize(E.stream_copy);
 		for (auto &g : E.z_graphs) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
 		for (int i = 0; i < E.n_bufs; i++) E.all_bufs[i]->release();
-		hipEvent_t evs[] = {E.ev_k0s[0], E.ev_k1s[0], E.ev_z0s[0], E.ev_z1s[0], E.ev_k0s[1], E.ev_k1s[1], E.ev_z0s[1], E.ev_z1s[1],
-		                    E.ev_small[0], E.ev_small[1], E.ev_pack[0], E.ev_pack[1], E.ev_copied[0], E.ev_copied[1],
-		                    E.ev_fork[0], E.ev_fork[1], E.ev_fork[2], E.ev_fork[3]};
-		for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+		for (HandoffSet &S : E.sets) S.release();
+		for (hipEvent_t e : E.ev_fork) if (e) (void)hipEventDestroy(e);
 		E.ev_zlib.release();
 		if (E.stream_copy) (void)hipStreamDestroy(E.stream_copy);
 		if (E.stream_side) { (void)hipStreamSynchronize(E.stream_side); (void)hipStreamDestroy(E.stream_side); }
@@ -910,9 +917,7 @@ int cct_shutdown(void)
 	for (int k = 0; k < N_DEC_SLOTS; k++) {
 		DecSlot &D = g_dec[k];
 		if (D.stream) (void)hipStreamSynchronize(D.stream);
-		for (int i = 0; i < D.n_bufs; i++) D.all_bufs[i]->release();
-		hipEvent_t evs[] = {D.ev_d0, D.ev_d1, D.ev_k_dec0, D.ev_k_dec1, D.ev_ws};
-		for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
+		D.release();
 		if (k > 0 && D.stream) (void)hipStreamDestroy(D.stream);
 	}
 	(void)hipStreamDestroy(g_ctx.stream);
@@ -1155,55 +1160,41 @@ struct FilesOut {
 	std::vector<size_t> offs;  // 16-byte aligned offsets of the files in a strided-pack buffer
 };
 
-// archive layout, whole batch, page-locked destination: pack into one of two device buffers, hand the copy to the copy
-// stream and give the slot back (lk) before waiting for it -- the next batch's kernels start while these files travel
-// first half: pack the files of a pass into one of the two device buffers (offsets computed on the device from the sizes, so
-// this can be queued right behind the DEFLATE pass, before the host knows the sizes -- the pack used to start a launch
-// latency after the host had read them); `cap` = what the buffer must hold
-static int pack_enqueue(EncSlot &E, int nc, size_t zstride, size_t cap, unsigned *slot_out)
+// archive layout, page-locked destination, first half: pack the files of a pass into the packed buffer of a hand-off set the
+// call owns (offsets computed on the device from the sizes, so this can be queued right behind the DEFLATE pass, before the
+// host knows the sizes -- the pack used to start a launch latency after the host had read them); `cap` = what the buffer must hold
+static int pack_enqueue(EncSlot &E, HandoffSet &S, int nc, size_t zstride, size_t cap)
 {
 	int rc;
-	const unsigned slot = E.pack_slot++ & 1u;
-	{
-		std::unique_lock<std::mutex> pl(g_pack_mu);
-		g_pack_cv.wait(pl, [&] { return !g_pack_busy[&E - g_enc][slot]; });
-	}
 	if (!E.stream_copy) {
 		const int crc = exclusive_section([&]() -> int {
 			HIP_TRY(hipStreamCreateWithFlags(&E.stream_copy, hipStreamNonBlocking));
-			for (int k = 0; k < 2; k++) {
-				HIP_TRY(hipEventCreateWithFlags(&E.ev_pack[k], hipEventDisableTiming));
-				HIP_TRY(hipEventCreateWithFlags(&E.ev_copied[k], hipEventDisableTiming));
-				HIP_TRY(hipEventRecord(E.ev_copied[k], E.stream_copy));
+			for (HandoffSet &s : E.sets) {
+				HIP_TRY(hipEventCreateWithFlags(&s.ev_packed, hipEventDisableTiming));
+				HIP_TRY(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming));
+				HIP_TRY(hipEventRecord(s.ev_copied, E.stream_copy));
 			}
 			return CCT_OK;
 		});
 		if (crc) return crc;
 	}
-	if (E.z_packed2[slot].cap < cap) HIP_TRY(hipEventSynchronize(E.ev_copied[slot]));  // about to be reallocated
-	if ((rc = E.z_packed2[slot].ensure(cap))) return rc;
+	if (S.packed.cap < cap) HIP_TRY(hipEventSynchronize(S.ev_copied));  // about to be reallocated
+	if ((rc = S.packed.ensure(cap))) return rc;
 	if ((rc = E.z_packoffs.ensure((size_t)(nc + 1) * 8))) return rc;
-	HIP_TRY(hipStreamWaitEvent(E.stream, E.ev_copied[slot], 0));  // the copy out of this buffer two calls ago
+	HIP_TRY(hipStreamWaitEvent(E.stream, S.ev_copied, 0));  // the copy out of this buffer by the set's owner before
 	HIP_TRY(launch_pack((const uint8_t *)E.z_out.p, zstride, (const uint32_t *)E.z_outsizes.p, nc,
-	                    (uint64_t *)E.z_packoffs.p, (uint8_t *)E.z_packed2[slot].p, 1, E.stream));
-	HIP_TRY(hipEventRecord(E.ev_pack[slot], E.stream));
-	*slot_out = slot;
+	                    (uint64_t *)E.z_packoffs.p, (uint8_t *)S.packed.p, 1, E.stream));
+	HIP_TRY(hipEventRecord(S.ev_packed, E.stream));
 	return CCT_OK;
 }
 
-// archive layout, whole batch, page-locked destination: pack into one of two device buffers (unless pack_enqueue has done so:
-// packed_slot >= 0), hand the copy to the copy stream and give the slot back (the caller does) before waiting for it -- the
+// second half: the packed files to the copy stream.  The caller gives the slot back before it waits for S.ev_copied -- the
 // next batch's kernels start while these files travel
-static int files_to_pinned_archive_async(FilesOut &f, uint8_t *h_dst, int packed_slot, hipEvent_t *done)
+static int packed_to_pinned_archive_async(EncSlot &E, HandoffSet &S, size_t exact, uint8_t *h_dst)
 {
-	EncSlot &E = f.E;
-	int rc;
-	unsigned slot = (unsigned)packed_slot;
-	if (packed_slot < 0 && (rc = pack_enqueue(E, f.nc, f.zstride, f.offs[f.nc] + 16, &slot))) return rc;  // (the pack kernel works in 16-byte units)
-	HIP_TRY(hipStreamWaitEvent(E.stream_copy, E.ev_pack[slot], 0));
-	HIP_TRY(hipMemcpyAsync(h_dst, E.z_packed2[slot].p, f.exact, hipMemcpyDeviceToHost, E.stream_copy));
-	HIP_TRY(hipEventRecord(E.ev_copied[slot], E.stream_copy));
-	*done = E.ev_copied[slot];
+	HIP_TRY(hipStreamWaitEvent(E.stream_copy, S.ev_packed, 0));
+	HIP_TRY(hipMemcpyAsync(h_dst, S.packed.p, exact, hipMemcpyDeviceToHost, E.stream_copy));
+	HIP_TRY(hipEventRecord(S.ev_copied, E.stream_copy));
 	return CCT_OK;
 }
 
@@ -1260,15 +1251,13 @@ static int files_to_strided(FilesOut &f, uint8_t *h_first, size_t out_stride)
 
 // DEFLATE (or none) on the host thread team: payloads come back, libz at `level` per slice (9: core.py:340), header in front
 static int files_on_host(EncSlot &E, int n, size_t stride, const std::vector<uint32_t> &psz, const uint8_t hdr13[13], bool defl,
-                         int level, int strategy, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, const uint32_t *h_status)
+                         int level, int strategy, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes)
 {
 	const double t_copy0 = now_ms();
 	uint8_t *stage = (uint8_t *)E.h_stage.p;
-	for (int i = 0; i < n; i++) {  // bring back only the bytes each slice produced
-		if (h_status[i] & CCT_ST_CAP) return fail(CCT_E_CAP, "slice %d overflowed its payload stride", i);
+	for (int i = 0; i < n; i++)  // bring back only the bytes each slice produced (none has overflowed its stride: the caller has looked)
 		HIP_TRY(hipMemcpyAsync(stage + (size_t)i * stride, (uint8_t *)E.e_payload.p + (size_t)i * stride, psz[i],
 		                       hipMemcpyDeviceToHost, E.stream));
-	}
 	HIP_TRY(hipStreamSynchronize(E.stream));
 	const double t_defl0 = now_ms();
 	tl_d2h_ms = (float)(t_defl0 - t_copy0);
@@ -1303,6 +1292,25 @@ static int files_on_host(EncSlot &E, int n, size_t stride, const std::vector<uin
 	return CCT_OK;
 }
 
+// CCT_FLAG_DEFLATE_LEVEL / _STRATEGY fields of an encode call -> zlib level and strategy; the fields leave `flags` (the payload
+// stage and the .cct header do not depend on them)
+static int take_deflate_fields(uint32_t &flags, int *level, int *strategy)
+{
+	*strategy = flags_deflate_strategy(flags);
+	if (*strategy < 0)
+		return fail(CCT_E_ARG, "deflate strategy field %u: zlib strategies are 0 .. 4", (flags & CCT_FLAG_STRATEGY_MASK) >> 12);
+	*level = flags_deflate_level(flags, *strategy);
+	if (*level < 0) {
+		if (*strategy == 2 || *strategy == 3)
+			return fail(CCT_E_ARG, "deflate level field %u with strategy %d: levels 1 .. 9 only",
+			            (flags & CCT_FLAG_LEVEL_MASK) >> 8, *strategy);
+		return fail(CCT_E_ARG, "deflate level field %u with strategy %d: levels 4 .. 9 only (1 .. 3 are deflate_fast: not on the device)",
+		            (flags & CCT_FLAG_LEVEL_MASK) >> 8, *strategy);
+	}
+	flags &= ~(CCT_FLAG_LEVEL_MASK | CCT_FLAG_STRATEGY_MASK);
+	return CCT_OK;
+}
+
 static int encode_batch_impl(const uint16_t *images, int images_on_device, int n, int width, int height, int block_size,
                              uint32_t flags, int eof_byte, const char magic[4], int channels, int bytes_per_channel,
                              uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, uint32_t *h_status,
@@ -1313,38 +1321,37 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 	const bool packed = h_packed_offsets != nullptr;
 	const double t_call0 = now_ms();
 	EncodeInFlight in_flight;  // decode calls that start meanwhile pick the INFLATE geometry that shares the device best
-	const int strategy = flags_deflate_strategy(flags);
-	if (strategy < 0)
-		return fail(CCT_E_ARG, "deflate strategy field %u: zlib strategies are 0 .. 4", (flags & CCT_FLAG_STRATEGY_MASK) >> 12);
-	const int level = flags_deflate_level(flags, strategy);
-	if (level < 0) {
-		if (strategy == 2 || strategy == 3)
-			return fail(CCT_E_ARG, "deflate level field %u with strategy %d: levels 1 .. 9 only",
-			            (flags & CCT_FLAG_LEVEL_MASK) >> 8, strategy);
-		return fail(CCT_E_ARG, "deflate level field %u with strategy %d: levels 4 .. 9 only (1 .. 3 are deflate_fast: not on the device)",
-		            (flags & CCT_FLAG_LEVEL_MASK) >> 8, strategy);
-	}
-	flags &= ~(CCT_FLAG_LEVEL_MASK | CCT_FLAG_STRATEGY_MASK);  // the payload stage and the .cct header do not depend on them
-	int rc = check_shape(n, width, height, block_size);
-	if (rc) return rc;
+	int level, strategy, rc;
+	if ((rc = take_deflate_fields(flags, &level, &strategy))) return rc;
+
+	// ---- checks, context, slot, hand-off set ----
+	if ((rc = check_shape(n, width, height, block_size))) return rc;
 	if (!(g_ctx.ready && g_ctx.pid == getpid())) {  // first use in this process: bind the device
 		std::lock_guard<std::mutex> lk0(g_mu);
 		if ((rc = ensure_ctx())) return rc;
 	}
 	std::unique_lock<std::mutex> lk;
 	EncSlot &E = acquire_encode_slot(lk);
-	ApiCall in_call;  // after the slot: a thread waiting for a slot must not keep exclusive sections of the others waiting
+	HandoffRing &ring = g_handoff[&E - g_enc];
+	HandoffOwner own(ring);  // waits for the call two before this one; released where this call stops using the set, at the latest on return
+	HandoffSet &S = E.sets[own.set()];
+	ApiCall in_call;  // after the slot and the set: a thread waiting for either must not keep exclusive sections of the others waiting
 	const double t_lock0 = now_ms();
 	if ((rc = ensure_ctx())) return rc;
 	if (n == 0) return CCT_OK;
 	const size_t N = (size_t)width * height;
 	const size_t stride = cct_payload_stride(width, height, block_size);
+	const size_t zstride = cct_file_bound(width, height, block_size);
 	const bool defl = (flags & CCT_FLAG_DEFLATE) != 0;
-	if (!packed && out_stride < (defl ? cct_file_bound(width, height, block_size) : 13 + stride))
-		return fail(CCT_E_CAP, "out_stride %zu too small", out_stride);
+	if (!packed && out_stride < (defl ? zstride : 13 + stride)) return fail(CCT_E_CAP, "out_stride %zu too small", out_stride);
 	if (packed && !(defl && g_ctx.device_deflate))
 		return fail(CCT_E_ARG, "packed output needs deflate_compression with the device DEFLATE path");
+	// With DEFLATE on the device and the whole batch in one pass the host does not need sizes or status before
+	// the DEFLATE kernels are queued (they read the sizes on the device; a payload cannot outgrow its stride):
+	// one host synchronisation less per batch.
+	const bool one_pass = defl && g_ctx.device_deflate && (size_t)n * stride <= DEFLATE_PASS_BYTES;
 
+	// ---- transform+pack stage enqueued: uploads, workspaces, the kernels between their events, sizes / status / statistics back ----
 	const uint16_t *d_img = images;
 	if (!images_on_device) {
 		if ((rc = E.e_images.ensure((size_t)n * N * 2))) return rc;
@@ -1356,154 +1363,140 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 	if ((rc = E.e_status.ensure((size_t)n * 4))) return rc;
 	if ((rc = E.h_stage.ensure((size_t)n * stride))) return rc;
 	if ((rc = E.e_stats.ensure((size_t)n * sizeof(cct_slice_stats)))) return rc;
-	// (running this stage on a stream of the highest priority while the other slot is in its DEFLATE pass was tried: the
-	// kernels took as long as without, waves already resident are not displaced)
-	const unsigned par = E.call_parity++ & 1u;
-	// queue ahead (see below): possible when the whole call can be queued without the host knowing a size
-	const bool qa = packed && defl && g_ctx.device_deflate && g_ctx.queue_ahead && (size_t)n * stride <= DEFLATE_PASS_BYTES &&
-	                is_pinned_host(h_out, 1);
-	uint32_t *l_psz = nullptr, *l_status = nullptr, *l_osz = nullptr;  // landing places in pinned memory
-	cct_slice_stats *l_stats = nullptr;
+	// Queue ahead: possible when the whole call can be queued without the host knowing a size, into an archive that is
+	// page-locked over every byte the call can write.  Everything this call needs from the slot is in the stream then, so
+	// the slot goes to the next call BEFORE the host waits for the sizes: that call's kernels are queued behind this one's
+	// while they run, and the device no longer idles for a launch latency between one batch's pack and the next batch's
+	// first kernel and again before its DEFLATE graph (0.2 ms of a 4.2 ms step, profiles/r03_bench_timeline.log).  From
+	// the hand-over on the call touches its hand-off set and the copy stream only.
+	const bool qa = packed && one_pass && g_ctx.queue_ahead && is_pinned_host(h_out, std::min(out_stride, (size_t)n * zstride));
+	std::vector<uint32_t> psz(n);
+	uint32_t *l_psz = psz.data(), *l_status = h_status, *l_osz = nullptr;  // where the device's words land: with queue ahead in pinned memory
+	cct_slice_stats *l_stats = h_stats;
 	if (qa) {
-		if ((rc = E.h_small[par].ensure((size_t)n * (12 + sizeof(cct_slice_stats))))) return rc;
-		l_psz = (uint32_t *)E.h_small[par].p; l_status = l_psz + n; l_osz = l_status + n;
+		if ((rc = S.landing.ensure((size_t)n * (12 + sizeof(cct_slice_stats))))) return rc;
+		l_psz = (uint32_t *)S.landing.p; l_status = l_psz + n; l_osz = l_status + n;
 		l_stats = (cct_slice_stats *)(l_osz + n);
 	}
-	const hipEvent_t ev_k0 = E.ev_k0s[par], ev_k1 = E.ev_k1s[par], ev_z0 = E.ev_z0s[par], ev_z1 = E.ev_z1s[par];
-	float t_dev_deflate_ms = 0;
-	HIP_TRY(hipEventRecord(ev_k0, E.stream));
+	// (running this stage on a stream of the highest priority while the other slot is in its DEFLATE pass was tried: the
+	// kernels took as long as without, waves already resident are not displaced)
+	if ((rc = S.stage.begin(E.stream))) return rc;
 	rc = encode_payload_locked(E, E.stream, d_img, n, width, height, block_size, flags, eof_byte, (uint8_t *)E.e_payload.p, stride,
 	                           (uint32_t *)E.e_sizes.p, (uint32_t *)E.e_status.p,
 	                           h_stats ? (cct_slice_stats *)E.e_stats.p : nullptr, nullptr);
 	if (rc) return rc;
-	HIP_TRY(hipEventRecord(ev_k1, E.stream));
+	if ((rc = S.stage.end(E.stream))) return rc;
 	HIP_TRY(launch_gate_bump(g_gate, E.stream));  // decode kernels waiting for this stage to be over may go (cct_decode_batch)
-	if (h_stats)
-		HIP_TRY(hipMemcpyAsync(qa ? l_stats : h_stats, E.e_stats.p, (size_t)n * sizeof(cct_slice_stats), hipMemcpyDeviceToHost, E.stream));
-	std::vector<uint32_t> psz(n);
+	if (h_stats) HIP_TRY(hipMemcpyAsync(l_stats, E.e_stats.p, (size_t)n * sizeof(cct_slice_stats), hipMemcpyDeviceToHost, E.stream));
 	StreamDrain drain(E.stream);  // until the first synchronisation below
-	HIP_TRY(hipMemcpyAsync(qa ? l_psz : psz.data(), E.e_sizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
-	HIP_TRY(hipMemcpyAsync(qa ? l_status : h_status, E.e_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
-	// With DEFLATE on the device and the whole batch in one pass the host does not need sizes or status before
-	// the DEFLATE kernels are queued (they read the sizes on the device; a payload cannot outgrow its stride):
-	// one host synchronisation less per batch.
-	const bool one_pass = defl && g_ctx.device_deflate && (size_t)n * stride <= DEFLATE_PASS_BYTES;
+	HIP_TRY(hipMemcpyAsync(l_psz, E.e_sizes.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+	HIP_TRY(hipMemcpyAsync(l_status, E.e_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+	tl_enc_kernel_ms = 0;
 	if (!one_pass) {
 		HIP_TRY(hipStreamSynchronize(E.stream));
 		drain.disarm();
-		HIP_TRY(hipEventElapsedTime(&tl_enc_kernel_ms, ev_k0, ev_k1));
+		if ((rc = S.stage.add_ms(tl_enc_kernel_ms))) return rc;
+		for (int i = 0; i < n; i++)
+			if (h_status[i] & CCT_ST_CAP) return fail(CCT_E_CAP, "slice %d overflowed its payload stride", i);
 	}
 	uint8_t hdr13[13];
 	make_header13(hdr13, magic, width, height, channels, bytes_per_channel, flags);
-	if (defl && g_ctx.device_deflate) {
-		// DEFLATE on the device: zlib.compress(data, level) (core.py:340, level 9) restated in deflate_kernels.hip
-		if (!one_pass)
+
+	// ---- DEFLATE (or none) on the host thread team ----
+	if (!(defl && g_ctx.device_deflate)) {
+		rc = files_on_host(E, n, stride, psz, hdr13, defl, level, strategy, h_out, out_stride, h_out_sizes);
+		if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
+		return rc;
+	}
+
+	// ---- DEFLATE on the device: zlib.compress(data, level) (core.py:340, level 9) restated in deflate_kernels.hip ----
+	// bounded workspaces: at most DEFLATE_PASS_BYTES of payload per pass, in passes of equal size (several DEFLATE
+	// kernels give a slice one workgroup: a short last pass would leave most of the chip idle)
+	const int chunk_max = (int)std::max<size_t>(1, DEFLATE_PASS_BYTES / stride);
+	const int n_passes = (n + chunk_max - 1) / chunk_max;
+	const int chunk = (n + n_passes - 1) / n_passes;
+	tl_deflate_ms = 0; tl_d2h_ms = 0;
+	std::optional<StreamDrain> copies;  // on the copy stream, from the first copy into the caller's archive on: an error return must not leave one in flight
+	for (int c0 = 0, pass = 0; c0 < n; c0 += chunk, pass++) {
+		const int nc = std::min(chunk, n - c0);
+		const bool last = c0 + nc >= n;
+		uint32_t *osz = h_out_sizes + c0;
+		// the pass enqueued, with queue ahead the pack as well (the common pipelined case)
+		if ((rc = S.pass.begin(E.stream))) return rc;
+		rc = deflate_locked(E, (const uint8_t *)E.e_payload.p + (size_t)c0 * stride, stride,
+		                    (const uint32_t *)E.e_sizes.p + c0, nc, hdr13, zstride, level, strategy);
+		if (rc) return rc;
+		if ((rc = S.pass.end(E.stream))) return rc;
+		HIP_TRY(launch_gate_bump(g_gate + 1, E.stream));
+		g_gate_passes_issued.fetch_add(1, std::memory_order_relaxed);  // (only once the bump is in the stream: a count that is ahead of the device for good makes every later gate wait run to its timeout)
+		if (qa && (rc = pack_enqueue(E, S, nc, zstride, (size_t)nc * zstride + 16))) return rc;
+		HIP_TRY(hipMemcpyAsync(qa ? l_osz : osz, E.z_outsizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, E.stream));
+		// handed on, or synchronised
+		if (qa) {
+			HIP_TRY(hipEventRecord(S.landed, E.stream));
+			lk.unlock();
+			HIP_TRY(hipEventSynchronize(S.landed));
+			memcpy(psz.data(), l_psz, (size_t)n * 4); memcpy(h_status, l_status, (size_t)n * 4); memcpy(osz, l_osz, (size_t)nc * 4);
+			if (h_stats) memcpy(h_stats, l_stats, (size_t)n * sizeof(cct_slice_stats));
+		} else HIP_TRY(hipStreamSynchronize(E.stream));
+		drain.disarm();  // nothing queued targets this frame any more (later chunks copy into caller memory and synchronise at once)
+		float t_dev_deflate_ms = 0;
+		if ((rc = S.pass.add_ms(t_dev_deflate_ms))) return rc;
+		if (one_pass) {
+			if ((rc = S.stage.add_ms(tl_enc_kernel_ms))) return rc;
 			for (int i = 0; i < n; i++)
 				if (h_status[i] & CCT_ST_CAP) return fail(CCT_E_CAP, "slice %d overflowed its payload stride", i);
-		const size_t zstride = cct_file_bound(width, height, block_size);
-		// bounded workspaces: at most DEFLATE_PASS_BYTES of payload per pass, in passes of equal size (several DEFLATE
-		// kernels give a slice one workgroup: a short last pass would leave most of the chip idle)
-		const int chunk_max = (int)std::max<size_t>(1, DEFLATE_PASS_BYTES / stride);
-		const int n_passes = (n + chunk_max - 1) / chunk_max;
-		const int chunk = (n + n_passes - 1) / n_passes;
-		tl_deflate_ms = 0; tl_d2h_ms = 0;
-		struct CopyGuard {  // an error return must not leave a copy into the caller's archive in flight
-			EncSlot &E; bool armed = false;
-			~CopyGuard() { if (armed && E.stream_copy) (void)hipStreamSynchronize(E.stream_copy); }
-		} copies_in_flight{E};
-		for (int c0 = 0; c0 < n; c0 += chunk) {
-			const int nc = std::min(chunk, n - c0);
-			HIP_TRY(hipEventRecord(ev_z0, E.stream));
-			rc = deflate_locked(E, (const uint8_t *)E.e_payload.p + (size_t)c0 * stride, stride,
-			                    (const uint32_t *)E.e_sizes.p + c0, nc, hdr13, zstride, level, strategy);
-			if (rc) return rc;
-			HIP_TRY(hipEventRecord(ev_z1, E.stream));
-			g_gate_passes_issued.fetch_add(1, std::memory_order_relaxed);
-			HIP_TRY(launch_gate_bump(g_gate + 1, E.stream));
-			int packed_slot = -1;
-			if (qa) {  // the common pipelined case: pack queued behind the pass
-				unsigned ps = 0;
-				if ((rc = pack_enqueue(E, nc, zstride, (size_t)nc * zstride + 16, &ps))) return rc;
-				packed_slot = (int)ps;
-			}
-			uint32_t *osz = h_out_sizes + c0;
-			HIP_TRY(hipMemcpyAsync(qa ? l_osz : osz, E.z_outsizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, E.stream));
-			// Queue ahead: everything this call needs from the slot is in the stream now, so the slot goes to the next call
-			// BEFORE the host waits for the sizes: that call's kernels are queued behind this one's while they run, and the
-			// device no longer idles for a launch latency between one batch's pack and the next batch's first kernel and
-			// again before its DEFLATE graph (0.2 ms of a 4.2 ms step, profiles/r03_bench_timeline.log).  From here on the
-			// call touches its own events, its packed buffer (g_pack_busy) and the copy stream only.
-			struct PackOwner {
-				int e = -1; unsigned slot = 0;
-				void release() { if (e >= 0) { { std::lock_guard<std::mutex> pl(g_pack_mu); g_pack_busy[e][slot] = false; } g_pack_cv.notify_all(); e = -1; } }
-				~PackOwner() { release(); }
-			} pack_owner;
-			const bool queue_ahead = qa;
-			if (queue_ahead) {
-				HIP_TRY(hipEventRecord(E.ev_small[par], E.stream));
-				{ std::lock_guard<std::mutex> pl(g_pack_mu); g_pack_busy[&E - g_enc][packed_slot] = true; }
-				pack_owner.e = (int)(&E - g_enc); pack_owner.slot = (unsigned)packed_slot;
-				lk.unlock();
-				HIP_TRY(hipEventSynchronize(E.ev_small[par]));
-				memcpy(psz.data(), l_psz, (size_t)n * 4); memcpy(h_status, l_status, (size_t)n * 4); memcpy(osz, l_osz, (size_t)nc * 4);
-				if (h_stats) memcpy(h_stats, l_stats, (size_t)n * sizeof(cct_slice_stats));
-			} else HIP_TRY(hipStreamSynchronize(E.stream));
-			drain.disarm();  // nothing queued targets this frame any more (later chunks copy into caller memory and synchronise at once)
-			HIP_TRY(hipEventElapsedTime(&t_dev_deflate_ms, ev_z0, ev_z1));
-			if (one_pass) {
-				HIP_TRY(hipEventElapsedTime(&tl_enc_kernel_ms, ev_k0, ev_k1));
-				for (int i = 0; i < n; i++)
-					if (h_status[i] & CCT_ST_CAP) return fail(CCT_E_CAP, "slice %d overflowed its payload stride", i);
-			}
-			tl_deflate_ms += t_dev_deflate_ms;
-			const double t_c0 = now_ms();
-			FilesOut f{E, nc, osz, zstride, 0, std::vector<size_t>(nc + 1, 0)};
-			for (int i = 0; i < nc; i++) { f.exact += osz[i]; f.offs[i + 1] = f.offs[i] + (((size_t)osz[i] + 15) & ~(size_t)15); }
-			if (packed_slot < 0 && (rc = E.z_packoffs.ensure((size_t)(nc + 1) * 8))) return rc;
-			if (!packed) {
-				if ((rc = files_to_strided(f, h_out + (size_t)c0 * out_stride, out_stride))) return rc;
-				tl_d2h_ms += (float)(now_ms() - t_c0);
-				continue;
-			}
-			if (c0 == 0) h_packed_offsets[0] = 0;
-			const uint64_t at = h_packed_offsets[c0];
-			if (at + f.exact > out_stride) return fail(CCT_E_CAP, "packed output needs %zu bytes", (size_t)(at + f.exact));
-			for (int i = 0; i < nc; i++) h_packed_offsets[c0 + i + 1] = h_packed_offsets[c0 + i] + osz[i];
-			if (is_pinned_host(h_out + at, f.exact)) {
-				// page-locked archive: the files of this pass leave on the copy stream while the next pass (or, after the last
-				// one, the next batch) already runs its kernels
-				hipEvent_t done = nullptr;
-				if ((rc = files_to_pinned_archive_async(f, h_out + at, packed_slot, &done))) return rc;
-				pack_owner.release();  // the copy out of the buffer is queued: the call after next may pack into it
-				copies_in_flight.armed = true;
-				tl_d2h_ms += (float)(now_ms() - t_c0);
-				if (c0 + nc < n) continue;
-				if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
-				const float t_defl = t_dev_deflate_ms;
-				const double t_unlock = now_ms();
-				if (lk.owns_lock()) lk.unlock();  // the slot is free for the next batch; only the copy stream still works for this one
-				HIP_TRY(hipEventSynchronize(done));
-				copies_in_flight.armed = false;
-				if (getenv("CCT_TRACE"))
-					fprintf(stderr, "[cct] encode n=%d: waited for a slot %.2f ms, held it %.2f ms (kernel %.2f, deflate %.2f), tail %.2f ms, t=%.2f\n", nc,
-					        t_lock0 - t_call0, t_unlock - t_lock0, tl_enc_kernel_ms, t_defl, now_ms() - t_unlock, t_lock0);
-				tl_d2h_ms += (float)(now_ms() - t_c0);  // (no lock: a float for cct_last_timings)
-				return CCT_OK;
-			}
-			if (queue_ahead) return fail(CCT_E_ARG, "the archive buffer is page-locked at its start but not over the %zu bytes of this batch", f.exact);
+		}
+		tl_deflate_ms += t_dev_deflate_ms;
+		// delivered: strided, into a page-locked archive, or into any archive
+		const double t_c0 = now_ms();
+		FilesOut f{E, nc, osz, zstride, 0, std::vector<size_t>(nc + 1, 0)};
+		for (int i = 0; i < nc; i++) { f.exact += osz[i]; f.offs[i + 1] = f.offs[i] + (((size_t)osz[i] + 15) & ~(size_t)15); }
+		if (!qa && (rc = E.z_packoffs.ensure((size_t)(nc + 1) * 8))) return rc;
+		if (!packed) {
+			if ((rc = files_to_strided(f, h_out + (size_t)c0 * out_stride, out_stride))) return rc;
+			tl_d2h_ms += (float)(now_ms() - t_c0);
+			continue;
+		}
+		if (c0 == 0) h_packed_offsets[0] = 0;
+		const uint64_t at = h_packed_offsets[c0];
+		if (at + f.exact > out_stride) return fail(CCT_E_CAP, "packed output needs %zu bytes", (size_t)(at + f.exact));
+		for (int i = 0; i < nc; i++) h_packed_offsets[c0 + i + 1] = h_packed_offsets[c0 + i] + osz[i];
+		if (!is_pinned_host(h_out + at, f.exact) && !qa) {  // (queue ahead has checked the whole archive)
 			double t_c1 = t_c0;
 			if ((rc = files_to_archive(f, h_out + at, &t_c1))) return rc;
 			tl_d2h_ms += (float)(now_ms() - t_c0);
 			if (getenv("CCT_TRACE"))
 				fprintf(stderr, "[cct] encode n=%d: deflate %.2f ms, pack+d2h %.2f ms, host scatter %.2f ms (%zu bytes)\n", nc,
 				        t_dev_deflate_ms, t_c1 - t_c0, now_ms() - t_c1, f.exact);
+			continue;
 		}
+		// page-locked archive: the files of this pass leave on the copy stream while the next pass (or, after the last one,
+		// the next batch) already runs its kernels.  A call of several passes keeps the slot and alternates the two packed
+		// buffers: every second pass borrows the other set's, waiting for a call queued ahead of this one that still owns it.
+		std::optional<HandoffOwner> borrowed;
+		if (pass & 1) borrowed.emplace(ring, own.set() ^ 1u);
+		HandoffSet &P = E.sets[own.set() ^ (pass & 1u)];
+		if (!qa && (rc = pack_enqueue(E, P, nc, zstride, f.offs[nc] + 16))) return rc;  // (the pack kernel works in 16-byte units)
+		if (!copies) copies.emplace(E.stream_copy);
+		if ((rc = packed_to_pinned_archive_async(E, P, f.exact, h_out + at))) return rc;
+		// the copy out of the buffer is queued, durations and landing words are read: the call after next may have the set
+		if (borrowed) borrowed->release(); else if (last) own.release();
+		tl_d2h_ms += (float)(now_ms() - t_c0);
+		if (!last) continue;
 		if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
+		const double t_unlock = now_ms();
+		if (lk.owns_lock()) lk.unlock();  // the slot is free for the next batch; only the copy stream still works for this one
+		HIP_TRY(hipEventSynchronize(P.ev_copied));
+		copies->disarm();
+		if (getenv("CCT_TRACE"))
+			fprintf(stderr, "[cct] encode n=%d: waited for a slot %.2f ms, held it %.2f ms (kernel %.2f, deflate %.2f), tail %.2f ms, t=%.2f\n", nc,
+			        t_lock0 - t_call0, t_unlock - t_lock0, tl_enc_kernel_ms, t_dev_deflate_ms, now_ms() - t_unlock, t_lock0);
+		tl_d2h_ms += (float)(now_ms() - t_c0);  // (no lock: a float for cct_last_timings)
 		return CCT_OK;
 	}
-	rc = files_on_host(E, n, stride, psz, hdr13, defl, level, strategy, h_out, out_stride, h_out_sizes, h_status);
 	if (h_payload_sizes) memcpy(h_payload_sizes, psz.data(), (size_t)n * 4);
-	return rc;
+	return CCT_OK;
 }
 
 int cct_encode_batch(const uint16_t *images, int images_on_device, int n, int width, int height, int block_size,

@@ -893,3 +893,124 @@ def test_pipelined_packed_calls_with_and_without_the_scheduling_measures(hip, sc
             b.free()
         for p_ in pins:
             p_.free()
+
+
+def _serial_packed_reference(hip, L, batch, cfg):
+    """One call at a time, strided layout (cct_encode_batch): the files back to back, payload sizes, status words, statistics."""
+    import ctypes as C
+    from cct_hip import _ffi
+    flags, bs, eof, magic, ch, bpc = hip.codec_params(cfg, np.uint16)
+    n, W = batch.shape[0], batch.shape[1]
+    stride = L.cct_file_bound(W, W, bs)
+    out = np.zeros((n, stride), dtype=np.uint8)
+    sizes, status, psizes = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    stats = (_ffi.SliceStats * n)()
+    _ffi.check(L.cct_encode_batch(batch.ctypes.data, 0, n, W, W, bs, flags, eof, magic, ch, bpc, out.ctypes.data, stride,
+                                  sizes.ctypes.data, status.ctypes.data, psizes.ctypes.data, C.cast(stats, C.c_void_p)))
+    files = [out[i, :sizes[i]].tobytes() for i in range(n)]
+    assert files == hip.encode_batch(batch, cfg)
+    return b"".join(files), psizes, status, bytes(stats)
+
+
+@pytest.mark.parametrize("threads", [3, 4])
+def test_queue_ahead_calls_from_more_threads_than_handoff_sets(hip, threads):
+    """Three and four threads in cct_encode_batch_packed on ONE encode slot with the queue-ahead handover: a slot has two
+    hand-off sets (events, landing buffer, packed buffer), so the call after next must wait for the set's owner instead of
+    recording over its events and landing words.  Batches of 8, 12, 16 and 12 slices, so that landing and packed
+    buffers grow while a set is owned; every second thread asks for statistics.  Ten calls per thread: each returns 0 and
+    leaves the serial call's archive, payload sizes, status words and statistics."""
+    import ctypes as C
+    import threading
+    from cct_hip import _ffi
+    from cct_hip.batch import PinnedArray, DeviceBuffer
+    L = _ffi.lib()
+    cfg = hip.default_config()
+    flags, bs, eof, magic, ch, bpc = hip.codec_params(cfg, np.uint16)
+    W, CALLS = 256, 10
+    ns = [8, 12, 16, 12][:threads]
+    batches = [np.stack([gi.ct_phantom(1000 * t + i, W) for i in range(n)]) for t, n in enumerate(ns)]
+    serial = [_serial_packed_reference(hip, L, b, cfg) for b in batches]
+    caps = [L.cct_file_bound(W, W, bs) * n for n in ns]
+    d_imgs = [DeviceBuffer.from_numpy(b) for b in batches]
+    pins = [PinnedArray(cap) for cap in caps]
+    start = threading.Barrier(threads)
+    failures = [[] for _ in range(threads)]
+    done = [0] * threads
+
+    def caller(t):
+        n = ns[t]
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        sizes, status, psizes = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        stats = (_ffi.SliceStats * n)() if t % 2 else None
+        start.wait()
+        for i in range(CALLS):
+            pins[t].array[:] = 0
+            for a in (offs, sizes, status, psizes):
+                a[:] = 0xFFFFFFFF
+            rc = L.cct_encode_batch_packed(d_imgs[t].ptr, 1, n, W, W, bs, flags, eof, magic, ch, bpc, pins[t].ptr, caps[t],
+                                           offs.ctypes.data, sizes.ctypes.data, status.ctypes.data, psizes.ctypes.data,
+                                           C.cast(stats, C.c_void_p) if stats is not None else None)
+            ref, ref_psizes, ref_status, ref_stats = serial[t]
+            if rc != 0:
+                failures[t].append(f"call {i}: rc {rc}: {_ffi.last_error()}")
+            elif pins[t].array[:int(offs[n])].tobytes() != ref:
+                failures[t].append(f"call {i}: archive differs")
+            elif not (np.array_equal(psizes, ref_psizes) and np.array_equal(status, ref_status)):
+                failures[t].append(f"call {i}: payload sizes or status differ")
+            elif not np.array_equal(np.diff(offs.astype(np.int64)), sizes):
+                failures[t].append(f"call {i}: offsets and sizes disagree")
+            elif stats is not None and bytes(stats) != ref_stats:
+                failures[t].append(f"call {i}: statistics differ")
+            done[t] += 1
+
+    opt = C.c_int(0)
+    _ffi.check(L.cct_get_option(b"encode_slots", C.byref(opt)))
+    assert opt.value == 1
+    _ffi.check(L.cct_set_option(b"queue_ahead", 1))
+    pool = [threading.Thread(target=caller, args=(t,), daemon=True) for t in range(threads)]  # daemon: a lost wake-up fails the test, it does not hold the job
+    for th in pool:
+        th.start()
+    for th in pool:
+        th.join(timeout=120)
+    assert not any(th.is_alive() for th in pool), f"calls finished per thread: {done} of {CALLS}"
+    assert failures == [[] for _ in range(threads)]
+    assert done == [CALLS] * threads
+    for b in d_imgs:
+        b.free()
+    for p_ in pins:
+        p_.free()
+
+
+def test_packed_archive_page_locked_over_its_first_page_only(hip):
+    """An archive whose first page is page-locked and whose rest is ordinary memory: the queue-ahead handover needs the
+    whole archive page-locked, so the call takes the ordinary path and delivers the serial bytes."""
+    import ctypes as C
+    from cct_hip import _ffi
+    from cct_hip.batch import DeviceBuffer
+    L = _ffi.lib()
+    cfg = hip.default_config()
+    flags, bs, eof, magic, ch, bpc = hip.codec_params(cfg, np.uint16)
+    n, W = 8, 256
+    batch = np.stack([gi.ct_phantom(2000 + i, W) for i in range(n)])
+    ref, ref_psizes, ref_status, _ = _serial_packed_reference(hip, L, batch, cfg)
+    assert len(ref) > 2 * 4096
+    cap = L.cct_file_bound(W, W, bs) * n
+    # the HIP runtime the library itself runs on, to page-lock one page of an ordinary buffer
+    with open("/proc/self/maps") as f:
+        runtime = C.CDLL(next(ln.split()[-1] for ln in f if "libamdhip64" in ln))
+    buf = np.zeros(cap + 4096, dtype=np.uint8)
+    at = (-buf.ctypes.data) % 4096
+    base = buf.ctypes.data + at
+    assert runtime.hipHostRegister(C.c_void_p(base), C.c_size_t(4096), C.c_uint(0)) == 0
+    d_img = DeviceBuffer.from_numpy(batch)
+    try:
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        sizes, status, psizes = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        _ffi.check(L.cct_set_option(b"queue_ahead", 1))
+        _ffi.check(L.cct_encode_batch_packed(d_img.ptr, 1, n, W, W, bs, flags, eof, magic, ch, bpc, base, cap, offs.ctypes.data,
+                                             sizes.ctypes.data, status.ctypes.data, psizes.ctypes.data, None))
+        assert buf[at:at + int(offs[n])].tobytes() == ref
+        assert np.array_equal(psizes, ref_psizes) and np.array_equal(status, ref_status)
+    finally:
+        assert runtime.hipHostUnregister(C.c_void_p(base)) == 0
+        d_img.free()
