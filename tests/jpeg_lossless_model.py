@@ -305,13 +305,12 @@ def decode_frame(f, rows, cols, bits=16):
     for k, data in enumerate(intervals_of(f[h["s0"]:h["s1"]], n_int)):
         need = min(rpi, rows - k * rpi) * cols
         nbits, pos = 8 * len(data), 0
-        word = int.from_bytes(data, "big")
 
-        def take(n):
+        def take(n):  # from the bytes that hold the n bits, so that a long interval costs no more per bit than a short one
             nonlocal pos
             if pos + n > nbits:
                 raise JpegError("STREAM", "entropy data ends early")
-            v = (word >> (nbits - pos - n)) & ((1 << n) - 1)
+            v = (int.from_bytes(data[pos >> 3:(pos + n + 7) >> 3], "big") >> (-(pos + n) & 7)) & ((1 << n) - 1)
             pos += n
             return v
 

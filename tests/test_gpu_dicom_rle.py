@@ -1,6 +1,7 @@
 """Device DICOM RLE Lossless codec (cct_dicom_rle_encode_batch / _decode_batch) against tests/dicom_rle_model.py: frames
 byte for byte, rasters from the device's, the model's and libtiff's frames, hand-built segments, packet heads on every
-offset of a decoder tile, per-frame refusals, and the RLE column of tools/evaluate.py."""
+offset of a decoder tile, the lenient rules and the one refusal over several tiles and across a batch of the tile chain,
+per-frame refusals, and the RLE column of tools/evaluate.py."""
 import functools
 import importlib.util
 import os
@@ -207,6 +208,192 @@ def test_decode_refusals_leave_the_rest_alone():
         cct_hip.dicom_rle_decode_batch(batch, rows, cols)
     with pytest.raises(_ffi.CorruptStreamError):
         cct_hip.dicom_rle_decode_batch([g[:10]], rows, cols)
+
+
+# ---- lenient semantics and refusals beyond one tile and one chain batch ---------------------------------------------------
+
+def packets_prefix(s, rng):
+    """s bytes of packets: nothing, a no-op, or one literal"""
+    return b"" if s == 0 else bytes([128]) if s == 1 else bytes([s - 2]) + rng.integers(0, 256, s - 1, dtype=np.uint8).tobytes()
+
+
+def literal(n, rng):
+    """a literal packet of n bytes whose data never reads as a no-op head"""
+    return bytes([n - 1]) + rng.integers(0, 128, n, dtype=np.uint8).tobytes()
+
+
+def verdict(frame, rows, cols, bits):
+    """dicom_rle_model.decode_frame: the raster, or None for a ValueError (CCT_E_STREAM)"""
+    try:
+        return m.decode_frame(frame, rows, cols, bits)
+    except ValueError:
+        return None
+
+
+@functools.lru_cache(maxsize=None)
+def several_tiles():
+    """name -> (frame, raster or None) at 49 x 128, 8 bits: segments of more than 3 tiles of 129-byte literal packets"""
+    rows, cols = 49, 128
+    N = rows * cols
+    rng = np.random.default_rng(31)
+    full = [literal(128, rng) for _ in range(49)]
+    good = b"".join(full)
+    assert len(good) == 49 * 129 > 3 * TILE
+    segs = {"undamaged": good}
+    # 47 full packets, one of 100, a full one, and a last that claims 101 bytes: 28 complete the plane
+    head = b"".join(full[:47]) + literal(100, rng) + full[47]
+    tail = literal(101, rng)
+    assert len(head) > 3 * TILE and 47 * 128 + 100 + 128 + 28 == N
+    segs["literal_cut_at_completion"] = head + tail[:1 + 28]
+    segs["literal_cut_one_byte_before_completion"] = head + tail[:1 + 27]
+    # a replicate header as the last byte of the segment gives nothing
+    head = b"".join(full[:48]) + literal(126, rng)
+    segs["replicate_header_without_value"] = head + bytes([255])
+    segs["replicate_header_with_value"] = head + bytes([255, 9])
+    segs["replicate_header_behind_a_complete_plane"] = good + bytes([200])
+    # 4095 bytes that give N - 50, then a run of 100 whose header is the last byte of tile 1 and whose value opens tile 2
+    parts = []
+    for k in range(30):
+        parts.append(full[k])
+        if k < 19:
+            parts.append(bytes([257 - (128 if k < 18 else 78), 40 + k]))
+        parts.append(bytes([128]) * (7 if k < 7 else 6))
+    head = b"".join(parts)
+    assert len(head) == 2 * TILE - 1 and 30 * 128 + 18 * 128 + 78 == N - 50
+    segs["run_past_the_plane_from_the_last_byte_of_tile_1"] = head + bytes([257 - 100, 0x5A]) + full[30]
+    # spare packets behind completion fill tile 4
+    segs["a_spare_tile"] = good + b"".join(literal(128, rng) for _ in range(17))
+    assert len(segs["a_spare_tile"]) > 4 * TILE + 129
+    # one packet head changed: every later head moves, the plane comes out short, long or equal
+    spare = good + literal(128, rng)
+    for k in range(40):
+        j = int(rng.integers(16, 49))  # heads 129 j: tiles 1 .. 3
+        h = int(rng.choice([int(rng.integers(0, 127)), int(rng.integers(128, 256))]))
+        sg = spare if k % 3 == 0 else good  # with and without a spare packet to make up for what the change loses
+        assert TILE <= 129 * j < 4 * TILE and sg[129 * j] == 127
+        segs[f"head_{j}_becomes_{h}{'_spare_packet' if k % 3 == 0 else ''}"] = sg[:129 * j] + bytes([h]) + sg[129 * j + 1:]
+    return rows, cols, {name: (frame8(sg), verdict(frame8(sg), rows, cols, 8)) for name, sg in segs.items()}
+
+
+def test_decode_lenient_over_several_tiles():
+    import cct_hip
+    rows, cols, cases_ = several_tiles()
+    good = cases_["undamaged"][1]
+    heads = [w for name, (_, w) in cases_.items() if name.startswith("head_")]
+    assert sum(w is None for w in heads) >= 10 and sum(w is not None and not np.array_equal(w, good) for w in heads) >= 10
+    for name in ("literal_cut_at_completion", "replicate_header_with_value", "replicate_header_behind_a_complete_plane",
+                 "run_past_the_plane_from_the_last_byte_of_tile_1", "a_spare_tile"):
+        assert cases_[name][1] is not None, name
+    for name in ("literal_cut_one_byte_before_completion", "replicate_header_without_value"):
+        assert cases_[name][1] is None, name
+    assert (cases_["run_past_the_plane_from_the_last_byte_of_tile_1"][1].ravel()[-50:] == 0x5A).all()
+    back, status = cct_hip.dicom_rle_decode_batch([f for f, _ in cases_.values()], rows, cols, bits=8, raise_errors=False)
+    for (name, (_, w)), b, st in zip(cases_.items(), back, status):
+        assert st == (E_STREAM if w is None else 0), name
+        if w is not None:
+            assert np.array_equal(b, w), name
+
+
+CHAIN_ROWS, CHAIN_COLS = 256, 520
+CHAIN_BATCH = 64  # csrc/dicom_rle_kernels.hip CHAIN_TILES
+
+
+def chain_segment(s, rng):
+    """A segment of more than 64 tiles that gives exactly 256 x 520 bytes: s bytes of packets, then 129-byte literals, every
+    tile entered at another offset.  Behind the first whole literal whose head lies in tile 63, and in tile 64, sit a literal
+    of 64 bytes and a no-op.  -> (segment, {63: (head of the whole literal, head of the short one), 64: ...})"""
+    N = CHAIN_ROWS * CHAIN_COLS
+    seg = bytearray(packets_prefix(s, rng))
+    out, marks = max(s - 1, 0), {}
+    while N - out > 128 + 64:
+        tile = len(seg) // TILE
+        seg += literal(128, rng)
+        out += 128
+        if tile in (CHAIN_BATCH - 1, CHAIN_BATCH) and tile not in marks:
+            marks[tile] = (len(seg) - 129, len(seg))
+            seg += literal(64, rng) + bytes([128])
+            out += 64
+    while out < N:
+        n = min(128, N - out)
+        seg += literal(n, rng)
+        out += n
+    assert sorted(marks) == [CHAIN_BATCH - 1, CHAIN_BATCH] and len(seg) > (CHAIN_BATCH + 1) * TILE
+    return bytes(seg), marks
+
+
+def chain_damages(seg, marks):
+    """name -> segment: a whole literal made one byte shorter (its last byte becomes a no-op, the plane ends one byte short),
+    and the 64-byte literal made one longer (it takes the no-op as data, the plane is complete one byte early)"""
+    out = {"undamaged": seg}
+    for tile, (whole, short) in marks.items():
+        assert seg[whole] == 127 and seg[short] == 63 and seg[short + 65] == 128 and whole // TILE == tile
+        out[f"one_byte_short_in_tile_{tile}"] = seg[:whole] + bytes([126]) + seg[whole + 1:whole + 128] + bytes([128]) + seg[whole + 129:]
+        out[f"one_byte_long_in_tile_{tile}"] = seg[:short] + bytes([64]) + seg[short + 1:]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def chain_cases():
+    """[(name, frame, bits, raster or None, name of its undamaged frame)]"""
+    rng = np.random.default_rng(64)
+    out, segs = [], {}
+    for s in (0, 1, 64, 127, 128):
+        seg, marks = chain_segment(s, rng)
+        segs[s] = chain_damages(seg, marks)
+        for name, sg in segs[s].items():
+            out.append((f"prefix_{s}_{name}", frame8(sg), 8, f"prefix_{s}_undamaged"))
+    for s, t in ((0, 127), (1, 64), (64, 0), (127, 128), (128, 1)):  # the high segment of odd length: the low one starts on an odd offset
+        for name in ("undamaged", f"one_byte_short_in_tile_{CHAIN_BATCH}", f"one_byte_long_in_tile_{CHAIN_BATCH - 1}"):
+            hi, lo = segs[s][name], segs[t]["undamaged"]
+            if len(hi) % 2 == 0:
+                hi += bytes([128])
+            out.append((f"high_{s}_{name}_low_{t}", struct.pack("<16I", 2, 64, 64 + len(hi), *([0] * 13)) + hi + lo, 16, f"high_{s}_undamaged_low_{t}"))
+    return [(name, f, bits, verdict(f, CHAIN_ROWS, CHAIN_COLS, bits), base) for name, f, bits, base in out]
+
+
+@pytest.mark.parametrize("bits", [8, 16])
+def test_decode_chain_batches_entered_off_zero(bits):
+    import cct_hip
+    mine = [c for c in chain_cases() if c[2] == bits]
+    good = {c[0]: c[3] for c in mine if c[0] == c[4]}
+    assert len(good) == 5
+    for name, f, _, w, base in mine:
+        assert (w is None) == ("short" in name), name
+        if "long" in name:
+            assert not np.array_equal(w, good[base]), name
+    back, status = cct_hip.dicom_rle_decode_batch([c[1] for c in mine], CHAIN_ROWS, CHAIN_COLS, bits=bits, raise_errors=False)
+    for (name, _, _, w, _), b, st in zip(mine, back, status):
+        assert st == (E_STREAM if w is None else 0), name
+        if w is not None:
+            assert np.array_equal(b, w), name
+    with pytest.raises(cct_hip._ffi.CorruptStreamError):
+        cct_hip.dicom_rle_decode_batch([c[1] for c in mine], CHAIN_ROWS, CHAIN_COLS, bits=bits)
+    assert np.array_equal(cct_hip.dicom_rle_decode_batch([c[1] for c in mine if c[3] is not None], CHAIN_ROWS, CHAIN_COLS, bits=bits),
+                          np.stack([c[3] for c in mine if c[3] is not None]))
+
+
+def test_decode_short_long_segments_leave_the_rest_alone():
+    """segments of 66 tiles that end one byte short, between good frames, into a device buffer that holds a sentinel"""
+    import cct_hip
+    by_name = {c[0]: c for c in chain_cases() if c[2] == 8}
+    order = ["prefix_0_undamaged", f"prefix_64_one_byte_short_in_tile_{CHAIN_BATCH - 1}", "prefix_127_undamaged",
+             f"prefix_1_one_byte_short_in_tile_{CHAIN_BATCH}", f"prefix_128_one_byte_short_in_tile_{CHAIN_BATCH}", "prefix_1_undamaged"]
+    batch = [by_name[k] for k in order]
+    n = len(batch)
+    sentinel = np.full((n + 1, CHAIN_ROWS, CHAIN_COLS), 0xA5, np.uint8)
+    d = cct_hip.DeviceBuffer.from_numpy(sentinel)
+    try:
+        shape, status = cct_hip.dicom_rle_decode_batch([c[1] for c in batch], CHAIN_ROWS, CHAIN_COLS, bits=8, out_dev=d, raise_errors=False)
+        got = d.download(np.uint8, sentinel.size).reshape(sentinel.shape)
+    finally:
+        d.free()
+    assert shape == (n, CHAIN_ROWS, CHAIN_COLS)
+    assert list(status) == [0, E_STREAM, 0, E_STREAM, E_STREAM, 0]
+    for i, c in enumerate(batch):
+        assert (c[3] is None) == (status[i] != 0)
+        if c[3] is not None:
+            assert np.array_equal(got[i], c[3]), c[0]
+    assert (got[n] == 0xA5).all()  # the slot behind the batch
 
 
 def test_evaluate_tool_fills_the_rle_column(tmp_path):
