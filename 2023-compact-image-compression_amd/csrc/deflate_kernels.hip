@@ -539,12 +539,36 @@ __device__ __forceinline__ void light_match_from_memory(const uint8_t *in, const
 
 // QL: the quarter chain (max_chain >> 2) ends inside the light walk (levels 4 and 5), so the lane records it on its own;
 // otherwise the light walk never gets past it and the quarter record is the full one.
+//
+// Time: the kernel is bound by neither its instructions nor its bytes: its waves are parked two thirds of their life
+// (DESIGN.md 5), so a turn leaves as few round trips on its path as it can, and a wave makes many turns (launch_deflate), since
+// its entry (a chain of scalar loads, the first records) and its last flush are the part that nothing overlaps.
+//  - The records of the wave's NEXT turn are requested before this turn's chain walk and waited for at the top of the next
+//    turn (same clamped addresses as the turn itself would use: past the last turn they re-read records below npos).
+//  - Queued positions (kind 1 and 2) collect in a region of LDS that the wave owns (no barrier: LDS traffic of one wave keeps
+//    program order) with the two counts in registers.  A list is flushed after the wave's last turn, and earlier whenever fewer
+//    than 64 entries of its region are free: one returning atomicAdd of the whole count, then contiguous stores.  Before, lane 0
+//    paid two returning atomics on the slice's two counters in every turn, behind the turn's scattered stores.
+//    The order of the entries in the two lists depended on which wave's atomic won before and does now; dfl_match_heavy_kernel
+//    and dfl_match_run_kernel treat every entry on its own, so the bytes of the result do not depend on it.
+// MATCH_Q entries per wave and list: 2 KiB * MATCH_Q / 256 per wave, 8 KiB per workgroup at 256, and eight workgroups of a CU
+// hold 64 of its 160 KiB: the 8 waves per SIMD that the registers allow stay.
+#ifndef DFL_MATCH_Q
+#define DFL_MATCH_Q 256
+#endif
+#ifndef DFL_MATCH_GRID
+#define DFL_MATCH_GRID 32  // workgroups per slice with compact records, at least (launch_deflate)
+#endif
+constexpr uint32_t MATCH_Q = DFL_MATCH_Q;
+static_assert(MATCH_Q >= 128 && (MATCH_Q & 63) == 0, "a turn appends up to 64 entries to a list");
+
 template <bool CMP, bool QL>
-__global__ void dfl_match_kernel(DeflateArgs a, int n)
+__global__ void __launch_bounds__(256) dfl_match_kernel(DeflateArgs a, int n)
 {
+	__shared__ uint32_t queue[4][2][MATCH_Q];  // [wave][0 heavy, 1 run]
 	int s; uint32_t part, nparts;
 	if (!xcd_slice(n, s, part, nparts)) return;
-	const uint32_t L = a.in_sizes[s];
+	const uint32_t L = a.in_sizes[s], gen = *a.gen;  // (both requested at entry, neither behind the other)
 	const uint8_t *in = a.in + (size_t)s * a.in_stride;
 	const size_t base = (size_t)s * a.in_stride;
 	const uint32_t npos = L >= MIN_MATCH ? L - 2 : 0;
@@ -554,15 +578,37 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 	const uint16_t *rl = a.run_len + base;
 	const int lane = threadIdx.x & 63;
 	const uint64_t lt_mask = (1ull << lane) - 1ull;
-	const uint32_t gen = *a.gen;
 	const int quarter = QL ? (int)(a.max_chain >> 2) : LIGHT_STEPS + 1;
-	for (uint32_t i0 = part * blockDim.x; i0 < npos; i0 += nparts * blockDim.x) {  // wave-uniform trip count
+	const uint32_t stride = nparts * 256u;
+	uint32_t i0 = part * 256u;
+	if (i0 >= npos) return;  // (the whole workgroup: nothing to read, nothing queued)
+	uint32_t *qh = queue[threadIdx.x >> 6][0], *qr = queue[threadIdx.x >> 6][1];
+	uint32_t nh = 0, nr = 0;  // entries waiting in qh / qr (wave-uniform)
+	// lane l takes entry l, l + 64, ...; the heavy list grows upwards, the run list downwards from the end
+	auto flush = [&](const uint32_t *q, uint32_t cnt, uint32_t *counter, bool down) {
+		uint32_t b = 0;
+		if (lane == 0) b = atomicAdd(counter, cnt);
+		b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+		__builtin_amdgcn_wave_barrier();  // one wave: LDS order is program order; keep the compiler to it as well
+		for (uint32_t k = (uint32_t)lane; k < cnt; k += 64u) {
+			if (down) *(dfl_deep_top(heavy, a.in_stride) - (b + k)) = q[k];
+			else heavy[b + k] = q[k];
+		}
+		__builtin_amdgcn_wave_barrier();
+	};
+	// sorted index i and, with compact records, i - 64 (lane l: index (wave's first) + l - 64, unused where that is negative)
+	auto rec_at = [&](uint32_t i) { return recs[min(i, npos - 1)]; };
+	auto rec_before = [&](uint32_t i) { return recs[min(i >= 64 ? i - 64 : 0u, npos - 1)]; };
+	uint64_t ri_next = rec_at(i0 + threadIdx.x), rb_next = CMP ? rec_before(i0 + threadIdx.x) : 0ull;
+	for (; i0 < npos; i0 += stride) {  // wave-uniform trip count
 		const uint32_t i = i0 + threadIdx.x;
 		const bool valid = i < npos;
 		int kind = 0;  // 0: record written, 1: queue for the cooperative heavy pass, 2: queue for the run pass
 		int best = 0, best1 = 0;
 		uint32_t best_q = 0, best_q1 = 0, run_r = 0;
-		const uint64_t ri = recs[min(i, npos - 1)];
+		const uint64_t ri = ri_next, rb = rb_next;
+		ri_next = rec_at(i + stride);
+		if (CMP) rb_next = rec_before(i + stride);
 		const uint32_t p = rec_pos(ri, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu);
 		const uint32_t h = rec_hash(ri, CMP ? COMPACT_POS_MASK : 0xFFFFFFFFu);
 		bool from_memory = valid;
@@ -571,7 +617,6 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 			// The chain of sorted index i is i-1, i-2, ...: the records of the lanes below, then of the 64 indices before the wave.
 			// Both sit in registers (one coalesced load each) and move up one lane per step, so a step waits for nothing; with
 			// one load per step a wave paid a memory round trip for every entry of its longest chain.
-			const uint64_t rb = recs[min(i >= 64 ? i - 64 : 0u, npos - 1)];  // lane l: index (wave's first) + l - 64, unused where that is negative
 			const uint32_t lo_i = (uint32_t)ri, hi_i = (uint32_t)(ri >> 32), lo_b = (uint32_t)rb, hi_b = (uint32_t)(rb >> 32);
 			const uint32_t lookahead = L - p;
 			const int max_len = lookahead < (uint32_t)MAX_MATCH ? (int)lookahead : MAX_MATCH;
@@ -634,17 +679,16 @@ __global__ void dfl_match_kernel(DeflateArgs a, int n)
 			if (!QL) { best1 = best; best_q1 = best_q; }
 			mr[p] = pack_match((uint32_t)best, (uint32_t)best1, p - best_q, best1 ? p - best_q1 : 0u, gen);
 		}
-		// wave-aggregated appends: one atomic per wave and list
+		// queued positions go to the wave's regions (at least 64 entries of each are free here)
 		const uint64_t bh = __ballot(kind == 1), br = __ballot(kind == 2);
-		uint32_t base_h = 0, base_r = 0;
-		if (lane == 0) {
-			if (bh) base_h = atomicAdd(&a.heavy_count[s], (uint32_t)__popcll(bh));
-			if (br) base_r = atomicAdd(&a.deep_count[s], (uint32_t)__popcll(br));
-		}
-		base_h = (uint32_t)__shfl((int)base_h, 0, 64); base_r = (uint32_t)__shfl((int)base_r, 0, 64);
-		if (kind == 1) heavy[base_h + (uint32_t)__popcll(bh & lt_mask)] = i;
-		if (kind == 2) *(dfl_deep_top(heavy, a.in_stride) - (base_r + (uint32_t)__popcll(br & lt_mask))) = i;  // grows downwards from the end
+		if (kind == 1) qh[nh + (uint32_t)__popcll(bh & lt_mask)] = i;
+		if (kind == 2) qr[nr + (uint32_t)__popcll(br & lt_mask)] = i;
+		nh += (uint32_t)__popcll(bh); nr += (uint32_t)__popcll(br);
+		if (nh > MATCH_Q - 64u) { flush(qh, nh, &a.heavy_count[s], false); nh = 0; }
+		if (nr > MATCH_Q - 64u) { flush(qr, nr, &a.deep_count[s], true); nr = 0; }
 	}
+	if (nh) flush(qh, nh, &a.heavy_count[s], false);
+	if (nr) flush(qr, nr, &a.deep_count[s], true);
 }
 
 // Wave-cooperative longest_match for one position whose chain is long: 64 candidates per step, at most max_chain in all.
@@ -2342,15 +2386,19 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, hipStream_t st, hipStream
 	}
 	hipLaunchKernelGGL(dfl_run_lists_kernel, dim3(a.run_chunks, n), dim3(256), 0, s2, a);
 	hipLaunchKernelGGL(dfl_run_info_kernel, dim3(8, n), dim3(256), 0, s2, a);
-	// neither depends on anything before it: beside the match kernel, which is bound by its instructions, they are off the
+	// neither depends on anything before it: beside the match kernel, whose waves mostly wait, they are off the
 	// serial path (the clear takes 30 us here and 11 us alone; the pass is shorter this way)
 	launch_clear(a, n, s2);
 	hipLaunchKernelGGL(dfl_offsets2_kernel, dim3(256), dim3(256), 0, s2, a, n);
 	// wide records: one 256-lane block per 256 positions (more of them in flight hide the scattered accesses better than grid-stride
-	// loops); compact records: the kernel is bound by its instructions, and 256 blocks per slice with four turns each measured best
-	// (486 us against 499 / 510 with 128 / 512, profiles/r03_match_grid.log)
-	const int gm_cap = a.pos_mask == COMPACT_POS_MASK ? 256 : 2048;
-	const int gm = (int)std::min<size_t>(gm_cap, (a.in_stride + 255) / 256), n8 = (n + 7) & ~7;  // see xcd_slice()
+	// loops).  Compact records: the kernel's waves mostly wait, and with the next turn's records in flight a wave
+	// that makes more turns wastes less of its life on its entry and its last flush, so a slice gets as few workgroups as still
+	// fill an XCD (256 of them) with the slices it works through, xcd_slice(): DFL_MATCH_GRID of them in a large batch (33 turns
+	// on a bench payload; 256 slices: 426 us against 445 / 437 / 509 / 553 with 16 / 64 / 128 / 256 and 485 with 8,
+	// profiles/match_prefetch_sweeps.log), 256 for up to eight slices as before
+	const int n8 = (n + 7) & ~7;  // see xcd_slice()
+	const int gm_cap = a.pos_mask == COMPACT_POS_MASK ? std::max(DFL_MATCH_GRID, 256 / std::max(1, n8 / 8)) : 2048;
+	const int gm = (int)std::min<size_t>(gm_cap, (a.in_stride + 255) / 256);
 	if (a.max_chain < 16 || a.max_chain > 4096 || a.nice < 16 || a.nice > (uint32_t)MAX_MATCH) return hipErrorInvalidValue;  // levels 4 .. 9
 	const bool ql = (a.max_chain >> 2) <= (uint32_t)LIGHT_STEPS;  // the quarter chain ends inside the light walk
 	if (a.pos_mask == COMPACT_POS_MASK) {
