@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CCT_HIP_LIB") or os.path.join(_HERE, "libcompact_hip.so")  # CCT_HIP_LIB: tuning builds (tools/ab_build.sh)
 
 # error codes (include/compact_hip.h)
-OK, E_MAGIC, E_ZLIB, E_OVERFLOW, E_STREAM, E_SHAPE, E_CAP, E_NOMEM, E_DEVICE, E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K = range(15)
+OK, E_MAGIC, E_ZLIB, E_OVERFLOW, E_STREAM, E_SHAPE, E_CAP, E_NOMEM, E_DEVICE, E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K, E_TIFF = range(16)
 FLAG_FRACTAL, FLAG_SEGMENTATION, FLAG_DEFLATE, FLAG_SIGNED_SEG = 1, 2, 4, 8
 FLAG_LEVEL_MASK = 0xF00
 
@@ -113,6 +113,12 @@ _SIGS = {
                                              C.c_void_p]),
     "cct_dicom_rle_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_size_t, C.c_void_p]),
+    "cct_tiff_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cct_tiff_encode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cct_tiff_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cct_tiff_read_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t,
+                                      C.c_void_p]),
     "cct_jpegll_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "cct_j2k_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "cct_j2k_encode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -182,7 +188,7 @@ def raise_for(rc):
         raise MemoryError(msg)
     if rc == E_DEVICE:
         raise DeviceError(msg)
-    if rc in (E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K):
+    if rc in (E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K, E_TIFF):
         raise ValueError(msg)
     raise RuntimeError(f"libcompact_hip error {rc}: {msg}")
 

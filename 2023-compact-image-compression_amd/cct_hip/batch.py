@@ -955,3 +955,101 @@ def jpeg2000_decode_batch(files, rows, cols, bits=16, shift=0, out_dev=None, rai
     blob, offs = _archive(files)
     return _decode_rasters(lambda *to: L.cct_j2k_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, shift, *to), n, rows,
                            cols, dt, out_dev, raise_errors, (_ffi.E_J2K, _ffi.E_MIXED, _ffi.E_STREAM))
+
+
+# ---- strip-organised grayscale TIFF (TIFF 6.0; LZW, Deflate, horizontal predictor): files on the device -----------------
+
+_TIFF_COMPRESSION = {"none": 1, "lzw": 5, "deflate": 8}
+
+
+def _check_tiff_shape(rows, cols):
+    if not 1 <= rows <= 65535 or not 1 <= cols <= 65535:
+        raise ValueError(f"TIFF raster of {rows} x {cols} samples: rows and cols are 1 to 65535")
+
+
+def tiff_encode_batch(images, compression="lzw", predictor=1, rows_per_strip=None, level=6, shape=None, dtype=None):
+    """Grayscale TIFF files on the device: a uint16 or uint8 array of shape (n, rows, cols) or (rows, cols), or a DeviceBuffer
+    with shape= given (dtype= np.uint16 unless np.uint8 is named), -> a list of n `bytes`.  compression is "lzw", "deflate" or
+    "none"; predictor 1 or 2 (horizontal differencing; not with "none"); rows_per_strip None for Pillow's rule (strips of at
+    most 64 KiB, one row at least) or a height from 1 up, clamped to rows; level (4 to 9, -1 = 6) is Deflate's.  With "lzw",
+    and with "deflate" at level 6, the file is byte for byte what Pillow 12 / libtiff 4.7 write for the raster
+    (compression="tiff_lzw" / "tiff_adobe_deflate", tiffinfo={317: 2} for predictor 2, TiffImagePlugin.STRIP_SIZE =
+    rows_per_strip * row bytes where one is given); at other levels every strip is zlib.compress(strip, level) in the same
+    layout, and "none" uses that layout too.  tests/tiff_model.py states layout and coder.  Arguments are checked (TypeError /
+    ValueError) before any device call."""
+    src, shape, dt = _raster_batch(images, shape, dtype, "tiff_encode_batch", "raster")
+    n, rows, cols = shape
+    if dt != np.uint8 and dt != np.uint16:
+        raise TypeError(f"TIFF rasters take uint8 or uint16 samples, got {dt}")
+    if compression not in _TIFF_COMPRESSION:
+        raise ValueError(f"TIFF compression {compression!r}: 'lzw', 'deflate' or 'none'")
+    (predictor,) = _ints(predictor=predictor)
+    if predictor not in (1, 2):
+        raise ValueError(f"TIFF predictor {predictor}: 1 or 2")
+    if predictor == 2 and compression == "none":
+        raise ValueError("TIFF predictor 2 goes with 'lzw' or 'deflate', not with 'none'")
+    if rows_per_strip is None:
+        rps = 0
+    else:
+        (rps,) = _ints(rows_per_strip=rows_per_strip)
+        if rps < 1:
+            raise ValueError(f"TIFF rows_per_strip {rps}: None or a height from 1 up")
+        rps = min(rps, 65535)
+    (level,) = _ints(level=level)
+    if compression == "deflate":
+        if level == -1:
+            level = 6
+        if not 4 <= level <= 9:
+            raise ValueError(f"TIFF Deflate level {level}: -1 and 4 to 9 are on the device")
+    if n == 0:
+        return []
+    _check_tiff_shape(rows, cols)
+    bits, comp = 8 * dt.itemsize, _TIFF_COMPRESSION[compression]
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"raster batch shape {shape} of {dt}")
+    L = _ffi.lib()
+    out_stride = L.cct_tiff_bound(rows, cols, bits, comp, rps)
+    if out_stride == 0:
+        raise ValueError(f"TIFF raster of {rows} x {cols} samples: the file could pass 4 GiB")
+    out, sizes = _files_out(n, out_stride)
+    _ffi.check(L.cct_tiff_encode_batch(ptr, on_device, n, rows, cols, bits, comp, predictor, rps, level, out.ctypes.data, out_stride,
+                                       sizes.ctypes.data))
+    del keep
+    return _files_of(out, sizes)
+
+
+def tiff_info(file):
+    """(rows, cols, bits) of one TIFF file (`bytes`) from its first IFD, after every check of tiff_read_batch's parser; host
+    only.  ValueError for anything the reader refuses by structure (CCT_E_TIFF in include/compact_hip.h)."""
+    if not isinstance(file, (bytes, bytearray, memoryview)):
+        raise TypeError(f"a TIFF file is a bytes object, got {type(file).__name__}")
+    file = bytes(file)
+    rows, cols, bits = C.c_int(0), C.c_int(0), C.c_int(0)
+    _ffi.check(_ffi.lib().cct_tiff_info(file, len(file), C.byref(rows), C.byref(cols), C.byref(bits)))
+    return rows.value, cols.value, bits.value
+
+
+def tiff_read_batch(files, rows, cols, bits=16, out_dev=None, raise_errors=True):
+    """Grayscale TIFF files (a list of `bytes`) -> an (n, rows, cols) uint8 / uint16 array, decoded on the device.  Taken:
+    classic TIFF of either byte order, the first IFD, one sample per pixel of `bits` = 8 or 16, SampleFormat absent or 1,
+    Photometric 1, strips of any RowsPerStrip, StripOffsets / StripByteCounts as SHORT or LONG, compression 1, 5 (LZW) or
+    8 / 32946 (Deflate), predictor 1 or 2 (2 with 5 and 8 only), FillOrder absent or 1; unknown tags are ignored.  The rest
+    (BigTIFF, tiles, PackBits and other compressions, other photometrics, sample counts or depths, a strip outside the
+    file, a shape or depth other than the one asked for) is refused on the host as CCT_E_TIFF (15, ValueError) before
+    anything is uploaded.  A strip that does not decode to its rows gives CCT_E_STREAM (4) or, from the INFLATE kernel,
+    CCT_E_ZLIB (2).  LZW strips are read by libtiff's rules: decoding stops once the strip's bytes are out, a missing EOI is
+    no error, repeated Clears are allowed; a strip that does not open with a Clear is refused.  With out_dev it fills that
+    DeviceBuffer and returns the shape; with raise_errors=False it returns (array or shape, status) with the per-file codes,
+    and the raster of a refused file is unspecified.  Arguments are checked before any device call."""
+    rows, cols, bits = _ints(rows=rows, cols=cols, bits=bits)
+    if bits not in (8, 16):
+        raise ValueError(f"TIFF rasters of {bits} bits per sample: 8 or 16")
+    _check_tiff_shape(rows, cols)
+    files = _file_list(files, "tiff_read_batch", "file", "a TIFF file")
+    _check_out_dev(out_dev)
+    n, dt = len(files), np.dtype(np.uint8 if bits == 8 else np.uint16)
+    if n == 0:
+        return _no_rasters((0, rows, cols), dt, out_dev, raise_errors)
+    L = _ffi.lib()
+    blob, offs = _archive(files)
+    return _decode_rasters(lambda *to: L.cct_tiff_read_batch(blob, offs.ctypes.data, n, rows, cols, bits, *to), n, rows, cols, dt,
+                           out_dev, raise_errors, (_ffi.E_TIFF, _ffi.E_STREAM, _ffi.E_ZLIB))

@@ -908,6 +908,7 @@ int cct_shutdown(void)
 	dicom_rle_release();
 	jpegll_release();
 	j2k_release();
+	tiff_release();
 	if (g_gate) { (void)hipFree(g_gate); g_gate = nullptr; }
 	for (auto &kv : g_ctx.luts) {
 		ShapeTables &t = kv.second;
@@ -1797,6 +1798,19 @@ int cct::lease_decode_slot(DecLease &l)
 }
 
 void cct::set_last_kernel_ms(bool encode, float ms) { (encode ? tl_enc_kernel_ms : tl_dec_kernel_ms) = ms; }
+
+int cct::deflate_on_main(const uint8_t *d_in, size_t in_stride, const uint32_t *d_in_sizes, int n, size_t out_stride, int level,
+                         const uint8_t **d_out, const uint32_t **d_out_sizes)
+{
+	EncSlot &E = g_enc[0];
+	const uint8_t hdr13[13] = {0};
+	if (int rc = deflate_locked(E, d_in, in_stride, d_in_sizes, n, hdr13, out_stride, level, Z_DEFAULT_STRATEGY, 8)) return rc;
+	*d_out = (const uint8_t *)E.z_out.p;
+	*d_out_sizes = (const uint32_t *)E.z_outsizes.p;
+	return CCT_OK;
+}
+
+int cct::inflate_lanes_for_call() { return inflate_lanes_now(); }
 
 extern "C" {
 

@@ -270,6 +270,57 @@ struct RleDecodeArgs {
 };
 hipError_t launch_dicom_rle_decode(const RleDecodeArgs &a, hipStream_t st);
 
+// ---- TIFF strips: predictor, LZW, file layout (tiff_kernels.hip) ---------------------------------
+// LZW numbering (TIFF 6.0 section 13, as libtiff writes it): after a Clear the codes, Clear and EOI included, are counted from
+// 1; code j has 9 bits for j <= 254, 10 for j <= 766, 11 for j <= 1790 and 12 beyond, and code j >= 2 defines table entry
+// 256 + j.  An encoder writes its Clear as code 3837; a decoder follows a stream that does not up to code TIFF_LZW_MAX_J,
+// where libtiff's table (5119 entries) is full.
+constexpr uint32_t TIFF_LZW_SLOTS = 8192;   // encoder: dictionary slots in LDS (3836 entries at most: load below 47 %)
+constexpr uint32_t TIFF_LZW_TAB = 3904;     // decoder: codes whose (length, destination) are kept: entry 4095 is code 3839
+constexpr uint32_t TIFF_LZW_MAX_J = 4862;   // code 4862 defines entry 5118, the last of libtiff's table
+// bytes an LZW strip of L bytes takes at most: 12 bits a byte, a Clear per 3836 codes, the opening Clear, EOI, the fill,
+// rounded up to the words the encoder stores
+inline size_t tiff_lzw_bound(size_t L) { return ((L + L / 3836 + 4) * 3 / 2 + 8 + 3) & ~(size_t)3; }
+// Encode staging: raster i, rows [s * rps, ..) -> strip (i * spf + s) at strips + that * strip_stride as little-endian
+// samples, horizontal differences when predictor is 2; its byte count in strip_sizes
+hipError_t launch_tiff_stage(const void *d_images, int n, int rows, int cols, int bps, int predictor, int rps, int spf, uint8_t *d_strips,
+                             size_t strip_stride, uint32_t *d_strip_sizes, hipStream_t st);
+// one wave per strip: strip k of in_sizes[k] bytes -> LZW stream at out + k * out_stride (>= tiff_lzw_bound, a multiple of 4)
+hipError_t launch_tiff_lzw_encode(const uint8_t *d_strips, size_t strip_stride, const uint32_t *d_in_sizes, int nstrips, uint8_t *d_out,
+                                  size_t out_stride, uint32_t *d_out_sizes, hipStream_t st);
+struct TiffPackArgs {
+	const uint8_t *src; size_t src_stride; uint32_t src_skip;  // coded strip k = src + k * src_stride + src_skip ..
+	const uint32_t *src_sizes;                                 // .. of src_sizes[k] - src_skip bytes
+	uint32_t spf, rows, cols, bits, compression, predictor, rps;
+	uint32_t *strip_off;                                       // n * spf words: where each strip starts in its file
+	uint8_t *out; size_t out_stride; uint32_t *out_sizes;      // the files
+};
+// header, strips from offset 8, pad byte, IFD, StripByteCounts, StripOffsets: the layout of tests/tiff_model.py write_file
+hipError_t launch_tiff_pack(const TiffPackArgs &a, int n, hipStream_t st);
+// Read side.  The host has parsed every IFD (api_tiff.cpp); the device gets a list of strips whose [src, src + len) lies inside
+// the uploaded files and whose [dst, dst + want) lies inside the decoded-strip buffer, by the host's checks.
+struct TiffStrip {
+	uint64_t src;    // offset of the coded strip in the uploaded files
+	uint64_t dst;    // offset of its rows in the decoded-strip buffer
+	uint32_t len;    // coded bytes
+	uint32_t want;   // rows_in_strip * row_bytes
+	uint32_t file;   // file of the pass
+	uint32_t row0;   // its first row
+	uint32_t nrows;
+	uint32_t flags;  // TIFF_F_*
+};
+constexpr uint32_t TIFF_F_BIG_ENDIAN = 1u, TIFF_F_PREDICTOR = 2u, TIFF_F_FROM_FILE = 4u;  // FROM_FILE: uncompressed, the rows are at src
+// dst[offsets[k] ..] = files[src .. src + len) of strip k: Deflate strips back to back, as the INFLATE kernel takes them
+hipError_t launch_tiff_gather(const uint8_t *d_files, const TiffStrip *d_strips, uint32_t nstrips, const uint64_t *d_offsets, uint8_t *d_dst,
+                              hipStream_t st);
+// one wave per strip; status[k] = 1 for a strip that does not yield `want` bytes.  Nothing outside [dst, dst + want) is written.
+hipError_t launch_tiff_lzw_decode(const uint8_t *d_files, const TiffStrip *d_strips, uint32_t nstrips, uint8_t *d_decoded,
+                                  uint32_t *d_status, hipStream_t st);
+// rows of every strip (at dst of the decoded strips, or at src of the files) -> raster: byte swap for big-endian files,
+// inclusive sum along the row modulo 2^bits for predictor 2
+hipError_t launch_tiff_unpredict(const uint8_t *d_files, const uint8_t *d_decoded, const TiffStrip *d_strips, uint32_t nstrips, int rows,
+                                 int cols, int bps, void *d_images, hipStream_t st);
+
 // ---- JPEG Lossless, SOF3 (jpeg_lossless_kernels.hip) --------------------------------------------
 constexpr uint32_t JPL_HDR_MAX = 72;     // SOI 2, SOF3 13, DHT 4 + 1 + 16 + 17, DRI 6, SOS 10 = 69 bytes at most, rounded up
 constexpr uint32_t JPL_CHUNK = 1024;     // samples per step of the emit kernel: 4 per lane

@@ -1,5 +1,5 @@
 // Host-side declarations shared by the translation units of libcompact_hip.so (api.cpp: context, encode, decode;
-// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec; api_jpeg2000.cpp: JPEG 2000 codec),
+// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec; api_jpeg2000.cpp: JPEG 2000 codec; api_tiff.cpp: TIFF writer and reader),
 // and the scaffold every batch entry point is built from: StreamDrain, EventPair, Workspace, the decode slot lease, and the
 // copies of a pass (rasters_to_device, files_to_host, good_rasters_to_host).  Not part of the C ABI.
 #pragma once
@@ -142,6 +142,14 @@ void set_last_kernel_ms(bool encode, float ms);  // cct_last_timings [0] / [4] o
 void dicom_rle_release();        // cct_shutdown: workspaces and events of api_dicom_rle.cpp
 void jpegll_release();           // cct_shutdown: workspaces and events of api_jpeg_lossless.cpp
 void j2k_release();              // cct_shutdown: workspaces and events of api_jpeg2000.cpp
+void tiff_release();             // cct_shutdown: workspaces and events of api_tiff.cpp
+// The DEFLATE pass of encode slot 0 for a codec outside api.cpp.  The caller holds g_mu, counts as a call (ApiCall) and has
+// bound the device: n strings of d_in_sizes[i] bytes at d_in + i * in_stride (deflate_in_stride of the longest, the padding
+// zero) -> zlib streams of `level` (4 .. 9), default strategy, memLevel 8, on the main stream.  Stream i starts 13 bytes
+// into *d_out + i * out_stride (deflate_out_stride); (*d_out_sizes)[i] counts those 13 bytes too.  Both belong to the slot.
+int deflate_on_main(const uint8_t *d_in, size_t in_stride, const uint32_t *d_in_sizes, int n, size_t out_stride, int level,
+                    const uint8_t **d_out, const uint32_t **d_out_sizes);
+int inflate_lanes_for_call();    // launch_inflate's `lanes` as cct_zlib_decompress_batch picks them (option "inflate_lanes")
 
 // h_offsets[0 .. n] of an archive must not decrease; `noun` is what the caller's message calls an entry ("frame", "file")
 inline int check_offsets(const uint64_t *h_offsets, int n, const char *noun)

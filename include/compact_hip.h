@@ -65,6 +65,7 @@ extern "C" {
 #define CCT_E_CRC 12      /* cct_png_read_batch: a chunk's CRC-32 does not match           -> ValueError */
 #define CCT_E_JPEG 13     /* cct_jpegll_decode_batch / cct_jpegll_info: not a JPEG this reader takes -> ValueError */
 #define CCT_E_J2K 14      /* cct_j2k_info / cct_j2k_decode_batch: not a JPEG 2000 codestream or JP2 file they read -> ValueError */
+#define CCT_E_TIFF 15     /* cct_tiff_info / cct_tiff_read_batch: not a TIFF file they read -> ValueError */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
 #define CCT_FLAG_FRACTAL 1u       /* transforms.fractal      (core.py:234) */
@@ -458,6 +459,64 @@ int cct_j2k_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *p
  * cct_last_timings: [4] the decode kernels, HIP events, summed over the passes. */
 int cct_j2k_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits /* 8 or 16 */, int shift,
                          void *images, int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
+
+/* ---- strip-organised grayscale TIFF (TIFF 6.0; LZW, Deflate, horizontal predictor) ------------------------------------
+ * tests/tiff_model.py states the layout, the LZW coder and decoder, the parser and its refusals; Pillow / libtiff is the oracle.
+ *
+ * cct_tiff_bound: bytes a file of cct_tiff_encode_batch takes at most (0: an argument it refuses, or a file that could pass
+ * 4 GiB).  compression is the TIFF code: 1 none, 5 LZW, 8 Deflate.  rows_per_strip 0: strips of at most 64 KiB, one row at
+ * least (Pillow's rule); else the height, clamped to rows. */
+size_t cct_tiff_bound(int rows, int cols, int bits /* 8 or 16 */, int compression, int rows_per_strip);
+
+/* cct_tiff_encode_batch: n rasters of rows x cols samples (uint8 / uint16, C order, host or device) -> little-endian TIFF
+ * files, file i at h_out + i * out_stride (out_stride >= cct_tiff_bound), its size in h_out_sizes[i].  Layout, as libtiff
+ * writes it: header, the strips back to back from offset 8, a zero byte if they end on an odd offset, the IFD (tags 256,
+ * 257, 258, 259, 262, 273, 278, 279, 284, and 317 for predictor 2; no SamplesPerPixel), then StripByteCounts and
+ * StripOffsets (inline for one strip; the byte counts of several strips are SHORT when a full strip has fewer than 6553
+ * bytes -- 65536 uncompressed --, else LONG).  Strips hold little-endian samples, horizontal differences modulo 2^bits for
+ * predictor 2 (the first sample of a row as it is).  LZW strips are libtiff's: greedy parse, codes MSB first, a Clear when the
+ * next free entry is 4094, and its compression-ratio Clear; Deflate strips are zlib streams of `level` (4 .. 9, -1 = 6),
+ * default strategy, memLevel 8, from the device DEFLATE pass.  With LZW, and with Deflate at level 6, the file is byte for
+ * byte Pillow 12 / libtiff 4.7's.  Encode slot 0 (one call at a time).
+ * CCT_E_ARG, before the device is touched: bits other than 8 or 16, rows or cols outside 1 .. 65535, n < 0, a compression
+ * other than 1, 5, 8, a predictor other than 1, 2, predictor 2 with compression 1, rows_per_strip < 0, a level outside
+ * -1, 4 .. 9 with compression 8 (ignored otherwise), a file that could pass 4 GiB; CCT_E_CAP for out_stride below the bound.
+ * cct_last_timings: [0] the kernels of the call (staging, LZW or DEFLATE, layout), HIP events, summed over the passes. */
+int cct_tiff_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int bits, int compression, int predictor,
+                          int rows_per_strip, int level, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes);
+
+/* cct_tiff_info: (rows, cols, bits) of a file from its first IFD, after every structural check of cct_tiff_read_batch; host
+ * only; CCT_E_TIFF for what the reader refuses, CCT_E_ARG for a null argument. */
+int cct_tiff_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *bits);
+
+/* cct_tiff_read_batch: n files laid out back to back (file i = h_files[h_offsets[i] .. h_offsets[i+1])) -> n rasters of
+ * rows x cols samples of `bits` in `images` (host or device, images_cap_px samples), decoded on the device; h_status[i] is
+ * CCT_OK or the file's code, and the call returns the first code that is not CCT_OK.  A decode slot (two calls at a time).
+ * Taken: classic TIFF of either byte order, the first IFD, BitsPerSample 8 or 16 with one sample per pixel, SampleFormat
+ * absent or 1, Photometric 1, PlanarConfiguration absent or 1, FillOrder absent or 1, strips of any RowsPerStrip (absent:
+ * one strip) with a shorter last strip, StripOffsets and StripByteCounts as SHORT or LONG in any order in the file,
+ * Compression 1, 5, 8 or 32946, Predictor absent, 1, or 2 with compression 5 and 8; dimensions as SHORT or LONG; tags this
+ * list does not name are ignored.
+ * CCT_E_TIFF, decided on the host before anything is uploaded (scope, not damage): no II / MM header, BigTIFF, an IFD or an
+ * entry's values outside the file, tiles, any other compression, photometric, sample count, depth, sample format, fill
+ * order or planar configuration, predictor 2 on uncompressed strips or a predictor above 2, a missing ImageWidth,
+ * ImageLength, BitsPerSample, Photometric, StripOffsets or StripByteCounts, strip tables that do not hold
+ * ceil(rows / RowsPerStrip) entries, a strip outside the file, rows, cols or bits other than the ones asked for.
+ * A strip that does not yield its rows_in_strip * row_bytes bytes: CCT_E_STREAM for an LZW strip (found on the device), an
+ * uncompressed strip with fewer bytes, a coded strip of none (both found on the host), and a Deflate strip that inflates to
+ * another size; CCT_E_ZLIB for a Deflate strip the INFLATE kernel refuses (a strip is one whole zlib stream).
+ * LZW strips are read by libtiff's rules: decoding stops once the strip's bytes are out and what follows is ignored, a last
+ * string longer than what is left is cut, a missing EOI is no error, repeated Clears are allowed, a code equal to the next
+ * free entry is the KwKwK case; errors are data or an EOI that ends the strip early, a first code after a Clear that is
+ * not a literal, a code beyond the next free entry, more than 4862 codes without a Clear (libtiff's table is full), and --
+ * stricter than libtiff -- a strip that does not open with a Clear.  A damaged strip never makes the decoder read outside
+ * the strip's bytes or write outside its rows.  Refused files leave the others decoded; nothing is written outside a
+ * refused file's own rows * cols slot, and nothing at all for a file refused on the host.
+ * Whole-call errors, before the device is touched: CCT_E_ARG for rows or cols outside 1 .. 65535, n < 0, bits other than 8
+ * or 16, offsets that decrease; CCT_E_CAP for images_cap_px below n * rows * cols.
+ * cct_last_timings: [4] the kernels of the call (LZW decode, gather + INFLATE, predictor), HIP events, summed over the passes. */
+int cct_tiff_read_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits /* 8 or 16 */,
+                        void *images, int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
 
 /* ---- tuning / introspection (bench.py) --------------------------------------------- */
 /* Stage times of the CALLING THREAD's most recent cct_encode_batch / cct_decode_batch, milliseconds (kept per

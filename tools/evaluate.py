@@ -2,7 +2,7 @@
 """Corpus size comparison: the counterpart of the reference's scripts/evaluate.py:52-136 without pydicom.
 
     python tools/evaluate.py DIRECTORY [--results FILE.csv] [--batch 256] [--zip host|device] [--png host|device]
-                             [--png-input host|device] [--rle device] [--jpl device] [--jp2 device|device-native]
+                             [--png-input host|device] [--rle device] [--jpl device] [--jp2 device|device-native] [--tif lzw|deflate]
 
 Every slice under DIRECTORY (.npy, .u16/.raw, .u16.zz, 16-bit .png) gets one CSV row `File,Raw,ZIP,PNG,RLE,JP2,CCT` as
 in results/encoder-comparisons.csv: Raw = bytes of the pixel array, ZIP = zlib.compress at the default level
@@ -46,6 +46,7 @@ from _inputs import list_inputs, load_slice  # noqa: E402
 
 FILE, RAW, ZIP, PNG, RLE, JP2, CCT = "File", "Raw", "ZIP", "PNG", "RLE", "JP2", "CCT"  # evaluate.py:29-35
 JPL = "JPL"  # --jpl device only
+TIF = "TIF"  # --tif lzw|deflate only: the last column
 
 
 def png_size(image):
@@ -105,6 +106,9 @@ def main(argv=None):
     ap.add_argument("--jp2", choices=("na", "device", "device-native"), default="na",
                     help="the JP2 column: NA, the lossless .jp2 file of value << 4 at precision 16 from cct_hip.jpeg2000_encode_batch (device: the "
                          "reference's measure), or the same of the slice itself (device-native)")
+    ap.add_argument("--tif", choices=("na", "lzw", "deflate"), default="na",
+                    help="lzw / deflate: append a TIF column behind the others, the length of the slice's TIFF file from "
+                         "cct_hip.tiff_encode_batch at predictor 2 (what Pillow writes with that compression and tiffinfo={317: 2})")
     args = ap.parse_args(argv)
     import cct_hip
     with open(os.path.join(ROOT, "2023-compact-image-compression_amd", "config.json")) as f:
@@ -158,10 +162,15 @@ def main(argv=None):
                                                           precision=16, shift=4 if args.jp2 == "device" else 0, jp2=True)
                     for (name, _), f in zip(chunk, files):
                         rows[name][JP2] = len(f)
+                if args.tif != "na":
+                    stack = np.stack([img for _, img in chunk])
+                    files = cct_hip.tiff_encode_batch(stack.view(np.uint16) if stack.dtype.itemsize == 2 else stack, args.tif, 2)
+                    for (name, _), f in zip(chunk, files):
+                        rows[name][TIF] = len(f)
         for name, fut in futures.items():
             rows[name].update({k: v for k, v in fut.result().items() if k not in rows[name]})
     outputs = sorted(rows.values(), key=lambda r: r[FILE])  # evaluate.py:130
-    cols = [FILE, RAW, ZIP, PNG, RLE, JP2, CCT] + ([JPL] if args.jpl == "device" else [])
+    cols = [FILE, RAW, ZIP, PNG, RLE, JP2, CCT] + ([JPL] if args.jpl == "device" else []) + ([TIF] if args.tif != "na" else [])
     os.makedirs(os.path.dirname(os.path.abspath(args.results)), exist_ok=True)
     with open(args.results, "w") as fout:  # evaluate.py:133-136
         fout.write(",".join(cols))
