@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CCT_HIP_LIB") or os.path.join(_HERE, "libcompact_hip.so")  # CCT_HIP_LIB: tuning builds (tools/ab_build.sh)
 
 # error codes (include/compact_hip.h)
-OK, E_MAGIC, E_ZLIB, E_OVERFLOW, E_STREAM, E_SHAPE, E_CAP, E_NOMEM, E_DEVICE, E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K, E_TIFF = range(16)
+OK, E_MAGIC, E_ZLIB, E_OVERFLOW, E_STREAM, E_SHAPE, E_CAP, E_NOMEM, E_DEVICE, E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K, E_TIFF, E_JPEGLS = range(17)
 FLAG_FRACTAL, FLAG_SEGMENTATION, FLAG_DEFLATE, FLAG_SIGNED_SEG = 1, 2, 4, 8
 FLAG_LEVEL_MASK = 0xF00
 
@@ -131,6 +131,12 @@ _SIGS = {
     "cct_jpegll_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cct_jpegll_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                           C.c_size_t, C.c_void_p]),
+    "cct_jpegls_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "cct_jpegls_encode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_void_p]),
+    "cct_jpegls_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cct_jpegls_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_size_t, C.c_void_p]),
     "cct_last_timings": (C.c_int, [C.POINTER(C.c_float)]),
     "cct_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "cct_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
@@ -188,7 +194,7 @@ def raise_for(rc):
         raise MemoryError(msg)
     if rc == E_DEVICE:
         raise DeviceError(msg)
-    if rc in (E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K, E_TIFF):
+    if rc in (E_ARG, E_MIXED, E_PNG, E_CRC, E_JPEG, E_J2K, E_TIFF, E_JPEGLS):
         raise ValueError(msg)
     raise RuntimeError(f"libcompact_hip error {rc}: {msg}")
 

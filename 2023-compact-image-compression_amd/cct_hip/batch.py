@@ -788,11 +788,11 @@ def dicom_fragments(pixel_data):
 _JPL_MAX_PIXELS = 1 << 26
 
 
-def _check_jpl_shape(rows, cols):
+def _check_jpl_shape(rows, cols, what="JPEG Lossless"):
     if not 1 <= rows <= 65535 or not 1 <= cols <= 65535:
-        raise ValueError(f"JPEG Lossless frame of {rows} x {cols} samples: rows and cols are 1 to 65535")
+        raise ValueError(f"{what} frame of {rows} x {cols} samples: rows and cols are 1 to 65535")
     if rows * cols > _JPL_MAX_PIXELS:
-        raise ValueError(f"JPEG Lossless frame of {rows} x {cols} samples: more than {_JPL_MAX_PIXELS} pixels")
+        raise ValueError(f"{what} frame of {rows} x {cols} samples: more than {_JPL_MAX_PIXELS} pixels")
 
 
 def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=None, dtype=None):
@@ -867,6 +867,82 @@ def jpeg_lossless_decode_batch(files, rows, cols, bits=16, out_dev=None, raise_e
     blob, offs = _archive(files)
     return _decode_rasters(lambda *to: L.cct_jpegll_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, *to), n, rows,
                            cols, dt, out_dev, raise_errors, (_ffi.E_JPEG, _ffi.E_MIXED, _ffi.E_STREAM))
+
+
+# ---- JPEG-LS lossless (T.87; DICOM 1.2.840.10008.1.2.4.80): files on the device ------------------------------------------
+
+def jpeg_ls_encode_batch(images, precision=None, restart_rows=0, shape=None, dtype=None):
+    """JPEG-LS lossless files (ITU-T T.87 with NEAR = 0, DICOM transfer syntax 1.2.840.10008.1.2.4.80) on the device: a
+    uint16 or uint8 array of shape (n, rows, cols) or (rows, cols), or a DeviceBuffer with shape= given (dtype= np.uint16
+    unless np.uint8 is named), -> a list of n `bytes`, each one file: SOI, SOF55, DRI (with restart_rows > 0: a restart
+    interval of that many lines, at most 65535), SOS, the scan, EOI.  precision is 2 .. 16 and defaults to the sample width;
+    uint8 samples take at most 8.  The preset parameters are the defaults of the precision and no LSE segment is written;
+    tests/jpeg_ls_model.py states the file.  A sample >= 2^precision raises OverflowError.  dicom_encapsulate wraps the
+    files as PixelData.  Arguments are checked (TypeError / ValueError) before any device call.
+    A file without restart intervals is coded by one wave, one after the other of its lines: restart_rows trades a few
+    bytes an interval for that many waves a frame.
+    Memory: the call reserves cct_jpegls_bound(rows, cols, restart_rows) bytes per frame on the host, the worst case of 64
+    bits a sample and 7 bits a byte, about 9.2 bytes a sample (2.4 MB for 512 x 512, 613 MB for 256 such frames; pages a
+    file does not reach are never touched), and on the device twice that, at most 512 MB at a time: split a large batch
+    if the address space matters."""
+    src, shape, dt = _raster_batch(images, shape, dtype, "jpeg_ls_encode_batch", "frame")
+    n, rows, cols = shape
+    if dt != np.uint8 and dt != np.uint16:
+        raise TypeError(f"JPEG-LS frames take uint8 or uint16 samples, got {dt}")
+    src_bits = 8 * dt.itemsize
+    precision, restart_rows = _ints(precision=src_bits if precision is None else precision, restart_rows=restart_rows)
+    if not 2 <= precision <= 16:
+        raise ValueError(f"JPEG-LS precision {precision}: 2 to 16")
+    if precision > src_bits:
+        raise ValueError(f"precision {precision} for {dt} samples: at most {src_bits}")
+    if not 0 <= restart_rows <= 65535:
+        raise ValueError(f"restart_rows {restart_rows}: 0 (no restart intervals) or a number of lines up to 65535")
+    if n == 0:
+        return []
+    _check_jpl_shape(rows, cols, "JPEG-LS")
+    ptr, on_device, keep = _raster_ptr(src, shape, dt, f"frame batch shape {shape} of {dt}")
+    L = _ffi.lib()
+    out_stride = L.cct_jpegls_bound(rows, cols, restart_rows)
+    out, sizes = _files_out(n, out_stride)
+    status = np.zeros(n, dtype=np.uint32)
+    _ffi.check(L.cct_jpegls_encode_batch(ptr, on_device, n, rows, cols, src_bits, precision, restart_rows, out.ctypes.data,
+                                         out_stride, sizes.ctypes.data, status.ctypes.data))
+    del keep
+    return _files_of(out, sizes)
+
+
+def jpeg_ls_info(file):
+    """(rows, cols, precision) of one JPEG-LS file (`bytes`), from its SOF55 after the whole marker walk; host only.
+    ValueError for anything jpeg_ls_decode_batch refuses by structure (CCT_E_JPEGLS in include/compact_hip.h)."""
+    if not isinstance(file, (bytes, bytearray, memoryview)):
+        raise TypeError(f"a JPEG-LS file is a bytes object, got {type(file).__name__}")
+    file = bytes(file)
+    rows, cols, prec = C.c_int(0), C.c_int(0), C.c_int(0)
+    _ffi.check(_ffi.lib().cct_jpegls_info(file, len(file), C.byref(rows), C.byref(cols), C.byref(prec)))
+    return rows.value, cols.value, prec.value
+
+
+def jpeg_ls_decode_batch(files, rows, cols, bits=16, out_dev=None, raise_errors=True):
+    """JPEG-LS lossless files (a list of `bytes`: SOF55, one component, NEAR = 0, precision <= `bits` = 8 or 16 allocated)
+    -> an (n, rows, cols) uint8 / uint16 array, decoded on the device: restart intervals of whole lines, the default preset
+    parameters or those of an LSE segment of id 1.  With out_dev it fills that DeviceBuffer and returns the shape, like
+    decode_batch.  With raise_errors=False it returns (array or shape, status) with status[i] 0, CCT_E_JPEGLS (16: the
+    structure), CCT_E_MIXED (10: not rows x cols, or a precision above bits) or CCT_E_STREAM (4: the scan data);
+    include/compact_hip.h lists the cases.  The raster of a refused file is unspecified.  Arguments are checked before any
+    device call."""
+    rows, cols, bits = _ints(rows=rows, cols=cols, bits=bits)
+    if bits not in (8, 16):
+        raise ValueError(f"JPEG-LS rasters of {bits} bits allocated: 8 or 16")
+    _check_jpl_shape(rows, cols, "JPEG-LS")
+    files = _file_list(files, "jpeg_ls_decode_batch", "file", "a JPEG-LS file")
+    _check_out_dev(out_dev)
+    n, dt = len(files), np.dtype(np.uint8 if bits == 8 else np.uint16)
+    if n == 0:
+        return _no_rasters((0, rows, cols), dt, out_dev, raise_errors)
+    L = _ffi.lib()
+    blob, offs = _archive(files)
+    return _decode_rasters(lambda *to: L.cct_jpegls_decode_batch(blob, offs.ctypes.data, n, rows, cols, bits, *to), n, rows,
+                           cols, dt, out_dev, raise_errors, (_ffi.E_JPEGLS, _ffi.E_MIXED, _ffi.E_STREAM))
 
 
 # ---- JPEG 2000 Part-1 lossless (T.800; DICOM 1.2.840.10008.1.2.4.90): files on the device --------------------------------

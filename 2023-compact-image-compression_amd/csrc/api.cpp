@@ -907,6 +907,7 @@ int cct_shutdown(void)
 	comm_release();
 	dicom_rle_release();
 	jpegll_release();
+	jpegls_release();
 	j2k_release();
 	tiff_release();
 	if (g_gate) { (void)hipFree(g_gate); g_gate = nullptr; }

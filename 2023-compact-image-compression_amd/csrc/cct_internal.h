@@ -378,6 +378,51 @@ struct JplDecArgs {
 };
 hipError_t launch_jpl_decode(const JplDecArgs &a, hipStream_t st);
 
+// ---- JPEG-LS lossless, SOF55 (jpeg_ls_kernels.hip) ---------------------------------------------------
+constexpr uint32_t JLS_HDR_MAX = 32;      // SOI 2, SOF55 13, DRI 6, SOS 10 = 31 bytes at most, rounded up
+constexpr uint32_t JLS_LIMIT_MAX = 64;    // LIMIT = 2 * (bpp + max(8, bpp)) at bpp = 16: the longest code
+constexpr uint32_t JLS_STEP_WORDS = 260;  // LDS words of the encoder's bit buffer: a carry below a byte and 64 lanes of up to 128 bits, 257 words, and the two a put may touch behind
+constexpr uint32_t JLS_DEC_LANES = 8;     // intervals per workgroup of the decoder: a context table of 367 * 12 bytes each in LDS
+constexpr uint32_t JLS_ST_OVERFLOW = 1u;  // encode: a sample >= 2^precision
+constexpr uint32_t JLS_ST_BOUND = 2u;     // encode: an interval or a file would leave its bound (a defect of the bound, never seen)
+constexpr uint32_t JLS_ST_STREAM = 1u;    // decode: data that ends early or is left over, a run past the line end, a value outside the range
+// The bytes of a restart interval of `lines` lines, at most.  A sample in regular mode costs LIMIT bits at most.  A run of L
+// samples and its interruption sample cost at most L ones, a zero, J bits and LIMIT - J - 1 bits: LIMIT + L for L + 1 samples.
+// A run to the end of a line costs L + 1 bits for L samples.  LIMIT >= 20 > 2, so LIMIT bits a sample cover every case and one
+// bit a line is spare.  Behind a 0xFF a byte carries 7 bits: ceil(bits / 7) bytes, and one 0x00 if the last byte is 0xFF.
+inline size_t jls_interval_bound(size_t lines, size_t cols) { return (JLS_LIMIT_MAX * lines * cols + lines + 6) / 7 + 2; }
+struct JlsParams {  // T.87 C.2.4.1.1: the defaults of a precision (api_jpeg_ls.cpp jls_params), or what an LSE segment of id 1 states
+	uint32_t maxval, range, qbpp, limit, a0, reset;
+	int32_t t1, t2, t3;
+};
+// Encode.  Interval k of a frame holds lines [k * rpi, min(rows, (k + 1) * rpi)); n_int = ceil(rows / rpi).  Its stuffed bytes go
+// to stage + (frame * n_int + k) * istride, istride >= jls_interval_bound(rpi, cols); every store there is checked against
+// istride, and the layout kernel checks the sum against out_stride.
+struct JlsEncArgs {
+	const void *images;        // n * rows * cols samples of src_bits (8 or 16)
+	uint32_t src_bits, n, rows, cols, precision, rpi, n_int, restart;  // restart: Ri of the DRI segment, in lines; 0: none is written
+	JlsParams par;
+	uint32_t *status;          // n, zero on entry: JLS_ST_OVERFLOW, JLS_ST_BOUND
+	uint8_t *stage; size_t istride;
+	uint32_t *ibytes;          // n * n_int: bytes of an interval
+	uint32_t *ioff;            // n * n_int: offset in the file of the interval's first byte
+	uint8_t *out; size_t out_stride; uint32_t *out_sizes;  // a frame with a status gets size 0
+};
+hipError_t launch_jls_encode(const JlsEncArgs &a, hipStream_t st);
+// Decode.  The host has walked the headers and found the markers of the scan (api_jpeg_ls.cpp): the device gets every interval
+// as a byte range [src, src + len) of the upload that holds no marker, and the lines it fills.
+struct JlsFrame { uint32_t slot; JlsParams par; };  // slot: the raster this frame fills, images + slot * rows * cols
+struct JlsInterval { uint64_t src; uint32_t len, frame, row0, nrows; };
+struct JlsDecArgs {
+	const uint8_t *files;      // the upload
+	const JlsFrame *frames; uint32_t nframes;
+	const JlsInterval *intervals; uint32_t total_int;
+	uint32_t rows, cols, out_bits;  // out_bits 8 or 16: the sample type of images
+	uint32_t *status;          // nframes, zero on entry: JLS_ST_STREAM
+	void *images;
+};
+hipError_t launch_jls_decode(const JlsDecArgs &a, hipStream_t st);
+
 // ---- JPEG 2000 Part-1: what the layouts of the encoder and the decoder share -----------------------
 // The coefficients of all subbands share one rows x cols int32 plane in the Mallat arrangement (after a stage the LL band is
 // the top left corner), every code-block is a rectangle of it, the subbands are listed in packet order.  Device side: jpeg2000_device.h.

@@ -1,5 +1,5 @@
 // Host-side declarations shared by the translation units of libcompact_hip.so (api.cpp: context, encode, decode;
-// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec; api_jpeg2000.cpp: JPEG 2000 codec; api_tiff.cpp: TIFF writer and reader),
+// api_comm.cpp: RCCL all-gather; api_packbits.cpp: PackBits utility; api_dicom_rle.cpp: DICOM RLE codec; api_jpeg_lossless.cpp: JPEG Lossless codec; api_jpeg_ls.cpp: JPEG-LS codec; api_jpeg2000.cpp: JPEG 2000 codec; api_tiff.cpp: TIFF writer and reader),
 // and the scaffold every batch entry point is built from: StreamDrain, EventPair, Workspace, the decode slot lease, and the
 // copies of a pass (rasters_to_device, files_to_host, good_rasters_to_host).  Not part of the C ABI.
 #pragma once
@@ -141,6 +141,7 @@ int lease_decode_slot(DecLease &l);
 void set_last_kernel_ms(bool encode, float ms);  // cct_last_timings [0] / [4] of the calling thread
 void dicom_rle_release();        // cct_shutdown: workspaces and events of api_dicom_rle.cpp
 void jpegll_release();           // cct_shutdown: workspaces and events of api_jpeg_lossless.cpp
+void jpegls_release();           // cct_shutdown: workspaces and events of api_jpeg_ls.cpp
 void j2k_release();              // cct_shutdown: workspaces and events of api_jpeg2000.cpp
 void tiff_release();             // cct_shutdown: workspaces and events of api_tiff.cpp
 // The DEFLATE pass of encode slot 0 for a codec outside api.cpp.  The caller holds g_mu, counts as a call (ApiCall) and has

@@ -66,6 +66,7 @@ extern "C" {
 #define CCT_E_JPEG 13     /* cct_jpegll_decode_batch / cct_jpegll_info: not a JPEG this reader takes -> ValueError */
 #define CCT_E_J2K 14      /* cct_j2k_info / cct_j2k_decode_batch: not a JPEG 2000 codestream or JP2 file they read -> ValueError */
 #define CCT_E_TIFF 15     /* cct_tiff_info / cct_tiff_read_batch: not a TIFF file they read -> ValueError */
+#define CCT_E_JPEGLS 16   /* cct_jpegls_decode_batch / cct_jpegls_info: not a JPEG-LS file this reader takes -> ValueError */
 
 /* encoder flags: config['encoder']['transforms'] + deflate_compression (core.py:207-209) */
 #define CCT_FLAG_FRACTAL 1u       /* transforms.fractal      (core.py:234) */
@@ -399,6 +400,45 @@ int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int
                             uint32_t *h_status /* CCT_E_* per frame */);
 int cct_jpegll_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
 int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits, void *images,
+                            int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
+
+/* ---- JPEG-LS lossless (SOF55) --------------------------------------------------------- */
+/* JPEG-LS lossless (ITU-T T.87 with NEAR = 0, DICOM transfer syntax 1.2.840.10008.1.2.4.80) for one sample per pixel;
+ * tests/jpeg_ls_model.py states the format and both directions in Python.
+ * cct_jpegls_encode_batch: n rasters of shape (rows, cols), C order, uint16 (src_bits 16) or uint8 (src_bits 8), on the
+ * host (images_on_device 0) or the device (1); precision P is 2 .. src_bits.  Frame i lands at h_out + i*out_stride, its
+ * size in h_out_sizes[i]: SOI, SOF55, DRI (only with restart_rows > 0: Ri = restart_rows, counted in lines), SOS (NEAR 0,
+ * ILV 0), the scan, EOI; no LSE segment (the default preset parameters of MAXVAL = 2^P - 1), no APPn.  Every restart
+ * interval starts from the initial state with the line above it counted as zeros, and is led by RSTm, m = 0 .. 7 in turn.
+ * A frame with a sample >= 2^P gets CCT_E_OVERFLOW in h_status[i] and size 0; the other frames are written and the call
+ * returns the first non-OK status.  The call takes the encode slot, like the RLE codec.
+ * cct_jpegls_bound(rows, cols, restart_rows): a sample costs at most LIMIT = 64 bits, runs included, and a line one bit
+ * more; behind a 0xFF a byte carries 7 bits, so an interval of l lines takes at most ceil((64 l cols + l) / 7) + 2
+ * bytes and 2 for its RST; headers and EOI stay below 34: 34 + intervals * (that + 2).  0 for a refused shape; out_stride
+ * below it is CCT_E_CAP.  That is about 9.2 bytes a sample (2.4 MB for 512 x 512): size h_out for it, the files themselves
+ * are a fraction of it and each is copied out at its own length.
+ * cct_jpegls_info: (rows, cols, precision) of one file from its SOF55, after the whole marker walk; host only.
+ * cct_jpegls_decode_batch: n files laid out back to back -> n*rows*cols uint16 (bits 16) or uint8 (bits 8) at `images`
+ * (host or device), images_cap_px counted in pixels; a decode slot.  The host walks the markers and takes: any APPn / COM
+ * segment; SOF55 with Nf = 1, P 2 .. 16 (<= bits), Y = rows, X = cols (anything else: CCT_E_MIXED); DRI of length 4, 5 or
+ * 6, Ri in lines; an LSE segment of id 1 whose MAXVAL (<= 2^P - 1), T1 <= T2 <= T3 <= MAXVAL and RESET (3 ..
+ * max(255, MAXVAL)) replace the defaults, 0 standing for the default; one SOS with Ns = 1, no mapping table, NEAR = 0,
+ * ILV = 0, no point transform; bytes behind EOI.  CCT_E_JPEGLS, decided before upload: no SOI, SOF55, SOS or EOI, another SOF
+ * type, Nf != 1, Y = 0, DNL, NEAR != 0, an interleave mode, a mapping table, a point transform, an LSE segment of id 2 .. 4
+ * or with illegal values, a bad segment length, a marker other than RSTm or EOI inside the scan (0xFF and a byte >= 0x80).
+ * CCT_E_STREAM: a wrong number or sequence of RST markers (the host sees that while it looks for them), and on the device
+ * scan data that ends early or leaves whole bytes over, a run that passes the end of its line, a Golomb code longer than
+ * LIMIT or with a value above 2^qbpp.  Refused files leave the others decoded, nothing is written outside a refused file's
+ * own rows*cols slot, and the call returns the first non-OK status.
+ * Whole-call errors, before the device is touched: CCT_E_ARG for rows or cols outside 1 .. 65535, rows*cols above 2^26,
+ * n < 0, bits or src_bits other than 8 or 16, a precision outside 2 .. src_bits, restart_rows outside 0 .. 65535; CCT_E_CAP
+ * as above.  cct_last_timings: [0] the three encode kernels, [4] the decode kernel, HIP events, summed over the passes. */
+size_t cct_jpegls_bound(int rows, int cols, int restart_rows);
+int cct_jpegls_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int src_bits /* 8 or 16 */,
+                            int precision, int restart_rows, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes,
+                            uint32_t *h_status /* CCT_E_* per frame */);
+int cct_jpegls_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
+int cct_jpegls_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits, void *images,
                             int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);
 
 /* ---- JPEG 2000 Part-1 lossless codec (T.800; DICOM transfer syntax 1.2.840.10008.1.2.4.90) ----

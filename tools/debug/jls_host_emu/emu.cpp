@@ -1,0 +1,77 @@
+// The JPEG-LS kernels (csrc/jpeg_ls_kernels.hip) on the host, for checks that need no GPU: the shim of ../rle_host_emu stands
+// in for the HIP runtime (a std::thread per GPU thread, the blocks of a launch one after another), so the kernel source
+// compiles unchanged with g++ and runs under AddressSanitizer / UBSan.  drive.py feeds it rasters and files of
+// tests/jpeg_ls_model.py and compares.
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -I../rle_host_emu -x c++ emu.cpp -o emu -lpthread && python drive.py
+// Slow (a thread per lane): small shapes.  It checks the algorithm and the bounds, not the timing.
+#include "emu_common.h"
+static inline uint32_t atomicMin(uint32_t *p, uint32_t v)
+{
+	uint32_t o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
+	while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
+	return o;
+}
+static inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
+#include "../../../2023-compact-image-compression_amd/csrc/jpeg_ls_kernels.hip"
+using namespace cct;
+// params: 9 uint32 (maxval range qbpp limit a0 reset t1 t2 t3), as tests/jpeg_ls_model.py Params has them
+static JlsParams params_of(const uint32_t *w)
+{
+	JlsParams p{};
+	p.maxval = w[0]; p.range = w[1]; p.qbpp = w[2]; p.limit = w[3]; p.a0 = w[4]; p.reset = w[5];
+	p.t1 = (int32_t)w[6]; p.t2 = (int32_t)w[7]; p.t3 = (int32_t)w[8];
+	return p;
+}
+// encode: e src_bits precision rows cols n restart_rows params.bin in.bin out.bin
+// decode: d rows cols out_bits nslots job.bin files.bin out.bin
+//         job.bin: uint32 nframes, per frame 10 uint32 (slot, params); then per interval 5 uint32 (src, len, frame, row0, nrows)
+int main(int argc, char **argv)
+{
+	if (argv[1][0] == 'e') {
+		JlsEncArgs a{};
+		a.src_bits = atoi(argv[2]); a.precision = atoi(argv[3]); a.rows = atoi(argv[4]); a.cols = atoi(argv[5]); a.n = atoi(argv[6]);
+		const uint32_t rr = atoi(argv[7]);
+		a.rpi = rr && rr < a.rows ? rr : a.rows; a.n_int = (a.rows + a.rpi - 1) / a.rpi; a.restart = rr;
+		auto par = rd(argv[8]);
+		a.par = params_of((const uint32_t *)par.data());
+		auto in = rd(argv[9]);
+		const size_t ib = jls_interval_bound(a.rpi, a.cols), istride = (ib + 3) & ~(size_t)3;
+		const size_t bound = JLS_HDR_MAX + 2 + a.n_int * (ib + 2), stride = (bound + 3) & ~(size_t)3;
+		std::vector<uint32_t> status(a.n), ints((size_t)a.n * a.n_int * 2), sizes(a.n);
+		std::vector<uint8_t> stage((size_t)a.n * a.n_int * istride + GUARD, 0xEE), out(a.n * stride + GUARD, 0xEE);
+		a.images = in.data(); a.status = status.data(); a.stage = stage.data(); a.istride = istride;
+		a.ibytes = ints.data(); a.ioff = a.ibytes + (size_t)a.n * a.n_int;
+		a.out = out.data(); a.out_stride = stride; a.out_sizes = sizes.data();
+		launch_jls_encode(a, nullptr);
+		std::ofstream f(argv[10], std::ios::binary);
+		for (uint32_t i = 0; i < a.n; i++) {
+			uint32_t s = sizes[i], stt = status[i];
+			if (s > bound) { printf("size beyond bound\n"); return 2; }
+			f.write((char *)&s, 4); f.write((char *)&stt, 4); f.write((char *)out.data() + i * stride, s);
+		}
+		if (!guard_ok(stage, (size_t)a.n * a.n_int * istride) || !guard_ok(out, a.n * stride)) { printf("guard hit\n"); return 2; }
+	} else {
+		JlsDecArgs a{};
+		a.rows = atoi(argv[2]); a.cols = atoi(argv[3]); a.out_bits = atoi(argv[4]);
+		const size_t nslots = atoi(argv[5]), N = (size_t)a.rows * a.cols, px = a.out_bits / 8;
+		auto job = rd(argv[6]); auto files = rd(argv[7]);
+		const uint32_t *w = (const uint32_t *)job.data();
+		const size_t nf = w[0], ni = (job.size() / 4 - 1 - nf * 10) / 5;
+		std::vector<JlsFrame> frames(nf);
+		std::vector<JlsInterval> ints(ni);
+		for (size_t i = 0; i < nf; i++) { frames[i].slot = w[1 + i * 10]; frames[i].par = params_of(w + 2 + i * 10); }
+		const uint32_t *v = w + 1 + nf * 10;
+		for (size_t i = 0; i < ni; i++) { ints[i].src = v[i * 5]; ints[i].len = v[i * 5 + 1]; ints[i].frame = v[i * 5 + 2]; ints[i].row0 = v[i * 5 + 3]; ints[i].nrows = v[i * 5 + 4]; }
+		// the files exactly as long as they are: a read behind the upload is the sanitizer's to find
+		std::vector<uint8_t> exact(files.begin(), files.end());
+		std::vector<uint8_t> img(nslots * N * px + GUARD, 0xEE);
+		std::vector<uint32_t> status(nf);
+		a.files = exact.data(); a.frames = frames.data(); a.nframes = (uint32_t)nf; a.intervals = ints.data(); a.total_int = (uint32_t)ni;
+		a.status = status.data(); a.images = img.data();
+		launch_jls_decode(a, nullptr);
+		std::ofstream f(argv[8], std::ios::binary);
+		f.write((char *)status.data(), nf * 4); f.write((char *)img.data(), nslots * N * px);
+		if (!guard_ok(img, nslots * N * px)) { printf("guard hit\n"); return 2; }
+	}
+	return 0;
+}

@@ -2,7 +2,7 @@
 """Corpus size comparison: the counterpart of the reference's scripts/evaluate.py:52-136 without pydicom.
 
     python tools/evaluate.py DIRECTORY [--results FILE.csv] [--batch 256] [--zip host|device] [--png host|device]
-                             [--png-input host|device] [--rle device] [--jpl device] [--jp2 device|device-native] [--tif lzw|deflate]
+                             [--png-input host|device] [--rle device] [--jpl device] [--jls device] [--jp2 device|device-native] [--tif lzw|deflate]
 
 Every slice under DIRECTORY (.npy, .u16/.raw, .u16.zz, 16-bit .png) gets one CSV row `File,Raw,ZIP,PNG,RLE,JP2,CCT` as
 in results/encoder-comparisons.csv: Raw = bytes of the pixel array, ZIP = zlib.compress at the default level
@@ -24,7 +24,9 @@ behind CCT: the length of the encapsulated PixelData of the slice's JPEG Lossles
 len(cct_hip.dicom_encapsulate([frame])) with the frame from cct_hip.jpeg_lossless_encode_batch; without the flag the CSV has
 no such column.  Like the RLE column it takes 2-byte slices as uint16 whatever their dtype (int16 slices are reinterpreted,
 not offset); 1-byte slices are widened to uint16 and coded at precision 16 too, so that the column means one thing, which
-costs them the longer codes of a 16-bit table and is not what precision 8 would give.  --jp2 device fills the JP2 column
+costs them the longer codes of a 16-bit table and is not what precision 8 would give.  --jls device appends a JLS column
+behind JPL (or CCT) in the same way: the encapsulated JPEG-LS lossless file of cct_hip.jpeg_ls_encode_batch at precision 16,
+slices taken as the JPL column takes them.  --jp2 device fills the JP2 column
 with len(cct_hip.jpeg2000_encode_batch(image, precision=16, shift=4, jp2=True)): a lossless .jp2 file of the 16-bit preview
 value << 4, which is what the reference measured (lib/jpeg2000.py compresses the PNG; OpenJPEG's defaults: 6 resolutions,
 64 x 64 code-blocks).  --jp2 device-native is the same call at shift=0, the .jp2 file of the slice itself, about 38 % smaller
@@ -46,6 +48,7 @@ from _inputs import list_inputs, load_slice  # noqa: E402
 
 FILE, RAW, ZIP, PNG, RLE, JP2, CCT = "File", "Raw", "ZIP", "PNG", "RLE", "JP2", "CCT"  # evaluate.py:29-35
 JPL = "JPL"  # --jpl device only
+JLS = "JLS"  # --jls device only
 TIF = "TIF"  # --tif lzw|deflate only: the last column
 
 
@@ -103,6 +106,9 @@ def main(argv=None):
     ap.add_argument("--jpl", choices=("na", "device"), default="na",
                     help="device: append a JPL column, the encapsulated JPEG Lossless frame from cct_hip.jpeg_lossless_encode_batch at "
                          "precision 16 (2-byte slices viewed as uint16, 1-byte slices widened to uint16)")
+    ap.add_argument("--jls", choices=("na", "device"), default="na",
+                    help="device: append a JLS column, the encapsulated JPEG-LS lossless file from cct_hip.jpeg_ls_encode_batch at "
+                         "precision 16 (slices taken as for --jpl)")
     ap.add_argument("--jp2", choices=("na", "device", "device-native"), default="na",
                     help="the JP2 column: NA, the lossless .jp2 file of value << 4 at precision 16 from cct_hip.jpeg2000_encode_batch (device: the "
                          "reference's measure), or the same of the slice itself (device-native)")
@@ -156,6 +162,12 @@ def main(argv=None):
                                                                 precision=16)
                     for (name, _), fr in zip(chunk, frames):
                         rows[name][JPL] = len(cct_hip.dicom_encapsulate([fr]))
+                if args.jls == "device":
+                    stack = np.stack([img for _, img in chunk])
+                    frames = cct_hip.jpeg_ls_encode_batch(stack.view(np.uint16) if stack.dtype.itemsize == 2 else stack.astype(np.uint16),
+                                                          precision=16)
+                    for (name, _), fr in zip(chunk, frames):
+                        rows[name][JLS] = len(cct_hip.dicom_encapsulate([fr]))
                 if args.jp2 != "na":
                     stack = np.stack([img for _, img in chunk])
                     files = cct_hip.jpeg2000_encode_batch(stack.view(np.uint16) if stack.dtype.itemsize == 2 else stack.astype(np.uint16),
@@ -170,7 +182,7 @@ def main(argv=None):
         for name, fut in futures.items():
             rows[name].update({k: v for k, v in fut.result().items() if k not in rows[name]})
     outputs = sorted(rows.values(), key=lambda r: r[FILE])  # evaluate.py:130
-    cols = [FILE, RAW, ZIP, PNG, RLE, JP2, CCT] + ([JPL] if args.jpl == "device" else []) + ([TIF] if args.tif != "na" else [])
+    cols = [FILE, RAW, ZIP, PNG, RLE, JP2, CCT] + ([JPL] if args.jpl == "device" else []) + ([JLS] if args.jls == "device" else []) + ([TIF] if args.tif != "na" else [])
     os.makedirs(os.path.dirname(os.path.abspath(args.results)), exist_ok=True)
     with open(args.results, "w") as fout:  # evaluate.py:133-136
         fout.write(",".join(cols))
