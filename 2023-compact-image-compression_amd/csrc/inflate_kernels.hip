@@ -62,12 +62,22 @@ constexpr int SEG_BITS = CCT_INF_SEG_BITS;    // compressed bits per lane and ro
 constexpr int LANE_OUT_CAP = 16384;           // a lane stops (and ends the round) once it has produced this much
 constexpr int MLIST_CAP = 2048;               // LZ77 copies a round may hold (one lane alone: at most SEG_BITS / 2)
 constexpr uint32_t SEG_EOB = 1, SEG_BAD = 2, SEG_CUT = 4;
+// walk_segment's bit budget.  A symbol: code <= 15 bits, a length adds <= 5 extra bits, a distance <= 13.
+constexpr int LL_SYM_BITS = 15 + 5, D_SYM_BITS = 15 + 13, SYM_BITS = LL_SYM_BITS + D_SYM_BITS;
+constexpr int WALK_MIN_BITS = 33 - LL_BITS;   // valid bits a lane holds at least whenever it looks a symbol up
+// How far past the end of its segment a lane reads the staged input.  A symbol starts before `end`, so a lane stands at most
+// SYM_BITS - 1 bits past it; its buffer holds at most 64 bits beyond where it stands; a fast step then reads one dword more.
+// The general step reads two, but only while the lane still stands before `end`: 64 + 64 bits, which is less.  The last
+// lane's `end` is the round's, and need_end rounds that down to a byte: one byte more.
+constexpr int WALK_AHEAD_BITS = SYM_BITS - 1 + 64 + 32;
+constexpr int ROUND_IN_SLACK = 32;            // bytes staged past the last segment of a round (need_end)
+static_assert(WALK_AHEAD_BITS >= 64 + 64 && (WALK_AHEAD_BITS + 7) / 8 + 1 <= ROUND_IN_SLACK, "the walks read inside what a round stages");
 template <class G>
 constexpr bool geo_ok()
 {
 	return 32768 + G::ROUND_OUT_BUDGET <= INF_RING          // the ring holds the 32 KiB window and the output of a round
 	       && LANE_OUT_CAP + 512 <= G::ROUND_OUT_BUDGET        // lane 0 alone always fits a round
-	       && G::NT * SEG_BITS / 8 + 32 + INF_CHUNK <= G::INF_IN  // the staged window covers a round's input
+	       && G::NT * SEG_BITS / 8 + ROUND_IN_SLACK + INF_CHUNK <= G::INF_IN  // the staged window covers a round's input
 	       && G::NWV >= 4;                                     // build_tables: a wave takes at most two chunks of symbols
 }
 static_assert(geo_ok<Geo<256>>() && geo_ok<Geo<512>>(), "INFLATE geometry");
@@ -295,21 +305,21 @@ __device__ void build_tables(InfShared<G> &S, int n)
 		uint32_t a1 = 0;
 #pragma unroll
 		for (int len = FB; len >= 1; len--) if (v < lim[len]) { L1 = len; a1 = adj[len]; }
-		uint32_t e = 0;
-		if (L1) {
-			e = sent[(v >> (15 - L1)) + a1];
-			if (!DIST && (e & (3u << 24)) == K_LIT && L1 < FB) {  // a second literal in the bits that remain?
-				const uint32_t v2 = ((rev << L1) & ((1u << FB) - 1u)) << (15 - FB);
-				int L2 = 0;
-				uint32_t a2 = 0;
+		// a second code in the bits that remain?  Where it starts is known from L1 alone, so both entries are asked for together
+		// (slot 0 stands in where there is none: read, not used)
+		const uint32_t v2 = ((rev << L1) & ((1u << FB) - 1u)) << (15 - FB);
+		int L2 = 0;
+		uint32_t a2 = 0;
+		if (!DIST) {
 #pragma unroll
-				for (int len = FB; len >= 1; len--) if (v2 < lim[len]) { L2 = len; a2 = adj[len]; }
-				if (L2 && L1 + L2 <= FB) {
-					const uint32_t e2 = sent[(v2 >> (15 - L2)) + a2];
-					if ((e2 & (3u << 24)) == K_LIT) e = K_LIT | K_TWO | (((e2 >> 8) & 0xFFu) << 16) | (e & 0xFF00u) | ((uint32_t)L1 << 4) | (uint32_t)(L1 + L2);
-				}
-			}
+			for (int len = FB; len >= 1; len--) if (v2 < lim[len]) { L2 = len; a2 = adj[len]; }
 		}
+		const bool second = !DIST && L1 && L2 && L1 + L2 <= FB;
+		const uint32_t e1 = sent[L1 ? (v >> (15 - L1)) + a1 : 0u];
+		const uint32_t e2 = DIST ? 0u : sent[second ? (v2 >> (15 - L2)) + a2 : 0u];
+		uint32_t e = L1 ? e1 : 0u;
+		if (second && (e & (3u << 24)) == K_LIT && (e2 & (3u << 24)) == K_LIT)
+			e = K_LIT | K_TWO | (((e2 >> 8) & 0xFFu) << 16) | (e & 0xFF00u) | ((uint32_t)L1 << 4) | (uint32_t)(L1 + L2);
 		tab[idx] = e;
 	}
 	__syncthreads();
@@ -326,16 +336,6 @@ __device__ __forceinline__ void lane_init(const InfShared<G> &S, LaneBits &lb, u
 	const uint32_t idx = org_dword + (rel_bit >> 5), sh = rel_bit & 31u;
 	const uint64_t w = (uint64_t)in32[idx & (INF_IN / 4 - 1)] | ((uint64_t)in32[(idx + 1) & (INF_IN / 4 - 1)] << 32);
 	lb.buf = w >> sh; lb.cnt = 64 - (int)sh; lb.next = idx + 2;
-}
-template <class G>
-__device__ __forceinline__ void lane_refill(const InfShared<G> &S, LaneBits &lb)
-{
-	GEO_CONSTANTS;
-	if (lb.cnt <= 32) {
-		const uint32_t *in32 = reinterpret_cast<const uint32_t *>(S.inbuf);
-		lb.buf |= (uint64_t)in32[lb.next & (INF_IN / 4 - 1)] << lb.cnt;
-		lb.cnt += 32; lb.next++;
-	}
 }
 __device__ __forceinline__ uint32_t lane_pos(const LaneBits &lb, uint32_t org_dword) { return (lb.next - org_dword) * 32u - (uint32_t)lb.cnt; }
 
@@ -386,7 +386,21 @@ __device__ __forceinline__ void walk_segment(InfShared<G> &S, uint32_t org_dword
 		if (v < d_lim[D_BITS]) L = 0;
 		return L ? S.d_sent[(v >> (15 - L)) + a] : 0u;
 	};
-	// invariant at the top of a step: more than 21 valid bits in lb.buf (a root lookup needs 11)
+	// Valid bits in lb.buf (lb.cnt), and which LDS reads stand on the lane's dependent chain:
+	//   * top of an iteration: lb.cnt >= 33 (lane_init, or the last merge of the general step);
+	//   * the first fast step therefore has nothing to merge and reads no dword; the others merge at lb.cnt <= 32; each drops
+	//     at most LL_BITS, so every fast step looks up with >= WALK_MIN_BITS valid bits and the general step starts with that many;
+	//   * the general step asks for its root entry and the next two input dwords in one round trip, the index taken from the
+	//     buffer as it is: a merge ORs in above bit lb.cnt and changes no bit a lookup reads.  Code and extra bits of a
+	//     literal/length symbol (LL_SYM_BITS) lie inside the WALK_MIN_BITS; after them a merge gives >= 33 again, which holds
+	//     a distance symbol (D_SYM_BITS), so the d_tab lookup follows the length with no input read in between;
+	//   * the three merges of a general step (top, after the length, bottom) take their dword from registers.  No more than
+	//     two of them happen: a merge leaves lb.cnt <= 64, a third one would leave WALK_MIN_BITS + 96 - SYM_BITS or more.
+	//     w0 is always the dword at lb.next, which advances by one per merge.
+	// No read of the input window stands under a per-lane condition: such a read is waited for where it stands.
+	static_assert(WALK_MIN_BITS >= LL_SYM_BITS && WALK_MIN_BITS >= LL_BITS, "the literal/length lookup and its extra bits need no merge");
+	static_assert(33 >= D_SYM_BITS, "a distance symbol fits what a merge leaves");
+	static_assert(WALK_MIN_BITS + 3 * 32 - SYM_BITS > 64, "a general step merges at most two dwords");
 	auto literal_step = [&](uint32_t e, bool live) {
 		const bool lit = live && (e & (3u << 24)) == K_LIT;
 		const uint32_t l1 = (e >> 4) & 15u;
@@ -403,8 +417,15 @@ __device__ __forceinline__ void walk_segment(InfShared<G> &S, uint32_t org_dword
 	for (;;) {
 #pragma unroll
 		for (int k = 0; k < FAST_STEPS; k++) {
-			const uint32_t w = in32[lb.next & (INF_IN / 4 - 1)];  // next dword, in flight together with the table lookup
-			const uint32_t e = S.ll_tab[(uint32_t)lb.buf & ((1u << LL_BITS) - 1u)];
+			if (k == 0) {  // lb.cnt >= 33 at the top of an iteration: nothing to merge, nothing to read
+				literal_step(S.ll_tab[(uint32_t)lb.buf & ((1u << LL_BITS) - 1u)], p < end);
+				continue;
+			}
+			uint32_t w = in32[lb.next & (INF_IN / 4 - 1)];  // next dword, in flight together with the table lookup
+			uint32_t e = S.ll_tab[(uint32_t)lb.buf & ((1u << LL_BITS) - 1u)];
+			// the last one's dword is only needed if the walk goes on: left alone, its read sinks below the exit test and
+			// becomes a round trip of its own
+			if (k == FAST_STEPS - 1) asm volatile("" : "+v"(w), "+v"(e));
 			const bool take = lb.cnt <= 32;
 			lb.buf |= take ? (uint64_t)w << (lb.cnt & 63) : 0ull;
 			lb.cnt += take ? 32 : 0; lb.next += take ? 1u : 0u;
@@ -413,9 +434,17 @@ __device__ __forceinline__ void walk_segment(InfShared<G> &S, uint32_t org_dword
 		if (p >= end) break;
 		if (steps) ++*steps;
 		if (nbytes >= (uint32_t)LANE_OUT_CAP) { flags = SEG_CUT; break; }  // keeps a round inside the output ring
-		lane_refill(S, lb);
+		uint32_t e = S.ll_tab[(uint32_t)lb.buf & ((1u << LL_BITS) - 1u)];
+		uint32_t w0 = in32[lb.next & (INF_IN / 4 - 1)], w1 = in32[(lb.next + 1u) & (INF_IN / 4 - 1)];
+		asm volatile("" : "+v"(e), "+v"(w0), "+v"(w1));  // all three asked for here, one wait
+		auto merge = [&]() {
+			const bool take = lb.cnt <= 32;
+			lb.buf |= take ? (uint64_t)w0 << (lb.cnt & 63) : 0ull;
+			lb.cnt += take ? 32 : 0; lb.next += take ? 1u : 0u;
+			w0 = take ? w1 : w0;
+		};
+		merge();
 		const uint32_t lo = (uint32_t)lb.buf;
-		uint32_t e = S.ll_tab[lo & ((1u << LL_BITS) - 1u)];
 		if (e == 0) {
 			if (steps) ++steps[1];
 			e = long_ll(lo);
@@ -428,7 +457,7 @@ __device__ __forceinline__ void walk_segment(InfShared<G> &S, uint32_t org_dword
 			const uint32_t cb = e & 15u, xb = (e >> 4) & 15u;
 			const uint32_t val = ((e >> 8) & 0xFFFFu) + ((lo >> cb) & ((1u << xb) - 1u));  // code <= 15, extra <= 5 bits: inside lo
 			lb.buf >>= (cb + xb); lb.cnt -= (int)(cb + xb); p += cb + xb;
-			lane_refill(S, lb);
+			merge();
 			const uint32_t dlo = (uint32_t)lb.buf;
 			uint32_t de = S.d_tab[dlo & ((1u << D_BITS) - 1u)];
 			if (de == 0) {
@@ -444,7 +473,7 @@ __device__ __forceinline__ void walk_segment(InfShared<G> &S, uint32_t org_dword
 			}
 			nbytes += val; nmatch++;
 		}
-		lane_refill(S, lb);
+		merge();
 	}
 	land = p;
 }
@@ -766,7 +795,7 @@ __global__ void __launch_bounds__(G::NT) inflate_kernel(InflateArgs a, uint64_t 
 			PROF_T(P_FLUSH);
 			PROF_C(C_ROUNDS, 1);
 			if ((bitpos >> 3) > br.nbytes + 16) { err |= CCT_ST_ZLIB; break; }  // decoding zeros past the end
-			const uint64_t need_end = ((bitpos + (uint64_t)NT * SEG_BITS) >> 3) + 32;
+			const uint64_t need_end = ((bitpos + (uint64_t)NT * SEG_BITS) >> 3) + ROUND_IN_SLACK;
 			while (need_end > br.staged_end) stage_chunk(S, br);
 			PROF_T(P_STAGE);
 			const uint32_t org_dword = (uint32_t)(bitpos >> 5);      // lanes address bits relative to this dword
