@@ -182,7 +182,8 @@ struct Context {
 	int runtime_bs = 0;  // option "runtime_block_size": 1 sends every block size through the run-time block size kernels (encode_kernel<0>,
 	                     // decode_kernel<0>), which otherwise run the sizes that are not powers of two only; for cross-checks and measurements
 	int last_dec_path = -1;  // read-only option "last_decode_path": 0 a decode_kernel compiled for the block size, 1 the run-time block size kernel
-	int dbg_skip = 0;   // option "debug_skip": phase-ablation mask for tuning runs (outputs invalid when set)
+	int dbg_skip = 0;   // option "debug_skip", tuning build only (tuning.h): phase-ablation mask (outputs invalid when set)
+	int tuning_build = TUNING;  // read-only option "tuning_build", tuning build only: how a tool asks which library it loaded
 	int device_deflate = 1;  // option "device_deflate": 0 = DEFLATE stage on the host thread team (libz)
 	int device_inflate = 1;  // option "device_inflate": 1 = INFLATE on the device (inflate_kernels.hip, speculative lane-parallel
 	                         // decode), 0 = libz on the host thread team (same bytes; bounded by the host CPUs the process may use)
@@ -202,6 +203,11 @@ struct EncodeInFlight {
 	EncodeInFlight() { g_encodes_in_flight.fetch_add(1, std::memory_order_relaxed); }
 	~EncodeInFlight() { g_encodes_in_flight.fetch_sub(1, std::memory_order_relaxed); }
 };
+
+bool trace_on()  // CCT_TRACE (tuning.h): host timings of every batch call on stderr
+{
+	return tuning_env("CCT_TRACE", 0) != 0;
+}
 
 double now_ms()
 {
@@ -695,7 +701,7 @@ int encode_payload_locked(EncSlot &E, hipStream_t st, const uint16_t *d_images, 
 		sa.e = a;
 		sa.tiles = tb->tiles; sa.ptab = tb->d_ptab; sa.htab = tb->d_htab; sa.otab = tb->d_otab; sa.ttab = tb->d_ttab;
 		sa.n_tiles = tb->n_tiles; sa.row_pitch = width; sa.gps = gps; sa.tpg = tpg;
-		{ static const char *dbg = getenv("CCT_STREAM_DBG"); sa.dbg = dbg ? atoi(dbg) : 0; }
+		{ static const int dbg = tuning_env("CCT_STREAM_DBG", 0); sa.dbg = dbg; }
 		sa.hand = (uint64_t *)E.e_hand.p; sa.ticket = (uint32_t *)(sa.hand + (size_t)n * gps * 4);
 		sa.spill_mask = (uint64_t *)E.e_lmask.p; sa.spill_idx = (uint16_t *)E.e_lidx.p; sa.pairrec = (uint8_t *)E.e_pairrec.p;
 		g_ctx.last_path = 3;
@@ -1468,7 +1474,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 			double t_c1 = t_c0;
 			if ((rc = files_to_archive(f, h_out + at, &t_c1))) return rc;
 			tl_d2h_ms += (float)(now_ms() - t_c0);
-			if (getenv("CCT_TRACE"))
+			if (trace_on())
 				fprintf(stderr, "[cct] encode n=%d: deflate %.2f ms, pack+d2h %.2f ms, host scatter %.2f ms (%zu bytes)\n", nc,
 				        t_dev_deflate_ms, t_c1 - t_c0, now_ms() - t_c1, f.exact);
 			continue;
@@ -1491,7 +1497,7 @@ static int encode_batch_impl(const uint16_t *images, int images_on_device, int n
 		if (lk.owns_lock()) lk.unlock();  // the slot is free for the next batch; only the copy stream still works for this one
 		HIP_TRY(hipEventSynchronize(P.ev_copied));
 		copies->disarm();
-		if (getenv("CCT_TRACE"))
+		if (trace_on())
 			fprintf(stderr, "[cct] encode n=%d: waited for a slot %.2f ms, held it %.2f ms (kernel %.2f, deflate %.2f), tail %.2f ms, t=%.2f\n", nc,
 			        t_lock0 - t_call0, t_unlock - t_lock0, tl_enc_kernel_ms, t_dev_deflate_ms, now_ms() - t_unlock, t_lock0);
 		tl_d2h_ms += (float)(now_ms() - t_c0);  // (no lock: a float for cct_last_timings)
@@ -2222,7 +2228,7 @@ int cct_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, i
 			HIP_TRY(hipMemcpyAsync(images, d_img, (size_t)n * N * 2, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
 		HIP_TRY(hipEventElapsedTime(&tl_dec_kernel_ms, D.ev_d0, D.ev_d1));
-		if (getenv("CCT_TRACE"))
+		if (trace_on())
 			fprintf(stderr, "[cct] decode n=%d: inflate %.2f ms, h2d+kernel+sync %.2f ms (kernel %.2f), used %zu of stride %zu\n", n,
 			        t_inflate, now_ms() - t_h0, tl_dec_kernel_ms, used, stride);
 	}
@@ -2254,63 +2260,75 @@ int cct_last_timings(float *out6)
 	return CCT_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// One table for cct_set_option and cct_get_option.  `rule` validates or clamps a value on its way in (it may refuse with a
+// message); read-only keys have none.  Tuning-only keys are unknown to a release build (tuning.h).
+struct Option {
+	const char *name;
+	int Context::*member;
+	int (*rule)(int &value);
+	bool read_only, tuning_only;
+};
+int rule_any(int &) { return CCT_OK; }
+int rule_bool(int &v) { v = v ? 1 : 0; return CCT_OK; }
+const Option OPTIONS[] = {
+	{"zlib_threads", &Context::zlib_threads, [](int &v) { return v < 1 ? fail(CCT_E_ARG, "zlib_threads < 1") : CCT_OK; }},
+	{"tile_path", &Context::use_tiles, [](int &v) {
+		if (v == 3) return fail(CCT_E_ARG, "tile_path 3 (the four-kernel pipeline) has been removed");
+		v = (v >= 0 && v <= 4) ? v : 1; return (int)CCT_OK; }},
+	{"stream_tpg", &Context::stream_tpg, [](int &v) { v = (v == 1 || v == 2 || v == 4) ? v : STREAM_TPG; return (int)CCT_OK; }},
+	{"runtime_block_size", &Context::runtime_bs, rule_bool},
+	{"device_deflate", &Context::device_deflate, rule_bool},
+	{"device_inflate", &Context::device_inflate, rule_bool},
+	{"deflate_graph", &Context::use_graph, rule_bool},
+	{"deflate_compact_records", &Context::compact_recs, rule_bool},
+	{"decode_yields", &Context::decode_yields, rule_bool},
+	{"queue_ahead", &Context::queue_ahead, rule_bool},
+	{"deflate_fork", &Context::deflate_fork, rule_bool},
+	{"encode_slots", &Context::enc_slots, [](int &v) { v = std::max(1, std::min(v, N_ENC_SLOTS)); return (int)CCT_OK; }},
+	{"decode_slots", &Context::dec_slots, [](int &v) { v = std::max(1, std::min(v, N_DEC_SLOTS)); return (int)CCT_OK; }},
+	{"inflate_lanes", &Context::inflate_lanes, [](int &v) {
+		return v != 0 && v != 256 && v != 512 ? fail(CCT_E_ARG, "inflate_lanes must be 0 (automatic), 256 or 512") : CCT_OK; }},
+	{"png_unfilter_waves", &Context::png_unfilter_waves, [](int &v) {
+		return v != 1 && v != 2 && v != 4 && v != 8 ? fail(CCT_E_ARG, "png_unfilter_waves must be 1, 2, 4 or 8") : CCT_OK; }},
+	{"wg_threads", &Context::wg_threads, [](int &v) {
+		return v != 256 && v != 512 && v != 1024 ? fail(CCT_E_ARG, "wg_threads must be 256, 512 or 1024") : CCT_OK; }},
+	{"last_encode_path", &Context::last_path, nullptr, true},
+	{"last_decode_path", &Context::last_dec_path, nullptr, true},
+	{"last_inflate_lanes", &Context::last_inflate_lanes, nullptr, true},
+	{"debug_skip", &Context::dbg_skip, rule_any, false, true},
+	{"tuning_build", &Context::tuning_build, nullptr, true, true},
+};
+const Option *find_option(const char *key)
+{
+	for (const Option &o : OPTIONS)
+		if (!strcmp(key, o.name) && (TUNING || !o.tuning_only)) return &o;
+	fail(CCT_E_ARG, "unknown option %s", key);
+	return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
 int cct_set_option(const char *key, int value)
 {
 	std::lock_guard<std::mutex> lk(g_mu);
-	if (!strcmp(key, "zlib_threads")) { if (value < 1) return fail(CCT_E_ARG, "zlib_threads < 1"); g_ctx.zlib_threads = value; return CCT_OK; }
-	if (!strcmp(key, "tile_path")) {
-		if (value == 3) return fail(CCT_E_ARG, "tile_path 3 (the four-kernel pipeline) has been removed");
-		g_ctx.use_tiles = (value >= 0 && value <= 4) ? value : 1; return CCT_OK;
-	}
-	if (!strcmp(key, "stream_tpg")) { g_ctx.stream_tpg = (value == 1 || value == 2 || value == 4) ? value : STREAM_TPG; return CCT_OK; }
-	if (!strcmp(key, "debug_skip")) { g_ctx.dbg_skip = value; return CCT_OK; }
-	if (!strcmp(key, "runtime_block_size")) { g_ctx.runtime_bs = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "device_deflate")) { g_ctx.device_deflate = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "device_inflate")) { g_ctx.device_inflate = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "deflate_graph")) { g_ctx.use_graph = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "deflate_compact_records")) { g_ctx.compact_recs = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "decode_yields")) { g_ctx.decode_yields = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "queue_ahead")) { g_ctx.queue_ahead = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "deflate_fork")) { g_ctx.deflate_fork = value ? 1 : 0; return CCT_OK; }
-	if (!strcmp(key, "encode_slots")) { g_ctx.enc_slots = std::max(1, std::min(value, N_ENC_SLOTS)); return CCT_OK; }
-	if (!strcmp(key, "decode_slots")) { g_ctx.dec_slots = std::max(1, std::min(value, N_DEC_SLOTS)); return CCT_OK; }
-	if (!strcmp(key, "inflate_lanes")) {
-		if (value != 0 && value != 256 && value != 512) return fail(CCT_E_ARG, "inflate_lanes must be 0 (automatic), 256 or 512");
-		g_ctx.inflate_lanes = value; return CCT_OK;
-	}
-	if (!strcmp(key, "png_unfilter_waves")) {
-		if (value != 1 && value != 2 && value != 4 && value != 8) return fail(CCT_E_ARG, "png_unfilter_waves must be 1, 2, 4 or 8");
-		g_ctx.png_unfilter_waves = value; return CCT_OK;
-	}
-	if (!strcmp(key, "wg_threads")) {
-		if (value != 256 && value != 512 && value != 1024) return fail(CCT_E_ARG, "wg_threads must be 256, 512 or 1024");
-		g_ctx.wg_threads = value; return CCT_OK;
-	}
-	return fail(CCT_E_ARG, "unknown option %s", key);
+	const Option *o = find_option(key);
+	if (!o) return CCT_E_ARG;
+	if (o->read_only) return fail(CCT_E_ARG, "unknown option %s", key);
+	if (int rc = o->rule(value)) return rc;
+	g_ctx.*o->member = value;
+	return CCT_OK;
 }
 int cct_get_option(const char *key, int *value)
 {
 	std::lock_guard<std::mutex> lk(g_mu);
-	if (!strcmp(key, "zlib_threads")) { *value = g_ctx.zlib_threads; return CCT_OK; }
-	if (!strcmp(key, "tile_path")) { *value = g_ctx.use_tiles; return CCT_OK; }
-	if (!strcmp(key, "stream_tpg")) { *value = g_ctx.stream_tpg; return CCT_OK; }
-	if (!strcmp(key, "last_encode_path")) { *value = g_ctx.last_path; return CCT_OK; }
-	if (!strcmp(key, "runtime_block_size")) { *value = g_ctx.runtime_bs; return CCT_OK; }
-	if (!strcmp(key, "last_decode_path")) { *value = g_ctx.last_dec_path; return CCT_OK; }
-	if (!strcmp(key, "device_deflate")) { *value = g_ctx.device_deflate; return CCT_OK; }
-	if (!strcmp(key, "device_inflate")) { *value = g_ctx.device_inflate; return CCT_OK; }
-	if (!strcmp(key, "deflate_graph")) { *value = g_ctx.use_graph; return CCT_OK; }
-	if (!strcmp(key, "deflate_compact_records")) { *value = g_ctx.compact_recs; return CCT_OK; }
-	if (!strcmp(key, "decode_yields")) { *value = g_ctx.decode_yields; return CCT_OK; }
-	if (!strcmp(key, "queue_ahead")) { *value = g_ctx.queue_ahead; return CCT_OK; }
-	if (!strcmp(key, "deflate_fork")) { *value = g_ctx.deflate_fork; return CCT_OK; }
-	if (!strcmp(key, "encode_slots")) { *value = g_ctx.enc_slots; return CCT_OK; }
-	if (!strcmp(key, "decode_slots")) { *value = g_ctx.dec_slots; return CCT_OK; }
-	if (!strcmp(key, "inflate_lanes")) { *value = g_ctx.inflate_lanes; return CCT_OK; }
-	if (!strcmp(key, "last_inflate_lanes")) { *value = g_ctx.last_inflate_lanes; return CCT_OK; }
-	if (!strcmp(key, "png_unfilter_waves")) { *value = g_ctx.png_unfilter_waves; return CCT_OK; }
-	if (!strcmp(key, "wg_threads")) { *value = g_ctx.wg_threads; return CCT_OK; }
-	return fail(CCT_E_ARG, "unknown option %s", key);
+	const Option *o = find_option(key);
+	if (!o) return CCT_E_ARG;
+	*value = g_ctx.*o->member;
+	return CCT_OK;
 }
 
 }  // extern "C"

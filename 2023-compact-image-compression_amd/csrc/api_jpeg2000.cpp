@@ -233,8 +233,8 @@ int cct_j2k_encode_batch(const void *images, int images_on_device, int n, int ro
 		J2kArgs a{};
 		a.images = d_img; a.src_bits = (uint32_t)src_bits; a.n = (uint32_t)nc; a.rows = (uint32_t)rows; a.cols = (uint32_t)cols;
 		a.precision = (uint32_t)precision; a.shift = (uint32_t)shift; a.levels = (uint32_t)levels; a.codeblock = (uint32_t)codeblock;
-		const char *stages = getenv("CCT_J2K_STAGES");  // tools/bench_jpeg2000.py: time the stages; the files are valid at 7 only
-		a.stages = stages ? (uint32_t)atoi(stages) | 1u : 7u;
+		const int stages = tuning_env("CCT_J2K_STAGES", 7);  // tools/bench_jpeg2000.py: time the stages (read per call: the tool changes it); the files are valid at 7 only
+		a.stages = (uint32_t)stages | 1u;
 		a.plane_a = (int32_t *)W[E_PLANE_A].p; a.plane_b = (int32_t *)W[E_PLANE_B].p;
 		a.blocks = (const J2kBlock *)W[E_LAYOUT].p; a.nblocks = (uint32_t)nb;
 		a.bands = (const J2kBand *)((const uint8_t *)W[E_LAYOUT].p + blocks_bytes); a.nbands = (uint32_t)L.bands.size();
@@ -325,7 +325,7 @@ int cct_j2k_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int 
 		}
 		return b;
 	};
-	const char *stages = getenv("CCT_J2K_DEC_STAGES");  // tools/bench_jpeg2000_decode.py: time the stages; the rasters are valid at 15 only
+	const int stages = tuning_env("CCT_J2K_DEC_STAGES", 15);  // tools/bench_jpeg2000_decode.py: time the stages (read per call); the rasters are valid at 15 only
 	DecLease lease;
 	if ((rc = lease_decode_slot(lease))) return rc;
 	hipStream_t st = lease.stream;
@@ -390,7 +390,7 @@ int cct_j2k_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int 
 			a.cbs = (J2kDecCb *)W[D_CBS].p; a.ncbs = (uint32_t)ncbs; a.tt = (uint8_t *)W[D_TT].p; a.chunks = (J2kDecChunk *)W[D_CHUNKS].p;
 			a.status = (uint32_t *)W[D_STATUS].p; a.plane_a = (int32_t *)W[D_PLANE_A].p; a.plane_b = (int32_t *)W[D_PLANE_B].p;
 			a.nslots = (uint32_t)(c1 - c0); a.rows = (uint32_t)rows; a.cols = (uint32_t)cols; a.max_levels = max_levels;
-			a.out_bits = (uint32_t)bits; a.shift = (uint32_t)shift; a.stages = stages ? (uint32_t)atoi(stages) | 1u : 15u;
+			a.out_bits = (uint32_t)bits; a.shift = (uint32_t)shift; a.stages = (uint32_t)stages | 1u;
 			a.images = d_img;
 			if ((rc = ev.begin(st))) return rc;
 			HIP_TRY(hipMemsetAsync(W[D_STATUS].p, 0, nf * 4, st));

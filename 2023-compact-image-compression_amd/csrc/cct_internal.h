@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "deflate_workspace.h"
+#include "tuning.h"
 
 namespace cct {
 
@@ -44,7 +45,7 @@ struct EncArgs {
 	uint8_t *ws_lcur;         // n * NB spill: cur counts
 	uint32_t *stats;          // optional n * 4: short, full, jump tokens, difficult blocks
 	uint8_t *roles_out;       // optional n * NB: final role of every block (BLOCK_JUMPS)
-	uint32_t dbg_skip;        // tuning only (option "debug_skip"): phases to skip, results then invalid
+	uint32_t dbg_skip;        // tuning build only (tuning.h, option "debug_skip"): phases to skip, results then invalid; 0 in a release build
 	int bs;                   // block size, set by launch_encode, read by encode_kernel<0> (run-time block size) only; fills the tail
 	                          // padding, so the struct keeps its size and the other kernels their argument layout
 };
@@ -88,7 +89,7 @@ struct StreamArgs {
 	const uint32_t *ttab;        // 16 * 4 dwords: token byte selectors and length for the 16 two-byte masks of a 4-pixel group, kept
 	                             //   bits of the low bytes
 	int n_tiles, row_pitch, gps, tpg; // gps: groups per slice, tpg: tiles per group
-	int dbg;                     // tuning runs only (CCT_STREAM_DBG): 1 no carry wait, 2 no look-back (results then invalid), 4 wrong group guess (results valid)
+	int dbg;                     // tuning build only (tuning.h, CCT_STREAM_DBG): 1 no carry wait, 2 no look-back (results then invalid), 4 wrong group guess (results valid); 0 in a release build
 	uint64_t *hand;              // n * gps * 4 hand-off words, then
 	uint32_t *ticket;            // n group tickets (one allocation: zeroed by one memset before every launch)
 	uint64_t *spill_mask;        // n * NB: candidate masks beyond the LDS list of a tile
@@ -476,7 +477,7 @@ struct J2kBlockOut { uint32_t passes, bytes, zero_planes, dst; };  // Tier-1's r
 struct J2kArgs {
 	const void *images;        // n * rows * cols samples of src_bits (8 or 16)
 	uint32_t src_bits, n, rows, cols, precision, shift, levels, codeblock;
-	uint32_t stages;           // 7: all; tuning runs (CCT_J2K_STAGES) stop early: 1 convert and transform, 2 Tier-1, 4 Tier-2
+	uint32_t stages;           // 7: all, always in a release build; a tuning build (tuning.h, CCT_J2K_STAGES) stops early: 1 convert and transform, 2 Tier-1, 4 Tier-2
 	int32_t *plane_a, *plane_b;  // n * rows * cols each: the coefficients end up in plane_a
 	const J2kBlock *blocks; uint32_t nblocks;
 	const J2kBand *bands; uint32_t nbands;  // 1 + 3 * levels: LL, then HL, LH, HH of every resolution
@@ -605,7 +606,7 @@ struct J2kDecArgs {
 	uint8_t *tt; J2kDecChunk *chunks;
 	uint32_t *status;          // nfiles, zero on entry: J2K_DEC_ST_STREAM
 	int32_t *plane_a, *plane_b;  // one rows x cols plane per slot each
-	uint32_t nslots, rows, cols, max_levels, out_bits, shift, stages;  // stages: 15 all; 1 parse, 2 Tier-1, 4 transform, 8 finish
+	uint32_t nslots, rows, cols, max_levels, out_bits, shift, stages;  // stages: 15 all, always in a release build (tuning.h, CCT_J2K_DEC_STAGES); 1 parse, 2 Tier-1, 4 transform, 8 finish
 	void *images;
 };
 struct J2kDecRun { uint32_t cb0, ncbs, xcb, ycb; };  // consecutive files with the same code-block exponents: one Tier-1 launch

@@ -215,7 +215,7 @@ __device__ __forceinline__ void hand_store(uint64_t *p, uint64_t v) { __hip_atom
 __device__ __forceinline__ uint64_t hand_load(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 constexpr uint32_t SPIN_LIMIT = 1u << 18;   // polls (a microsecond or more each) before a wait gives up with CCT_ST_INTERNAL
 
-// diagnostic build only (CCT_STREAM_STAMPS=1): shader clock at every phase boundary, per wave, to a buffer of their own
+// tuning build only (tuning.h, CCT_STREAM_STAMPS=1): shader clock at every phase boundary, per wave, to a buffer of their own
 #define STAMP(k) do { if (STAMPS) { __builtin_amdgcn_sched_barrier(0); st_[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
 constexpr int N_STAMPS = 16;
 
@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 			}
 		}
 	};
-	const int g_guess = (int)((blockIdx.x / (gridDim.x / gps) + ((a.dbg & 4) ? 1u : 0u)) % (uint32_t)gps);   // (dbg 4: a wrong guess on purpose)
+	const int g_guess = (int)((blockIdx.x / (gridDim.x / gps) + ((TUNING && (a.dbg & 4)) ? 1u : 0u)) % (uint32_t)gps);   // (dbg 4: a wrong guess on purpose)
 	// the tables are requested before the pixels (the loads of a wave return in order: what is needed first goes first)
 	for (int i = tid; i < 128; i += ST) {   // (a workgroup of one wave makes two rounds)
 		const uint32_t tabv = i < 64 ? a.otab[i] : a.ttab[i - 64];
@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 	// the predecessor's carry and last pixel: asked for now, looked at after the resolve (most groups have published both
 	// long before); lanes 0 and 1 of wave 0
 	carry_v = 0;
-	carry_lane = wave == 0 && g > 0 && lane < 2 && !(a.dbg & 1);
+	carry_lane = wave == 0 && g > 0 && lane < 2 && !(TUNING && (a.dbg & 1));
 	carry_src = lane == 0 ? &hand[g > 0 ? g - 1 : 0].carry : &hand[g > 0 ? g - 1 : 0].lastpx;
 	if (carry_lane) carry_v = hand_load(carry_src);
 
@@ -650,7 +650,7 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 		}
 	};
 	if (wave == SW - 1 && !last_group && !carry_out_done && !(head_deferred && chain)) publish_carry();
-	if (wave == 0 && g > 0 && !(a.dbg & 1)) {
+	if (wave == 0 && g > 0 && !(TUNING && (a.dbg & 1))) {
 		uint64_t v = carry_v;
 		uint32_t spins = 0;
 		bool ok = lane >= 2 || (v & H_VALID) != 0;
@@ -808,7 +808,7 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 	uint64_t lb_v = 0;
 	if (wave == 0) {
 		if (lane == 0) hand_store(&hand[g].total, H_VALID | (uint64_t)gtot | (uint64_t)npairs << 24 | (uint64_t)misc[M_NDIFF] << 40);
-		if (lane < g && !(a.dbg & 2)) lb_v = hand_load(&hand[lane].total);
+		if (lane < g && !(TUNING && (a.dbg & 2))) lb_v = hand_load(&hand[lane].total);
 	}
 	STAMP(12);
 
@@ -822,7 +822,7 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 	}
 	__syncthreads();
 	STAMP(13);
-	if (wave == 0 && lane < g && !(lb_v & H_VALID) && !(a.dbg & 2)) lb_v = hand_load(&hand[lane].total);   // asked again
+	if (wave == 0 && lane < g && !(lb_v & H_VALID) && !(TUNING && (a.dbg & 2))) lb_v = hand_load(&hand[lane].total);   // asked again
 #pragma unroll
 	for (int s = 0; s < 4; s++) {
 		const int b = 256 * wave + 64 * s + lane;
@@ -850,7 +850,7 @@ __global__ void __launch_bounds__(64 * SW, 4) stream_kernel(StreamArgs a, uint64
 	if (wave == 0) {
 		// the bytes before the group: the predecessors' totals, 64 at a time
 		uint32_t bytes = 0, nj = 0, ndf = 0, spins = 0;
-		if (a.dbg & 2) bytes = (uint32_t)g * (uint32_t)(NBG * 20);
+		if (TUNING && (a.dbg & 2)) bytes = (uint32_t)g * (uint32_t)(NBG * 20);
 		else for (int c0 = 0; c0 < g; c0 += 64) {
 			uint64_t v = c0 == 0 ? lb_v : 0ull;
 			bool ok = c0 + lane >= g || (v & H_VALID) != 0;
@@ -957,28 +957,22 @@ static void report_stream_stamps(const uint64_t *d_buf, size_t nwaves)
 	for (int k = 0; k + 1 < N_STAMPS; k++) fprintf(stderr, "    %-16s %8.0f cycles  %5.1f %%\n", name[k], sum[k] / m, 100.0 * sum[k] / all);
 }
 
-hipError_t launch_encode_stream(const StreamArgs &sa, int n, hipStream_t s)
+// STAMPS is true in a tuning build with CCT_STREAM_STAMPS set only: a release build never instantiates the stamped kernels,
+// and the allocation, the synchronous clear and the wait below (what host.h records next to an open capture) leave with them
+template <bool STAMPS>
+static hipError_t launch_stream(const StreamArgs &sa, int n, hipStream_t s)
 {
-	// tickets and hand-off words start from zero in every launch (one memset node in a captured graph)
-	hipError_t e = hipMemsetAsync(sa.hand, 0, stream_ws_bytes(n, sa.gps), s);
-	if (e != hipSuccess) return e;
-	e = hipMemsetAsync(sa.e.status, 0, (size_t)n * sizeof(uint32_t), s);  // every group ORs its bits in
-	if (e != hipSuccess) return e;
 	const bool sg = (sa.e.flags & CCT_FLAG_SIGNED_SEG) != 0;
-	static const bool stamps_on = getenv("CCT_STREAM_STAMPS") != nullptr;
 	uint64_t *d_st = nullptr;
 	const size_t nw = (size_t)n * sa.gps * sa.tpg;
-	if (stamps_on) {
+	if constexpr (STAMPS) {
 		if (hipMalloc(&d_st, nw * (N_STAMPS + 2) * 8) != hipSuccess) return hipErrorOutOfMemory;
 		(void)hipMemset(d_st, 0, nw * (N_STAMPS + 2) * 8);
 	}
 #define CCT_LAUNCH(SWV)                                                                                                          \
 	do {                                                                                                                           \
-		if (stamps_on) {                                                                                                             \
-			if (sg) hipLaunchKernelGGL((stream_kernel<SWV, true, true>), dim3(n * sa.gps), dim3(64 * SWV), 0, s, sa, d_st);          \
-			else hipLaunchKernelGGL((stream_kernel<SWV, false, true>), dim3(n * sa.gps), dim3(64 * SWV), 0, s, sa, d_st);           \
-		} else if (sg) hipLaunchKernelGGL((stream_kernel<SWV, true, false>), dim3(n * sa.gps), dim3(64 * SWV), 0, s, sa, d_st);    \
-		else hipLaunchKernelGGL((stream_kernel<SWV, false, false>), dim3(n * sa.gps), dim3(64 * SWV), 0, s, sa, d_st);            \
+		if (sg) hipLaunchKernelGGL((stream_kernel<SWV, true, STAMPS>), dim3(n * sa.gps), dim3(64 * SWV), 0, s, sa, d_st);           \
+		else hipLaunchKernelGGL((stream_kernel<SWV, false, STAMPS>), dim3(n * sa.gps), dim3(64 * SWV), 0, s, sa, d_st);            \
 	} while (0)
 	switch (sa.tpg) {
 	case 1: CCT_LAUNCH(1); break;
@@ -987,12 +981,23 @@ hipError_t launch_encode_stream(const StreamArgs &sa, int n, hipStream_t s)
 	default: return hipErrorInvalidValue;
 	}
 #undef CCT_LAUNCH
-	if (stamps_on) {
+	if constexpr (STAMPS) {
 		(void)hipStreamSynchronize(s);
 		report_stream_stamps(d_st, nw);
 		(void)hipFree(d_st);
 	}
 	return hipGetLastError();
+}
+
+hipError_t launch_encode_stream(const StreamArgs &sa, int n, hipStream_t s)
+{
+	// tickets and hand-off words start from zero in every launch (one memset node in a captured graph)
+	hipError_t e = hipMemsetAsync(sa.hand, 0, stream_ws_bytes(n, sa.gps), s);
+	if (e != hipSuccess) return e;
+	e = hipMemsetAsync(sa.e.status, 0, (size_t)n * sizeof(uint32_t), s);  // every group ORs its bits in
+	if (e != hipSuccess) return e;
+	static const bool stamps_on = tuning_env("CCT_STREAM_STAMPS", 0) != 0;
+	return stamps_on ? launch_stream<TUNING>(sa, n, s) : launch_stream<false>(sa, n, s);
 }
 
 }  // namespace cct

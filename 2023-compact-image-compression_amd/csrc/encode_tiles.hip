@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(TT) encode_tiles_kernel(TileEncArgs ta)
 	const int sl = blockIdx.x;
 	const int N = a.N, NB = a.NB;
 	const int NS = N / STP;
-	const uint32_t dbg = a.dbg_skip;
+	const uint32_t dbg = TUNING ? a.dbg_skip : 0u;  // a release build skips nothing: every test of dbg below folds away
 	const bool seg = (a.flags & CCT_FLAG_SEGMENTATION) != 0 && !(dbg & 1u);
 	const uint16_t *img = a.images + (size_t)sl * N;
 	uint8_t *role_g = ROLE_LDS ? nullptr : a.ws_role + (size_t)sl * NB;

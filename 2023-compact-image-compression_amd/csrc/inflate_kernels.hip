@@ -592,7 +592,7 @@ __device__ __forceinline__ int first_lane_with(InfShared<G> &S, bool pred, int s
 	return (int)r;
 }
 
-// tuning runs only (CCT_INF_PROF=1): cycles per phase and event counts of every stream, written by lane 0
+// tuning build only (tuning.h, CCT_INF_PROF=1): cycles per phase and event counts of every stream, written by lane 0
 enum { P_M_SETUP, P_HDR, P_TABLES, P_T_CLLENS, P_T_CL, P_T_CLWALK, P_T_LL, P_STAGE, P_WALK0, P_RESTART, P_SCAN, P_EMIT, P_MATCH, P_FLUSH, P_TOTAL, C_BLOCKS, C_ROUNDS, C_PASSES, C_MATCHES,
        C_DEP, C_BATCH, C_LASTL, C_STEPMAX, C_STEPSUM, C_MATCHMAX, C_W0CYC, C_W0STEPS, P_N };
 #define PROF_T(slot) do { if (PROF) { const long long t_ = clock64(); prof[slot] += (uint64_t)(t_ - tprev); tprev = t_; } } while (0)
@@ -980,29 +980,33 @@ template <class G>
 static hipError_t launch_inflate_geo(const InflateArgs &a, int n, hipStream_t st)
 {
 	const size_t lds = sizeof(InfShared<G>);
-	static const bool want_prof = getenv("CCT_INF_PROF") != nullptr;
-	if (want_prof) {  // tuning runs only: synchronises and prints per-phase averages
-		static const char *names[P_N] = {"match_setup", "hdr", "tables(rest)", "t_cllens", "t_buildcl", "t_clwalk", "t_ll", "stage", "walk0", "restart", "scan", "emit", "match", "flush", "TOTAL", "#blocks", "#rounds",
-		                                 "#passes", "#matches", "#dependent", "#batches", "#lanes_used", "sum_round_max_gensteps", "sum_gensteps",
-		                                 "sum_long_codes", "wave0_walk_cycles", "wave0_outer_steps"};
-		uint64_t *d_prof = nullptr;
-		hipError_t e = hipMalloc(&d_prof, (size_t)n * P_N * 8);
-		if (e != hipSuccess) return e;
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel<G, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		hipLaunchKernelGGL((inflate_kernel<G, true>), dim3(n), dim3(G::NT), lds, st, a, d_prof);
-		std::vector<uint64_t> h((size_t)n * P_N);
-		e = hipMemcpyAsync(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost, st);
-		if (e == hipSuccess) e = hipStreamSynchronize(st);
-		(void)hipFree(d_prof);
-		if (e != hipSuccess) return e;
-		fprintf(stderr, "[inflate prof] n=%d lanes=%d, per stream:", n, G::NT);
-		for (int i = 0; i < P_N; i++) {
-			double sum = 0;
-			for (int s = 0; s < n; s++) sum += (double)h[(size_t)s * P_N + i];
-			fprintf(stderr, " %s=%.0f", names[i], sum / n);
+	// tuning build only (tuning.h): in a release build this template's instantiations discard the block, so
+	// inflate_kernel<G, true> is never instantiated and the library holds the two production variants alone
+	if constexpr (TUNING) {
+		static const bool want_prof = tuning_env("CCT_INF_PROF", 0) != 0;
+		if (want_prof) {  // synchronises and prints per-phase averages
+			static const char *names[P_N] = {"match_setup", "hdr", "tables(rest)", "t_cllens", "t_buildcl", "t_clwalk", "t_ll", "stage", "walk0", "restart", "scan", "emit", "match", "flush", "TOTAL", "#blocks", "#rounds",
+			                                 "#passes", "#matches", "#dependent", "#batches", "#lanes_used", "sum_round_max_gensteps", "sum_gensteps",
+			                                 "sum_long_codes", "wave0_walk_cycles", "wave0_outer_steps"};
+			uint64_t *d_prof = nullptr;
+			hipError_t e = hipMalloc(&d_prof, (size_t)n * P_N * 8);
+			if (e != hipSuccess) return e;
+			(void)hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel<G, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+			hipLaunchKernelGGL((inflate_kernel<G, true>), dim3(n), dim3(G::NT), lds, st, a, d_prof);
+			std::vector<uint64_t> h((size_t)n * P_N);
+			e = hipMemcpyAsync(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost, st);
+			if (e == hipSuccess) e = hipStreamSynchronize(st);
+			(void)hipFree(d_prof);
+			if (e != hipSuccess) return e;
+			fprintf(stderr, "[inflate prof] n=%d lanes=%d, per stream:", n, G::NT);
+			for (int i = 0; i < P_N; i++) {
+				double sum = 0;
+				for (int s = 0; s < n; s++) sum += (double)h[(size_t)s * P_N + i];
+				fprintf(stderr, " %s=%.0f", names[i], sum / n);
+			}
+			fprintf(stderr, "\n");
+			return hipSuccess;
 		}
-		fprintf(stderr, "\n");
-		return hipSuccess;
 	}
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(inflate_kernel<G, false>),
 	                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -374,10 +374,10 @@ __global__ __launch_bounds__(256) void j2k_dec_finish_kernel(J2kDecArgs a)
 hipError_t launch_j2k_decode(const J2kDecArgs &a, const J2kDecRun *runs, size_t nruns, hipStream_t st)
 {
 	hipLaunchKernelGGL(j2k_dec_parse_kernel, dim3(a.nfiles), dim3(256), 0, st, a);
-	if (!(a.stages & 2)) return hipGetLastError();
+	if (TUNING && !(a.stages & 2)) return hipGetLastError();
 	for (size_t r = 0; r < nruns; r++)
 		hipLaunchKernelGGL(j2k_dec_tier1_kernel, dim3(runs[r].ncbs), dim3(64), j2k_dec_lds_bytes(runs[r].xcb, runs[r].ycb), st, a, runs[r].cb0);
-	if (!(a.stages & 4)) return hipGetLastError();
+	if (TUNING && !(a.stages & 4)) return hipGetLastError();
 	const J2kSizes z = j2k_level_sizes(a.rows, a.cols, a.max_levels);
 	for (uint32_t d = a.max_levels; d >= 1; d--) {
 		const uint32_t w = z.w[d - 1], h = z.h[d - 1];
@@ -385,7 +385,7 @@ hipError_t launch_j2k_decode(const J2kDecArgs &a, const J2kDecRun *runs, size_t 
 		hipLaunchKernelGGL(j2k_dec_idwt_kernel, grid, dim3(256), 0, st, a, (const int32_t *)a.plane_a, a.plane_b, d, w, h, 0u);
 		hipLaunchKernelGGL(j2k_dec_idwt_kernel, grid, dim3(256), 0, st, a, (const int32_t *)a.plane_b, a.plane_a, d, w, h, 1u);
 	}
-	if (!(a.stages & 8)) return hipGetLastError();
+	if (TUNING && !(a.stages & 8)) return hipGetLastError();
 	const dim3 per_sample((unsigned)(((size_t)a.nfiles * a.rows * a.cols + 255) / 256));
 	if (a.out_bits == 16) hipLaunchKernelGGL(j2k_dec_finish_kernel<uint16_t>, per_sample, dim3(256), 0, st, a);
 	else hipLaunchKernelGGL(j2k_dec_finish_kernel<uint8_t>, per_sample, dim3(256), 0, st, a);

@@ -386,10 +386,10 @@ hipError_t launch_j2k_encode(const J2kArgs &a, hipStream_t st)
 		hipLaunchKernelGGL(j2k_dwt_kernel, grid, dim3(256), 0, st, (const int32_t *)a.plane_a, a.plane_b, a.n, a.rows, a.cols, w, h, 1u);
 		hipLaunchKernelGGL(j2k_dwt_kernel, grid, dim3(256), 0, st, (const int32_t *)a.plane_b, a.plane_a, a.n, a.rows, a.cols, w, h, 0u);
 	}
-	if (!(a.stages & 2)) return hipGetLastError();
+	if (TUNING && !(a.stages & 2)) return hipGetLastError();
 	if (a.codeblock == 64) hipLaunchKernelGGL(j2k_tier1_kernel<64>, dim3(a.n * a.nblocks), dim3(64), 0, st, a);
 	else hipLaunchKernelGGL(j2k_tier1_kernel<32>, dim3(a.n * a.nblocks), dim3(64), 0, st, a);
-	if (!(a.stages & 4)) return hipGetLastError();
+	if (TUNING && !(a.stages & 4)) return hipGetLastError();
 	hipLaunchKernelGGL(j2k_tier2_kernel, dim3(a.n), dim3(256), 0, st, a);
 	return hipGetLastError();
 }

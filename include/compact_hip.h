@@ -567,12 +567,21 @@ int cct_tiff_read_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n
  * [5] reserved.  After cct_png_read_batch: [3] INFLATE, [4] the unfilter kernel, [5] the unpack kernel (CRC check + IDAT
  * gather), HIP events, summed over the passes of the call. */
 int cct_last_timings(float *out6);
-/* Options: "encode_slots" / "decode_slots" (1 or 2 batches on the device at a time), "device_deflate" / "device_inflate"
- * (0: that stage on the host thread team of "zlib_threads" threads), "png_unfilter_waves" (waves per image of the PNG reader's
- * unfilter kernel: 1, 2, 4 or 8), "inflate_lanes" (lanes per stream of the INFLATE kernel:
- * 256, 512, or 0 = 512 unless an encode call is in flight when the decode starts; "last_inflate_lanes" reads back the choice),
- * "tile_path", "stream_tpg", "deflate_graph", "deflate_compact_records", "wg_threads" (kernel choice and
- * tuning), "decode_yields" / "queue_ahead" (scheduling of pipelined calls; 0 switches them off). */
+/* Options.  cct_set_option refuses an unknown key and a read-only one with CCT_E_ARG ("unknown option <key>"); a value
+ * outside a key's set is refused (CCT_E_ARG, the option keeps its value) or clamped, as stated per key:
+ * "encode_slots" / "decode_slots": batches on the device at a time, clamped to 1 .. 2.
+ * "device_deflate" / "device_inflate": 0 runs that stage on the host thread team, any other value is 1.
+ * "zlib_threads": size of that team; below 1 is refused.
+ * "png_unfilter_waves": waves per image of the PNG reader's unfilter kernel: 1, 2, 4 or 8, anything else is refused.
+ * "inflate_lanes": lanes per stream of the INFLATE kernel: 256, 512, or 0 = 512 unless an encode call is in flight when
+ * the decode starts; anything else is refused.  "last_inflate_lanes" (read only) reads back the choice.
+ * "tile_path": 0, 1, 2 or 4 (kernel choice); 3 is refused, any other value is 1.  "stream_tpg": 1, 2 or 4, any
+ * other value is 4.  "wg_threads": 256, 512 or 1024, anything else is refused.
+ * "deflate_graph", "deflate_fork", "deflate_compact_records", "runtime_block_size" (tuning and cross-checks),
+ * "decode_yields" / "queue_ahead" (scheduling of pipelined calls; 0 switches them off): 0, any other value is 1.
+ * "last_encode_path", "last_decode_path" (read only): which kernel the last call ran.
+ * None of these makes an output invalid.  The diagnostic switches that can exist in the tuning build only (csrc/tuning.h;
+ * `make -C 2023-compact-image-compression_amd/csrc tuning`): this library has none to set. */
 int cct_set_option(const char *key, int value);
 int cct_get_option(const char *key, int *value);
 

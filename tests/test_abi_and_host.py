@@ -120,6 +120,99 @@ def test_options_round_trip_without_a_device():
     assert L.cct_get_option(b"no_such_option", C.byref(v)) != 0
 
 
+# every key include/compact_hip.h documents: (value given, value read back) pairs and the values refused, by the rule the
+# header states for the key; None: read only
+OPTION_RULES = {
+    "encode_slots": ([(1, 1), (2, 2), (0, 1), (-5, 1), (7, 2)], []),
+    "decode_slots": ([(1, 1), (2, 2), (0, 1), (9, 2)], []),
+    "device_deflate": ([(0, 0), (1, 1), (5, 1), (-1, 1)], []),
+    "device_inflate": ([(0, 0), (1, 1), (5, 1), (-1, 1)], []),
+    "zlib_threads": ([(1, 1), (3, 3), (64, 64)], [0, -1]),
+    "png_unfilter_waves": ([(1, 1), (2, 2), (4, 4), (8, 8)], [0, 3, 16, -1]),
+    "inflate_lanes": ([(256, 256), (512, 512), (0, 0)], [1, 128, 1024, -1]),
+    "last_inflate_lanes": None,
+    "tile_path": ([(0, 0), (1, 1), (2, 2), (4, 4), (5, 1), (-1, 1), (9, 1)], [3]),
+    "stream_tpg": ([(1, 1), (2, 2), (4, 4), (3, 4), (0, 4), (8, 4)], []),
+    "wg_threads": ([(256, 256), (512, 512), (1024, 1024)], [0, 64, 768, 2048]),
+    "deflate_graph": ([(0, 0), (1, 1), (7, 1), (-1, 1)], []),
+    "deflate_fork": ([(0, 0), (1, 1), (7, 1), (-1, 1)], []),
+    "deflate_compact_records": ([(0, 0), (1, 1), (7, 1), (-1, 1)], []),
+    "runtime_block_size": ([(0, 0), (1, 1), (7, 1), (-1, 1)], []),
+    "decode_yields": ([(0, 0), (1, 1), (7, 1), (-1, 1)], []),
+    "queue_ahead": ([(0, 0), (1, 1), (7, 1), (-1, 1)], []),
+    "last_encode_path": None,
+    "last_decode_path": None,
+}
+
+
+def _documented_options():
+    text = open(os.path.join(ROOT, "include", "compact_hip.h")).read()
+    text = text[text.index("/* Options."):text.index("int cct_set_option")]
+    return sorted(set(re.findall(r'"([a-z_]+)"', text)))
+
+
+def test_every_documented_option_follows_its_rule():
+    """Every key of the header's option list goes through cct_set_option and cct_get_option: accepted values read back as
+    the header says (kept or clamped), refused values return CCT_E_ARG and leave the option alone, read-only keys can be
+    read and not set.  Each key gets its first value back at the end."""
+    from cct_hip import _ffi
+    L = _ffi.lib()
+    keys = _documented_options()
+    assert keys == sorted(OPTION_RULES) and len(keys) == 19
+    v = C.c_int(-1)
+    for key in keys:
+        k = key.encode()
+        assert L.cct_get_option(k, C.byref(v)) == 0, key
+        first = v.value
+        if OPTION_RULES[key] is None:
+            assert L.cct_set_option(k, first) == _ffi.E_ARG and _ffi.last_error() == f"unknown option {key}"
+            assert L.cct_get_option(k, C.byref(v)) == 0 and v.value == first
+            continue
+        accepted, refused = OPTION_RULES[key]
+        for given, want in accepted:
+            assert L.cct_set_option(k, given) == 0, (key, given)
+            assert L.cct_get_option(k, C.byref(v)) == 0 and v.value == want, (key, given, v.value)
+            for bad in refused:
+                assert L.cct_set_option(k, bad) == _ffi.E_ARG and key in _ffi.last_error(), (key, bad)
+                assert L.cct_get_option(k, C.byref(v)) == 0 and v.value == want, (key, bad, v.value)
+        if L.cct_set_option(k, first) != 0:   # a default outside what can be set ("zlib_threads" 0: not chosen yet)
+            assert first in refused and L.cct_shutdown() == 0   # host state back to its defaults
+        assert L.cct_get_option(k, C.byref(v)) == 0 and v.value == first, key
+
+
+SWITCH_NAMES = (b"CCT_STREAM_DBG", b"CCT_STREAM_STAMPS", b"CCT_INF_PROF", b"CCT_J2K_STAGES", b"CCT_J2K_DEC_STAGES", b"CCT_TRACE")
+release_only = pytest.mark.skipif(bool(os.environ.get("CCT_HIP_LIB")), reason="CCT_HIP_LIB names another build of the library")
+
+
+@release_only
+def test_release_library_refuses_debug_skip():
+    from cct_hip import _ffi
+    L = _ffi.lib()
+    assert L.cct_set_option(b"debug_skip", 1) == _ffi.E_ARG and _ffi.last_error() == "unknown option debug_skip"
+    assert L.cct_set_option(b"debug_skip", 0) == _ffi.E_ARG
+
+
+@release_only
+def test_release_library_is_no_tuning_build():
+    from cct_hip import _ffi
+    L = _ffi.lib()
+    v = C.c_int(-1)
+    assert L.cct_get_option(b"tuning_build", C.byref(v)) == _ffi.E_ARG and v.value == -1
+    assert _ffi.last_error() == "unknown option tuning_build"
+    assert L.cct_set_option(b"tuning_build", 1) == _ffi.E_ARG
+
+
+@release_only
+def test_release_library_names_no_diagnostic_switch():
+    """No environment variable can reach a diagnostic path of the release library: their names are not in it."""
+    from cct_hip import _ffi
+    with open(_ffi.LIB_PATH, "rb") as f:
+        blob = f.read()
+    assert len(blob) > 100000
+    for name in SWITCH_NAMES:
+        assert name not in blob, name.decode()
+
+
 def test_shutdown_twice_and_from_threads():
     """cct_shutdown replaces the slot objects; the slot mutexes it holds meanwhile live outside them (round 2 destroyed
     them while locked).  Twice in a row, and racing threads that poll options, must leave a usable library."""

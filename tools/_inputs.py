@@ -1,4 +1,5 @@
-"""Slice loaders shared by tools/demo.py and tools/evaluate.py: the reference callers read DICOM files through pydicom
+"""What the tools share.  need_tuning_build: the check of the tools that use a diagnostic switch.  Slice loaders of
+tools/demo.py and tools/evaluate.py: the reference callers read DICOM files through pydicom
 (scripts/demo.py:51, scripts/evaluate.py:114); pydicom is not part of this environment, so the counterparts take the
 pixel array itself: .npy, raw little-endian 16-bit (.u16, .raw; square or WxH given), zlib'd raw (.u16.zz, the form
 tests/golden keeps the two real slices in) or a 16-bit PNG preview written as value << 4 (lib/png.py:25-31)."""
@@ -8,6 +9,22 @@ import zlib
 import numpy as np
 
 EXTENSIONS = (".npy", ".u16", ".raw", ".u16.zz", ".png")
+
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "2023-compact-image-compression_amd", "csrc")
+TUNING_HOWTO = (f"make -C {_CSRC} tuning, then CCT_HIP_LIB="
+                f"{os.path.join(os.path.dirname(_CSRC), 'cct_hip', 'tuning', 'libcompact_hip.so')}")
+
+
+def need_tuning_build(what, L):
+    """True when the loaded library `L` is the tuning build (csrc/tuning.h): the only one with diagnostic switches.
+    Otherwise one line on stderr says that `what` needs it and how to get one; the caller leaves that part out or exits."""
+    import ctypes as C
+    import sys
+    v = C.c_int(0)
+    if L.cct_get_option(b"tuning_build", C.byref(v)) == 0 and v.value == 1:
+        return True
+    print(f"{what} needs the tuning build of the library: {TUNING_HOWTO}", file=sys.stderr)
+    return False
 
 
 def _square(a):

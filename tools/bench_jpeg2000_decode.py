@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests")]
+sys.path[:0] = [os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 
 def median_ms(fn, reps, L, slot):
@@ -63,7 +63,9 @@ def main(argv=None):
         have_pillow = bool(features.check_codec("jpg_2000"))
     except Exception:
         have_pillow = False
+    from _inputs import need_tuning_build
     L = cct_hip._ffi.lib()
+    split = need_tuning_build("the stage split of tools/bench_jpeg2000_decode.py", L)  # else: the whole-call figures alone
     n = args.slices
     uniq = [ct_phantom(i) for i in range(min(n, 32))]
     real = [gi.load_slice("slice0671"), gi.load_slice("slice3706")]
@@ -83,12 +85,13 @@ def main(argv=None):
                 return cct_hip.jpeg2000_decode_batch(files, 512, 512, out_dev=d_out)
             assert np.array_equal(cct_hip.jpeg2000_decode_batch(files, 512, 512), imgs), "the device does not decode its files to the input"
             r = {"bytes": sum(map(len, files))}
-            cum, call = staged(dec, args.reps, L, 4, "CCT_J2K_DEC_STAGES", (1, 3, 7, 15))
-            ecum, ecall = staged(enc, args.reps, L, 0, "CCT_J2K_STAGES", (1, 3, 7))
-            r.update(parse_ms=cum[1], tier1_ms=cum[3] - cum[1], idwt_ms=cum[7] - cum[3], finish_ms=cum[15] - cum[7], kernel_ms=cum[15], call_ms=call,
-                     kernel_mpix_s=mpix / (cum[15] / 1e3), call_mpix_s=mpix / (call / 1e3),
-                     encoder_tier1_ms=ecum[3] - ecum[1], encoder_kernel_ms=ecum[7], encoder_call_ms=ecall,
-                     tier1_decode_over_encode=(cum[3] - cum[1]) / max(ecum[3] - ecum[1], 1e-6))
+            cum, call = staged(dec, args.reps, L, 4, "CCT_J2K_DEC_STAGES", (1, 3, 7, 15) if split else (15,))
+            ecum, ecall = staged(enc, args.reps, L, 0, "CCT_J2K_STAGES", (1, 3, 7) if split else (7,))
+            r.update(kernel_ms=cum[15], call_ms=call, kernel_mpix_s=mpix / (cum[15] / 1e3), call_mpix_s=mpix / (call / 1e3),
+                     encoder_kernel_ms=ecum[7], encoder_call_ms=ecall)
+            if split:
+                r.update(parse_ms=cum[1], tier1_ms=cum[3] - cum[1], idwt_ms=cum[7] - cum[3], finish_ms=cum[15] - cum[7],
+                         encoder_tier1_ms=ecum[3] - ecum[1], tier1_decode_over_encode=(cum[3] - cum[1]) / max(ecum[3] - ecum[1], 1e-6))
             if have_pillow:
                 from PIL import Image
                 k = min(args.cpu_slices, n)

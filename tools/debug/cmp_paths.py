@@ -1,19 +1,22 @@
 #!/usr/bin/env python3
 """Debug aid: stage (i) through the pipeline (tile_path 1) and the generic kernel (0) on a few slices; prints where the
-block roles / sizes / payload bytes first differ."""
+block roles / sizes / payload bytes first differ.  DBG=mask sets option debug_skip (tuning build only)."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 import golden_inputs as gi
 import cct_hip
 from cct_hip import _ffi, DeviceBuffer, codec_params, encode_payload_dev
 from cct_hip.batch import payload_stride
+from _inputs import need_tuning_build
 
 n_px = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 n = 3
 imgs = np.stack([gi.ct_phantom(40 + i, n_px) for i in range(n)])
 L = _ffi.lib()
+if not need_tuning_build("tools/debug/cmp_paths.py (option debug_skip, DBG=mask)", L):
+    sys.exit(2)
 cfg = cct_hip.default_config()
 w = h = n_px
 nb = w * h // 16

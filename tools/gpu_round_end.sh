@@ -5,6 +5,8 @@
 #   counters of the transform+pack kernels.  Copy what is kept from gpurun_out/round_end/ into profiles/ (tools/collect_profiles.py).
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/round_end
+# the two diagnostic runs below need the tuning build (csrc/tuning.h; make -C .../csrc tuning): the tools say so without it
+TUNING_LIB=$PWD/2023-compact-image-compression_amd/cct_hip/tuning/libcompact_hip.so
 rm -rf $O && mkdir -p $O
 set -e
 timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err
@@ -34,7 +36,7 @@ rm -rf $O/pmc_sq
 timeout -k 10 200 python tools/prof_encode.py --paths 1,2 --reps 30 > $O/prof_encode.log 2>&1
 # every stage alone (serial calls, nothing else on the device), and the INFLATE kernel's phase profile for both geometries
 timeout -k 10 200 python tools/prof_codec.py --reps 5 > $O/prof_codec.log 2>&1
-CCT_INF_PROF=1 timeout -k 10 200 python tools/prof_codec.py --reps 1 --what dec 2>&1 | grep "inflate prof" | head -1 >> $O/prof_codec.log
+CCT_HIP_LIB=$TUNING_LIB CCT_INF_PROF=1 timeout -k 10 200 python tools/prof_codec.py --reps 1 --what dec 2>&1 | grep "inflate prof" | head -1 >> $O/prof_codec.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -- python tools/prof_codec.py --reps 5 > $O/prof_codec_traced.log 2>&1
 find $O/prof2 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/codec_serial_kernel_stats.csv
 rm -rf $O/prof2
@@ -47,8 +49,8 @@ done
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $O/pmcc_sq -- python tools/prof_codec.py --reps 3 > $O/pmc_codec_sq.log 2>&1
 find $O/pmcc_sq -name "*counter_collection.csv" | head -1 | xargs -I{} cp {} $O/pmc_codec_sq_counter_collection.csv
 rm -rf $O/pmcc_sq
-# phase stamps of the streaming kernel (diagnostic build of the same source)
-CCT_STREAM_STAMPS=1 timeout -k 10 200 python tools/prof_encode.py --paths 1 --reps 1 2>&1 | grep -A16 "stream stamps" | head -17 > $O/stream_stamps.log
+# phase stamps of the streaming kernel (tuning build of the same source)
+CCT_HIP_LIB=$TUNING_LIB CCT_STREAM_STAMPS=1 timeout -k 10 200 python tools/prof_encode.py --paths 1 --reps 1 2>&1 | grep -A16 "stream stamps" | head -17 > $O/stream_stamps.log
 echo "pmc done"
 python -c "
 import json

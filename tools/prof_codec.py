@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Tuning harness (not part of the product): whole encode_batch / decode_batch calls on the bench workload, serial
-(no overlap), with the library's own stage timings.  CCT_INF_PROF=1 prints the INFLATE kernel's per-phase cycle counts.
+(no overlap), with the library's own stage timings.  CCT_INF_PROF=1 prints the INFLATE kernel's per-phase cycle counts
+(tuning build of the library only, csrc/tuning.h).
 
     python tools/prof_codec.py [--reps 10] [--slices 256] [--real] [--what enc,dec]
 """
@@ -12,7 +13,7 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 
 def main():
@@ -33,6 +34,10 @@ def main():
     import cct_hip
     from cct_hip import _ffi
     L = _ffi.lib()
+    if os.environ.get("CCT_INF_PROF"):
+        from _inputs import need_tuning_build
+        if not need_tuning_build("CCT_INF_PROF", L):
+            sys.exit(2)
     cfg = cct_hip.default_config()
     files = cct_hip.encode_batch(batch, cfg)
     print(f"n={n} payload->file bytes {sum(len(f) for f in files)}", file=sys.stderr)

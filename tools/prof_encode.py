@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Tuning harness (not part of the product): stage (i) alone -- cct_encode_payload_dev on the bench workload (256
 slices of 512x512, three rotating batches so that HBM and not the Infinity Cache is measured), timed with HIP events
-on the library's stream.  Run it under `rocprofv3 --kernel-trace --stats` for per-kernel times.
+on the library's stream.  Run it under `rocprofv3 --kernel-trace --stats` for per-kernel times.  CCT_STREAM_STAMPS=1 prints
+the phase split of the streaming kernel (tuning build of the library only, csrc/tuning.h).
 
     python tools/prof_encode.py [--paths 1,2] [--reps 30] [--size 512] [--slices 256] [--real]
 """
@@ -12,7 +13,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 
 
 def main():
@@ -43,6 +44,10 @@ def main():
     from cct_hip import _ffi, DeviceBuffer, Event, codec_params, encode_payload_dev
     from cct_hip.batch import payload_stride
     L = _ffi.lib()
+    if os.environ.get("CCT_STREAM_STAMPS"):
+        from _inputs import need_tuning_build
+        if not need_tuning_build("CCT_STREAM_STAMPS", L):
+            sys.exit(2)
     d_imgs = [DeviceBuffer.from_numpy(b) for b in batches]
     stride = payload_stride(w, w, 16)
     d_pay, d_sz, d_st = DeviceBuffer(n * stride), DeviceBuffer(4 * n), DeviceBuffer(4 * n)

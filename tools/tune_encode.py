@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
 """Tuning harness (not part of the product): times the encode kernel alone with phase-ablation
-masks (option debug_skip) on the bench workload.  Usage: python tools_tune.py [masks...]"""
+masks (option debug_skip: tuning build only) on the bench workload.  Usage: python tools/tune_encode.py [masks...]"""
 import sys, os, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "2023-compact-image-compression_amd"), os.path.join(ROOT, "tools")]
 import cct_hip
 from cct_hip import _ffi, DeviceBuffer, Event, codec_params, encode_payload_dev
 from cct_hip.batch import payload_stride
 from bench import make_batches
+from _inputs import need_tuning_build
 
 def main():
     masks = [int(x, 0) for x in sys.argv[1:]] or [0]
     L = _ffi.lib()
+    if not need_tuning_build("tools/tune_encode.py (option debug_skip)", L):
+        sys.exit(2)
     n, w, h = 256, 512, 512
     batches = make_batches(0, n)
     d_imgs = [DeviceBuffer.from_numpy(b) for b in batches]
