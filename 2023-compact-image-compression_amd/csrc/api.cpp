@@ -167,6 +167,7 @@ struct Context {
 	int deflate_fork = 1;   // independent kernels of the DEFLATE pass on a side branch (launch_deflate)
 	int queue_ahead = 1;    // an encode call hands its slot on before it waits for the sizes (encode_batch_impl)
 	int decode_yields = 1;  // decode kernels issued next to an encode wait for the next transform+pack stage to end (cct_decode_batch)
+	int tree_waves = 0;     // option "tree_waves": waves per workgroup of dfl_tree_kernel, 1 or 16; 0 = chosen per pass (deflate_kernels.hip launch_tree)
 	int compact_recs = 1;  // sort records that carry the first five string bytes (slices below 4 MiB; deflate_kernels.hip "Sort records")
 	int enc_slots = 1;  // option "encode_slots": encode batches on the device at a time.  Default 1: on two of the three boxes
 	                    // measured a second batch in flight cost more (each kernel slows down next to another batch's
@@ -768,6 +769,7 @@ int deflate_locked(EncSlot &E, const uint8_t *d_in, size_t in_stride, const uint
 	}
 	a.in = d_in; a.in_stride = in_stride; a.in_sizes = d_in_sizes;
 	dfl_bind(a, base, shape);
+	a.tree_waves = (uint32_t)g_ctx.tree_waves;  // 0: launch_tree and the kernel choose (part of the graph key below)
 	// compact sort records hold a 15-bit hash: memLevel 8 only (deflate_kernels.hip "Sort records").  A compact record for the
 	// 16-bit hash would need a 20-bit position field.  memLevel 9 serves the PNG writer, and on filtered PNG rows compact records
 	// do not pay even at memLevel 8 (61.7 against 61.0 ms per 256 slices at level 6)
@@ -2287,6 +2289,8 @@ const Option OPTIONS[] = {
 	{"decode_yields", &Context::decode_yields, rule_bool},
 	{"queue_ahead", &Context::queue_ahead, rule_bool},
 	{"deflate_fork", &Context::deflate_fork, rule_bool},
+	{"tree_waves", &Context::tree_waves, [](int &v) {
+		return v != 0 && v != 1 && v != 16 ? fail(CCT_E_ARG, "tree_waves must be 0 (automatic), 1 or 16") : CCT_OK; }},
 	{"encode_slots", &Context::enc_slots, [](int &v) { v = std::max(1, std::min(v, N_ENC_SLOTS)); return (int)CCT_OK; }},
 	{"decode_slots", &Context::dec_slots, [](int &v) { v = std::max(1, std::min(v, N_DEC_SLOTS)); return (int)CCT_OK; }},
 	{"inflate_lanes", &Context::inflate_lanes, [](int &v) {

@@ -1257,8 +1257,9 @@ __global__ void __launch_bounds__(256) dfl_symbols_kernel(DeflateArgs a)
 // statistics, code assignment) is done by all 64 lanes, and the tables the serial parts index are staged in LDS (a __constant__ lookup with a
 // per-lane index is a global load: ~10x the latency of an LDS read when nothing hides it).
 // The working set decides how many blocks a CU works on at once (the serial heap replay is pure LDS latency, so
-// resident waves are what hides it): 7.3 KB lets 13 waves share the ~96 KB a CU hands out, which is one wave for every
-// block of a 256-slice batch (13 blocks per slice) in a single round.  Hence the aliasing below: the histogram
+// resident waves are what hides it): just under 8 KB each, so that sixteen of them fit the 160 KB of a CU and a slice's blocks
+// (13 on a bench payload) run as one workgroup on one CU, one wave for every block of a 256-slice batch in a single round
+// (dfl_tree_kernel<16>; measured placement: profiles/tree_placement.log).  Hence the aliasing below: the histogram
 // counters live in the heap array, the length/distance code tables of the histogram phase in dad[], codes are kept for
 // leaves only, the header bits go straight to HBM and the static code lengths are a formula.
 struct TreeScratch {  // one block's working set, in LDS
@@ -1288,7 +1289,15 @@ struct TreeScratch {  // one block's working set, in LDS
 	// dad[] of the literal/length tree is free by then.  token = symbol 0..18 | extra-bits value << 5
 	__device__ __forceinline__ uint16_t *tok() { return dad; }
 };
-static_assert(sizeof(TreeScratch) <= 8192, "13 tree waves per CU: keep the working set around 8 KB");
+static_assert(16 * sizeof(TreeScratch) <= 160 * 1024, "a workgroup of 16 tree waves has to fit the LDS of a CU");
+// A tree wave shares its TreeScratch with no other wave, so what orders its phases is wave-local: the LDS operations of one
+// wave complete in program order, and the compiler is kept to that order.  (A workgroup barrier would hang: waves of one
+// workgroup leave early or work on different trees.)
+__device__ __forceinline__ void tree_wave_sync()
+{
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+}
 static_assert(HEAP_SIZE >= L_CODES + D_CODES, "token list fits dad[]");
 static_assert((HEAP_SIZE + 1) * 4 >= (L_CODES + 2 + D_CODES) * 4 && HEAP_SIZE * 2 >= 768, "aliases fit");
 // tr_static_init's literal/length code lengths (trees.c:255-258)
@@ -1330,7 +1339,7 @@ __device__ __forceinline__ int elems_of(int kind) { return kind == 0 ? L_CODES :
 __device__ void tree_leaves(TreeScratch &S, int kind)
 {
 	const TreeView t = view_of(S, kind);
-	const int lane = threadIdx.x, elems = elems_of(kind);
+	const int lane = threadIdx.x & 63, elems = elems_of(kind);
 	const uint64_t lt_mask = (1ull << lane) - 1ull;
 	int max_code = -1;
 	uint32_t nleaf = 0;
@@ -1361,7 +1370,7 @@ constexpr int TREE_SIFTS = 8;  // at most 5 in flight: one starts every other ti
 __device__ void tree_heap(TreeScratch &S, int kind)
 {
 	const TreeView t = view_of(S, kind);
-	const int lane = threadIdx.x;
+	const int lane = threadIdx.x & 63;
 	int max_code = S.max_code, h = S.heap_len;
 	while (h < 2) {  // (uniform) at least two codes, trees.c:612-621
 		const int node = max_code < 2 ? ++max_code : 0;
@@ -1373,7 +1382,7 @@ __device__ void tree_heap(TreeScratch &S, int kind)
 			else if (kind == 1) S.static_len -= 5;
 		}
 	}
-	__syncthreads();
+	tree_wave_sync();
 	for (int d = 31 - __clz(h >> 1); d >= 0; d--) {  // heapify, deepest inner level first
 		const int lo = 1 << d, hi = min((2 << d) - 1, h >> 1);
 		for (int n0 = lo; n0 <= hi; n0 += 64) {
@@ -1446,7 +1455,7 @@ __device__ void tree_heap(TreeScratch &S, int kind)
 __device__ void tree_depths(TreeScratch &S, int kind)
 {
 	const TreeView t = view_of(S, kind);
-	const int lane = threadIdx.x;
+	const int lane = threadIdx.x & 63;
 	const int max_length = kind == 2 ? MAX_BL_BITS : MAX_BITS;
 	const int base = kind == 0 ? 257 : 0;
 	const int max_code = S.max_code, heap_max = S.heap_max;
@@ -1458,7 +1467,7 @@ __device__ void tree_depths(TreeScratch &S, int kind)
 	for (int h = heap_max + 1 + lane; h < HEAP_SIZE; h += 64) t.len[S.heap[h] & 1023u] = UNKNOWN;
 	if (lane == 0) t.len[root & 1023u] = 0;
 	if (lane <= MAX_BITS) S.bl_count[lane] = 0;
-	__syncthreads();
+	tree_wave_sync();
 	for (bool again = true; again;) {
 		again = false;
 		for (int h0 = heap_max + 1; h0 < HEAP_SIZE; h0 += 64) {
@@ -1474,7 +1483,7 @@ __device__ void tree_depths(TreeScratch &S, int kind)
 			}
 			if (__ballot(unknown)) again = true;
 		}
-		__syncthreads();
+		tree_wave_sync();
 	}
 	int overflow = 0;
 	for (int h0 = heap_max + 1; h0 < HEAP_SIZE; h0 += 64) {
@@ -1535,7 +1544,7 @@ __device__ void tree_fix(TreeScratch &S, int kind)
 __device__ void tree_codes(TreeScratch &S, int kind)
 {
 	const TreeView t = view_of(S, kind);
-	const int lane = threadIdx.x, max_code = S.max_code;
+	const int lane = threadIdx.x & 63, max_code = S.max_code;
 	const uint64_t lt_mask = (1ull << lane) - 1ull;
 	uint32_t seen[MAX_BITS + 1];
 #pragma unroll
@@ -1567,7 +1576,7 @@ __device__ void tree_codes(TreeScratch &S, int kind)
 // header is written) and moved to bfreq by the caller.
 __device__ void scan_tree_wave(TreeScratch &S, const TreeView &t, int max_code)
 {
-	const int lane = threadIdx.x;
+	const int lane = threadIdx.x & 63;
 	constexpr int NCH = (L_CODES + 63) / 64;  // 5 chunks of 64 positions
 	const int n_el = max_code + 1;
 	uint32_t v[NCH];
@@ -1651,7 +1660,7 @@ __device__ __forceinline__ void hdr_or(TreeScratch &S, uint32_t pos, uint32_t va
 // bit-length alphabet in bl_order, then the tokens scan_tree recorded, each at its prefix-summed bit offset
 __device__ void send_header(TreeScratch &S)
 {
-	const int lane = threadIdx.x;
+	const int lane = threadIdx.x & 63;
 	const int nbl = S.max_blindex + 1;
 	if (lane == 0) hdr_or(S, 0, (uint32_t)(S.lmax + 1 - 257) | ((uint32_t)(S.dmax + 1 - 1) << 5) | ((uint32_t)(nbl - 4) << 10), 14);
 	if (lane < nbl) hdr_or(S, 14u + 3u * (uint32_t)lane, S.blen[S.bl_order[lane]], 3);
@@ -1675,11 +1684,6 @@ __device__ void send_header(TreeScratch &S)
 	if (lane == 0) S.hdr_nbits = base;
 }
 
-// One wave per TREE_BLOCKS consecutive blocks of a slice: histograms + trees (trees.c _tr_flush_block).  The serial
-// parts of a block (overflow repair, block type) run on lane q for block m0 + q; the heap replay and the parallel parts
-// take the blocks in turn.
-constexpr int TREE_BLOCKS = 1;
-
 // Absolute position of window[0] at the top of the loop iteration at position `top` (deflate.c fill_window).  The window
 // holds 64 KiB; fill_window runs once the lookahead is <= lam (deflate_slow: < MIN_LOOKAHEAD, deflate_rle: <= MAX_MATCH,
 // deflate_huff: 0) and slides it by 32 KiB when strstart >= 32768 + MAX_DIST.  While input is left the window is full after
@@ -1694,25 +1698,78 @@ __device__ __forceinline__ uint32_t window_base(uint32_t top, uint32_t L, uint32
 	if (k == kf && 32768u * k + (uint32_t)(WSIZE + MAX_DIST) <= top && L <= top + lam) k++;
 	return 32768u * k;
 }
-__global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
+#ifdef CCT_TREE_PROF
+// tuning builds only (tools/debug/tree_prof.sh): where and when every tree wave that has a block ran.  One record per
+// (slice, block), written by lane 0 at the wave's exit; the buffer belongs to the library (a capture allocates nothing), the
+// tool clears it before the call it looks at and reads it afterwards.  No other code reads it.
+struct TreeProbe { uint32_t hw_id, xcc_id, slice, block; uint64_t rt0, rt1, cycles; };  // rt*: s_memrealtime (100 MHz), cycles: s_memtime delta
+constexpr int TREE_PROBE_CAP = 16384;
+__device__ TreeProbe g_tree_probe[TREE_PROBE_CAP];
+extern "C" int cct_tree_prof_reset()
 {
-	__shared__ TreeScratch S4[TREE_BLOCKS];
-	const int s = blockIdx.y, m0 = blockIdx.x * TREE_BLOCKS, lane = threadIdx.x;
-	const uint32_t T = a.total_syms[s];
-	const uint32_t L = a.in_sizes[s];
-	// number of blocks: one flush per 16383 (32767) tallied symbols inside the loop, plus the final flush
-	const uint32_t BS = a.block_syms;
+	void *p;
+	if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_tree_probe)) != hipSuccess) return -1;
+	return hipMemset(p, 0, sizeof(TreeProbe) * TREE_PROBE_CAP) == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+extern "C" int cct_tree_prof_read(void *out, int cap)  // -> records copied (32 bytes each; rt1 == 0: no wave wrote it)
+{
+	const int n = cap < TREE_PROBE_CAP ? cap : TREE_PROBE_CAP;
+	if (hipDeviceSynchronize() != hipSuccess) return -1;
+	return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tree_probe), sizeof(TreeProbe) * (size_t)n) == hipSuccess ? n : -1;
+}
+#define TREE_PROBE_ENTER() const uint64_t prt0 = __builtin_amdgcn_s_memrealtime(), pmt0 = __builtin_amdgcn_s_memtime()
+#define TREE_PROBE_EXIT(s_, m_, max_blocks_) do { \
+		const uint64_t pmt1 = __builtin_amdgcn_s_memtime(), prt1 = __builtin_amdgcn_s_memrealtime(); \
+		const uint32_t pidx = (uint32_t)(s_) * (uint32_t)(max_blocks_) + (uint32_t)(m_); \
+		if (lane == 0 && pidx < (uint32_t)TREE_PROBE_CAP) \
+			g_tree_probe[pidx] = TreeProbe{(uint32_t)__builtin_amdgcn_s_getreg(4 | (31 << 11)) /* HW_ID */, \
+			                               (uint32_t)__builtin_amdgcn_s_getreg(20 | (31 << 11)) /* XCC_ID */, \
+			                               (uint32_t)(s_), (uint32_t)(m_), prt0, prt1, pmt1 - pmt0}; \
+	} while (0)
+#else
+#define TREE_PROBE_ENTER() do {} while (0)
+#define TREE_PROBE_EXIT(s_, m_, max_blocks_) do {} while (0)
+#endif
+// DEFLATE blocks of slice s: one flush per 16383 (32767) tallied symbols inside the loop, plus the final flush
+__device__ __forceinline__ uint32_t tree_nblocks(const DeflateArgs &a, int s)
+{
+	const uint32_t T = a.total_syms[s], BS = a.block_syms;
 	uint32_t nfull = T / BS;
 	// the post-loop literal never flushes (deflate_slow only: deflate_huff and deflate_rle have none, and there a symbol count that
 	// is a multiple of the block size ends the stream with an empty final block)
 	if (T % BS == 0 && nfull > 0 && !short_pass(a.strategy) && a.postloop_lit[s]) nfull--;
-	const uint32_t nblocks = nfull + 1;
+	return nfull + 1;
+}
+// One wave per block: histograms + trees (trees.c _tr_flush_block); lane 0 runs the serial parts (overflow repair, block type).
+// A workgroup is WAVES waves of one slice, each with a TreeScratch of its own: wave w of workgroup (s, c) takes block
+// c * WAVES + w of slice s, and a wave whose block does not exist leaves at once.  The waves share nothing, so nothing in
+// here or below may be a workgroup barrier (tree_wave_sync).  WAVES = 16 claims the LDS of a whole CU for the slice; slices
+// are the fast grid index (launch_tree).
+// a.tree_waves == 0: both instantiations are launched and the waves that have a block choose, all alike, from what only the
+// device knows, the blocks of every slice: sixteen waves per workgroup where the workgroups that have a block then fit the
+// CUs in one round (a 16-wave workgroup has a CU to itself, whatever its slice holds: launch_tree), one wave otherwise
+template <int WAVES>
+__global__ void __launch_bounds__(64 * WAVES) dfl_tree_kernel(DeflateArgs a, uint32_t cus)
+{
+	extern __shared__ __attribute__((aligned(16))) uint8_t tree_lds[];  // WAVES * sizeof(TreeScratch)
+	const int wave = WAVES == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (uniform, and known to be)
+	const int s = blockIdx.x, n = gridDim.x, m = blockIdx.y * WAVES + wave, lane = threadIdx.x & 63;
+	TreeScratch &S = reinterpret_cast<TreeScratch *>(tree_lds)[wave];
+	const uint32_t T = a.total_syms[s];
+	const uint32_t L = a.in_sizes[s];
+	const uint32_t BS = a.block_syms;
+	const uint32_t nblocks = tree_nblocks(a, s);
 	BlockMeta *meta = a.block_meta + (size_t)s * a.max_blocks;
-	if ((uint32_t)m0 >= nblocks) return;
-	const int nb = (int)min((uint32_t)TREE_BLOCKS, nblocks - (uint32_t)m0);
+	if ((uint32_t)m >= nblocks) return;  // (wave-uniform)
+	if (a.tree_waves == 0) {
+		uint32_t wgs = 0;  // workgroups of sixteen waves that have a block
+		for (int i = lane; i < n; i += 64) wgs += (tree_nblocks(a, i) + 15u) / 16u;
+		wgs = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum(wgs));
+		if ((wgs <= cus ? 16 : 1) != WAVES) return;
+	}
 	const uint32_t *bend = a.blk_end + (size_t)s * a.max_blocks;
-	const bool owner = lane < nb;  // lane q runs the serial parts of block m0 + q
-#ifdef CCT_TREE_PROF  // tuning builds only: phase times of one workgroup
+	TREE_PROBE_ENTER();
+#ifdef CCT_TREE_PROF  // tuning builds only: phase times of one wave
 	long long tp[16]; int tpi = 0;
 #define TREE_STAMP() do { if (tpi < 16) tp[tpi++] = clock64(); } while (0)
 #else
@@ -1720,12 +1777,10 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 #endif
 	TREE_STAMP();
 
-	for (int q = 0; q < nb; q++) {
-		TreeScratch &S = S4[q];
-		const int m = m0 + q;
-		const bool last = (uint32_t)m == nblocks - 1;
-		const uint32_t first = (uint32_t)m * BS;
-		const uint32_t nsym = last ? T - first : BS;
+	const bool last = (uint32_t)m == nblocks - 1;
+	const uint32_t first = (uint32_t)m * BS;
+	const uint32_t nsym = last ? T - first : BS;
+	{
 		const uint32_t *sym = a.sym + (size_t)s * a.in_stride + first;
 		for (int i = lane; i < HEAP_SIZE; i += 64) { S.freq[i] = 0; S.len[i] = 0; }
 		for (int i = lane; i < L_CODES + 2; i += 64) S.code[i] = 0;
@@ -1754,7 +1809,7 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		uint32_t *hl = S.hist_l(), *hd = S.hist_d();
 		for (int i = lane; i < L_CODES; i += 64) hl[i] = 0;
 		if (lane < D_CODES) hd[lane] = 0;
-		__syncthreads();
+		tree_wave_sync();
 		// sixteen loads in flight (one wave per block, nothing else hides HBM latency), and the next sixteen requested before
 		// these are counted: the index is clamped instead of tested so that the loads carry no branch
 		{
@@ -1781,55 +1836,47 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 				}
 			}
 		}
-		__syncthreads();
+		tree_wave_sync();
 		for (int i = lane; i < L_CODES; i += 64) S.freq[i] = (uint16_t)hl[i];
 		if (lane < D_CODES) S.dfreq[lane] = (uint16_t)hd[lane];
 		for (int i = lane; i < 160; i += 64) S.hdr_bits[i] = 0;
 		if (lane == 0) { S.opt_len = 0; S.static_len = 0; S.hdr_nbits = 0; S.ntok = 0; S.btype = 0; S.max_blindex = 0; }
-		__syncthreads();
+		tree_wave_sync();
 		if (lane == 0) S.freq[END_BLOCK] = 1;
 		for (int i = lane; i < HEAP_SIZE; i += 64) S.dad[i] = 0;  // held the code tables of the histogram
 	}
-	__syncthreads();
+	tree_wave_sync();
 	TREE_STAMP();
 #pragma unroll 1
 	for (int kind = 0; kind < 3; kind++) {  // literal/length, distance, then the bit-length tree over both
 		if (kind == 2) {
-			if (owner) S4[lane].dyn_body_bits = S4[lane].opt_len;  // code + extra bits of all symbols and END_BLOCK
-			__syncthreads();
-			for (int q = 0; q < nb; q++) {
-				TreeScratch &S = S4[q];
-				scan_tree_wave(S, view_of(S, 0), S.lmax);
-				__syncthreads();  // (the token count of the first sequence is the base of the second)
-				scan_tree_wave(S, view_of(S, 1), S.dmax);
-				__syncthreads();
-				if (lane < BL_CODES) { S.bfreq[lane] = (uint16_t)S.hdr_bits[lane]; S.hdr_bits[lane] = 0; }
-			}
-			__syncthreads();
+			if (lane == 0) S.dyn_body_bits = S.opt_len;  // code + extra bits of all symbols and END_BLOCK
+			tree_wave_sync();
+			scan_tree_wave(S, view_of(S, 0), S.lmax);
+			tree_wave_sync();  // (the token count of the first sequence is the base of the second)
+			scan_tree_wave(S, view_of(S, 1), S.dmax);
+			tree_wave_sync();
+			if (lane < BL_CODES) { S.bfreq[lane] = (uint16_t)S.hdr_bits[lane]; S.hdr_bits[lane] = 0; }
+			tree_wave_sync();
 		}
-		for (int q = 0; q < nb; q++) tree_leaves(S4[q], kind);
-		__syncthreads();
+		tree_leaves(S, kind);
+		tree_wave_sync();
 		TREE_STAMP();
-		for (int q = 0; q < nb; q++) tree_heap(S4[q], kind);
-		__syncthreads();
+		tree_heap(S, kind);
+		tree_wave_sync();
 		TREE_STAMP();
-		for (int q = 0; q < nb; q++) tree_depths(S4[q], kind);
-		__syncthreads();
-		if (owner) {
-			tree_fix(S4[lane], kind);
-			if (kind == 0) S4[lane].lmax = S4[lane].max_code; else if (kind == 1) S4[lane].dmax = S4[lane].max_code;
+		tree_depths(S, kind);
+		tree_wave_sync();
+		if (lane == 0) {
+			tree_fix(S, kind);
+			if (kind == 0) S.lmax = S.max_code; else if (kind == 1) S.dmax = S.max_code;
 		}
-		__syncthreads();
-		for (int q = 0; q < nb; q++) tree_codes(S4[q], kind);
-		__syncthreads();
+		tree_wave_sync();
+		tree_codes(S, kind);
+		tree_wave_sync();
 		TREE_STAMP();
 	}
-	if (owner) {
-		TreeScratch &S = S4[lane];
-		const int m = m0 + lane;
-		const bool last = (uint32_t)m == nblocks - 1;
-		const uint32_t first = (uint32_t)m * BS;
-		const uint32_t nsym = last ? T - first : BS;
+	if (lane == 0) {
 		const uint32_t in_begin = m == 0 ? 0u : bend[m - 1];
 		const uint32_t in_end = last ? L : bend[m];
 		int max_blindex;
@@ -1858,32 +1905,27 @@ __global__ void __launch_bounds__(64) dfl_tree_kernel(DeflateArgs a)
 		meta[m] = bm;
 		if (m == 0) a.n_blocks[s] = nblocks;
 	}
-	__syncthreads();
-	for (int q = 0; q < nb; q++) {
-		TreeScratch &S = S4[q];
-		if (S.btype != 2) continue;  // (uniform)
+	tree_wave_sync();
+	BlockTables *bt = a.block_tables + ((size_t)s * a.max_blocks + m);
+	if (S.btype == 2) {  // (uniform)
 		send_header(S);
-		__syncthreads();
-		BlockTables *bt = a.block_tables + ((size_t)s * a.max_blocks + m0 + q);
+		tree_wave_sync();
 		for (int i = lane; i * 32 < (int)S.hdr_nbits; i += 64) bt->hdr_bits[i] = S.hdr_bits[i];
-		if (lane == 0) meta[m0 + q].hdr_nbits = S.hdr_nbits;
+		if (lane == 0) meta[m].hdr_nbits = S.hdr_nbits;
 	}
-	__syncthreads();
+	tree_wave_sync();
 	TREE_STAMP();
 #ifdef CCT_TREE_PROF
-	if (s == 0 && m0 == 0 && lane == 0) {
-		printf("[tree prof] nb=%d:", nb);
+	if (s == 0 && m == 0 && lane == 0) {
+		printf("[tree prof] waves=%d:", WAVES);
 		for (int i = 1; i < tpi; i++) printf(" %lld", tp[i] - tp[i - 1]);
 		printf("  (hist | leaves0 heap0 rest0 | scan+leaves1 heap1 rest1 | scan_tree+leaves2 heap2 rest2 | final)\n");
 	}
 #endif
 	// publish the code tables for the emit kernel
-	for (int q = 0; q < nb; q++) {
-		TreeScratch &S = S4[q];
-		BlockTables *bt = a.block_tables + ((size_t)s * a.max_blocks + m0 + q);
-		for (int i = lane; i < L_CODES; i += 64) { bt->lcode[i] = S.code[i]; bt->llen[i] = (uint8_t)S.len[i]; }
-		if (lane < D_CODES) { bt->dcode[lane] = S.dcode[lane]; bt->dlen[lane] = (uint8_t)S.dlen[lane]; }
-	}
+	for (int i = lane; i < L_CODES; i += 64) { bt->lcode[i] = S.code[i]; bt->llen[i] = (uint8_t)S.len[i]; }
+	if (lane < D_CODES) { bt->dcode[lane] = S.dcode[lane]; bt->dlen[lane] = (uint8_t)S.dlen[lane]; }
+	TREE_PROBE_EXIT(s, m, a.max_blocks);
 }
 
 // ------------------------------------------------------------------ 5. Adler-32 + layout
@@ -2276,6 +2318,7 @@ bool deflate_mem_level_args(int mem_level, DeflateArgs &a)
 	return true;
 }
 
+static int g_tree_cus = 0;  // CUs of the device (deflate_init_tables; launch_tree)
 // host: trees.c tr_static_init tables -> constant memory
 hipError_t deflate_init_tables()
 {
@@ -2318,7 +2361,41 @@ hipError_t deflate_init_tables()
 	if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_static_lcode), static_lcode, sizeof static_lcode)) != hipSuccess) return e;
 	if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_static_llen), static_llen, sizeof static_llen)) != hipSuccess) return e;
 	if ((e = hipMemcpyToSymbol(HIP_SYMBOL(c_static_dcode), static_dcode, sizeof static_dcode)) != hipSuccess) return e;
-	return hipSuccess;
+	// (once per process, not per launch: launch_tree)
+	int dev;
+	if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+	if ((e = hipDeviceGetAttribute(&g_tree_cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+	return hipFuncSetAttribute(reinterpret_cast<const void *>(dfl_tree_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+	                           (int)(16 * sizeof(TreeScratch)));
+}
+
+// The tree kernel at a.tree_waves waves per workgroup, slices the fast grid index (dfl_tree_kernel).  Sixteen waves are faster
+// where they apply and much slower where they do not: a workgroup of sixteen claims the LDS of a whole CU, so a CU holds as
+// many tree waves as that chunk of its slice has blocks (one wave per workgroup: up to 20), and the workgroups that have a
+// block must fit the CUs in one round.  Measured, dfl_tree_kernel in us at 1 / 16 waves (profiles/tree_placement.log):
+// 256 slices of 13 blocks 375 / 357, of 2 blocks 278 / 280; 300 slices of 13 blocks 382 / 700; 512 slices of 52 blocks
+// 1965 / 2644; 2048 slices of 1 block 214 / 1358; and with few slices thirteen waves on each of a few CUs lose to one or two on
+// many, 64 slices of 13 blocks 324 / 334 (128: 359 / 337).  So, for a.tree_waves == 0: one wave below TREE_WAVES16_MIN_SLICES
+// and above one slice per CU, where sixteen cannot win; in between the device chooses, because only it knows how many blocks
+// the slices have (the host knows max_blocks, a bound from the stride that is 34 where the bench payloads have 13): both
+// instantiations are launched and the one not chosen leaves at once.  launch_deflate refuses any value but 0, 1 and 16
+// before it launches a kernel; the LDS limit of dfl_tree_kernel<16> is raised once, by deflate_init_tables.
+constexpr int TREE_WAVES16_MIN_SLICES = 128;
+template <int WAVES>
+static void launch_tree_waves(const DeflateArgs &a, int n, hipStream_t st)
+{
+	// slices are the fast grid index: the workgroups that have blocks then follow each other in dispatch order whatever
+	// max_blocks is.  (Blocks first for the one-wave kernel where there are more slices than CUs, the order it used to have,
+	// was tried and gained nothing: 300 slices of 13 blocks 501 us against 386, 2048 of 3 blocks 687 against 692.)
+	hipLaunchKernelGGL(dfl_tree_kernel<WAVES>, dim3(n, (a.max_blocks + WAVES - 1) / WAVES), dim3(64 * WAVES),
+	                   WAVES * sizeof(TreeScratch), st, a, (uint32_t)g_tree_cus);
+}
+static void launch_tree(const DeflateArgs &a0, int n, hipStream_t st)
+{
+	DeflateArgs a = a0;
+	if (a.tree_waves == 0 && (n < TREE_WAVES16_MIN_SLICES || n > g_tree_cus)) a.tree_waves = 1;
+	if (a.tree_waves != 1) launch_tree_waves<16>(a, n, st);
+	if (a.tree_waves != 16) launch_tree_waves<1>(a, n, st);
 }
 
 // One DEFLATE pass.  `side` + `ev` (four events without timing), when given, let kernels that do not depend on each other share
@@ -2353,7 +2430,7 @@ static hipError_t launch_deflate_short(const DeflateArgs &a, int n, hipStream_t 
 		else hipLaunchKernelGGL(dfl_huff_symbols_kernel<BLOCK_SYMS>, dim3(gx, n), dim3(256), 0, st, a);
 	}
 	hipLaunchKernelGGL(dfl_adler_kernel, dim3(n), dim3(256), 0, st, a);
-	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
+	launch_tree(a, n, st);
 	hipLaunchKernelGGL(dfl_layout_kernel, dim3(n), dim3(64), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_emit_kernel, dim3(a.max_blocks, n), dim3(256), 0, st, a);
 	return hipGetLastError();
@@ -2366,6 +2443,7 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, hipStream_t st, hipStream
 	if ((a.hash_bits != 15 && !ml9) || a.block_syms != (uint32_t)(ml9 ? BLOCK_SYMS_ML9 : BLOCK_SYMS)) return hipErrorInvalidValue;
 	if (ml9 && a.pos_mask != 0xFFFFFFFFu) return hipErrorInvalidValue;  // memLevel 9: wide records only ("Sort records")
 	if ((a.out_stride & 3) || ((uintptr_t)a.out & 3)) return hipErrorInvalidValue;
+	if (a.tree_waves != 0 && a.tree_waves != 1 && a.tree_waves != 16) return hipErrorInvalidValue;
 	if (short_pass(a.strategy)) return launch_deflate_short(a, n, st);
 	hipLaunchKernelGGL(dfl_offsets_kernel, dim3(64), dim3(256), 0, st, a, n);  // (also zeroes sort_hist and run_counts)
 	const int gx = (int)std::min<size_t>(64, (a.in_stride + 255) / 256);
@@ -2425,7 +2503,7 @@ hipError_t launch_deflate(const DeflateArgs &a, int n, hipStream_t st, hipStream
 	hipLaunchKernelGGL(dfl_walk_kernel, dim3(n), dim3(WALK_T), 0, st, a, n);
 	if (ml9) hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS_ML9>, dim3(gx, n), dim3(256), 0, st, a);
 	else hipLaunchKernelGGL(dfl_symbols_kernel<BLOCK_SYMS>, dim3(gx, n), dim3(256), 0, st, a);
-	hipLaunchKernelGGL(dfl_tree_kernel, dim3((a.max_blocks + TREE_BLOCKS - 1) / TREE_BLOCKS, n), dim3(64), 0, st, a);
+	launch_tree(a, n, st);
 	hipLaunchKernelGGL(dfl_layout_kernel, dim3(n), dim3(64), 0, st, a, n);
 	hipLaunchKernelGGL(dfl_emit_kernel, dim3(a.max_blocks, n), dim3(256), 0, st, a);
 	return hipGetLastError();

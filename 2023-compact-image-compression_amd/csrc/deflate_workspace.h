@@ -58,6 +58,8 @@ struct DeflateArgs {
 	uint32_t strategy, min_len;
 	// the zlib memLevel (8 or 9): hash bits (memLevel + 7) and symbols per block (lit_bufsize - 1)
 	uint32_t hash_bits, block_syms;
+	// waves per workgroup of dfl_tree_kernel, 1 or 16, or 0: chosen per pass (option "tree_waves"; deflate_kernels.hip launch_tree)
+	uint32_t tree_waves;
 };
 
 // ---- shared constants ------------------------------------------------------------------------------

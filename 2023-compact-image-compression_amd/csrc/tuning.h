@@ -17,7 +17,8 @@
 //   CCT_TRACE             api.cpp: host timings of every encode and decode call on stderr
 //
 // Apart from these: -DCCT_TREE_PROF (deflate_kernels.hip, tools/debug/tree_prof.sh) stays a flag of its own.  Its stamps
-// are always on once compiled and would perturb the DEFLATE timings the switches above are used to take.
+// and its placement records (where and when every tree wave ran: tools/debug/tree_placement.py) are always on once
+// compiled and would perturb the DEFLATE timings the switches above are used to take.
 #pragma once
 #include <stdlib.h>
 

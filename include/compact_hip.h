@@ -584,6 +584,9 @@ int cct_last_timings(float *out6);
  * `make -C 2023-compact-image-compression_amd/csrc tuning`): this library has none to set. */
 int cct_set_option(const char *key, int value);
 int cct_get_option(const char *key, int *value);
+/* A further tuning key, "tree_waves": waves per workgroup of the DEFLATE tree kernel, 1 or 16, or 0 = chosen per pass (16 where
+ * a batch of 128 slices or more, at most one per CU, has blocks for no more 16-wave workgroups than the device has CUs;
+ * DESIGN.md 5); anything else is refused.  The streams are the same at every value (tests/test_gpu_tree_placement.py). */
 
 #ifdef __cplusplus
 }
