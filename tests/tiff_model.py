@@ -126,14 +126,14 @@ def lzw_decode(data, want):
     out, j, start, length = bytearray(), 0, [], []
     while len(out) < want:                          # decoding stops once the strip's bytes are out: the rest is ignored
         j += 1
-        if j > MAX_J:
-            return "CCT_E_STREAM", None             # the table is full and no Clear came
         c = get(width(j))
         if c is None or c == EOI:
             return "CCT_E_STREAM", None             # the data or an EOI ends the strip early
         if c == CLEAR:                              # repeated Clears are allowed
             j, start, length = 0, [], []
             continue
+        if j > MAX_J:
+            return "CCT_E_STREAM", None             # the table is full and no Clear came: code 4863 may still be that Clear
         if c < 256:
             s = bytes([c])
         else:
