@@ -33,6 +33,17 @@
 #include "wave_device.h"
 #include "../../include/compact_hip.h"
 
+// Two seams for the host emulation (tools/debug/inflate_host_emu), which compiles this file with a C++ compiler: where the
+// launch's dynamic LDS comes from, and a gap behind every array of the LDS structs.  On the device the gap is nothing, so the
+// structs keep their layout (asserted below InfShared); the emulation makes it 64 bytes that it fills, poisons and checks.
+#ifndef CCT_INF_DYNAMIC_LDS
+#define CCT_INF_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) uint8_t name[]
+#endif
+#ifndef CCT_INF_LDS_GAP
+#define CCT_INF_LDS_GAP(after)
+#define CCT_INF_LDS_PLAIN 1
+#endif
+
 namespace cct {
 namespace {
 
@@ -92,31 +103,43 @@ constexpr int CL_BITS = 7;  // code-length codes are at most 7 bits long: one fl
 
 // canonical code description, see "canonical Huffman codes" below
 struct CanonLds {
-	uint32_t lim[16], adj[16], offs[16];
+	uint32_t lim[16]; CCT_INF_LDS_GAP(lim)
+	uint32_t adj[16]; CCT_INF_LDS_GAP(adj)
+	uint32_t offs[16]; CCT_INF_LDS_GAP(offs)
 };
 
 template <class G>
 struct InfShared {
 	static constexpr int NT = G::NT, NWV = G::NWV, INF_IN = G::INF_IN;
-	uint8_t ring[INF_RING];
-	alignas(16) uint8_t inbuf[INF_IN];
+	uint8_t ring[INF_RING]; CCT_INF_LDS_GAP(ring)
+	alignas(16) uint8_t inbuf[INF_IN]; CCT_INF_LDS_GAP(inbuf)
 	// root decode tables (LL_BITS / D_BITS); entry layout at ll_entry() below; 0 = no code of root length or less
-	uint32_t ll_tab[1 << LL_BITS], d_tab[1 << D_BITS];
+	// no gap between the two: cl_sequence lays its ranking arrays over both as one stretch
+	uint32_t ll_tab[1 << LL_BITS];
+	uint32_t d_tab[1 << D_BITS]; CCT_INF_LDS_GAP(d_tab)
 	CanonLds ll_canon, d_canon;                 // ll_canon doubles as the code-length code's while a header is parsed
-	uint32_t ll_sent[288], d_sent[32];          // entry of every coded symbol by (length, symbol)
-	uint8_t chunkcnt[5 * 16];                   // table build: codes of every length in each chunk of 64 symbols
-	uint32_t cnt[16];
-	uint8_t cl_tab[1 << CL_BITS];               // symbol << 3 | code length, 0 = no such code
-	uint8_t lens[320];
-	uint2 mlist[MLIST_CAP];                     // x = destination, y = length | (distance - 1) << 9
-	uint16_t lbase[29], dbase[30];
-	uint8_t lext[29], dext[30];
+	uint32_t ll_sent[288]; CCT_INF_LDS_GAP(ll_sent)  // entry of every coded symbol by (length, symbol)
+	uint32_t d_sent[32]; CCT_INF_LDS_GAP(d_sent)
+	uint8_t chunkcnt[5 * 16]; CCT_INF_LDS_GAP(chunkcnt)  // table build: codes of every length in each chunk of 64 symbols
+	uint32_t cnt[16]; CCT_INF_LDS_GAP(cnt)
+	uint8_t cl_tab[1 << CL_BITS]; CCT_INF_LDS_GAP(cl_tab)  // symbol << 3 | code length, 0 = no such code
+	uint8_t lens[320]; CCT_INF_LDS_GAP(lens)
+	uint2 mlist[MLIST_CAP]; CCT_INF_LDS_GAP(mlist)  // x = destination, y = length | (distance - 1) << 9
+	uint16_t lbase[29]; CCT_INF_LDS_GAP(lbase)
+	uint16_t dbase[30]; CCT_INF_LDS_GAP(dbase)
+	uint8_t lext[29]; CCT_INF_LDS_GAP(lext)
+	uint8_t dext[30]; CCT_INF_LDS_GAP(dext)
 	// round state
-	uint32_t land[NT];                          // landing position of every lane, bits from the round's origin
-	uint32_t wsum_b[NWV], wsum_m[NWV], wred[2 * NWV];
-	uint32_t rres[4];                           // result of the round: bytes, copies, landing position, flags of its last lane
+	uint32_t land[NT]; CCT_INF_LDS_GAP(land)    // landing position of every lane, bits from the round's origin
+	uint32_t wsum_b[NWV]; CCT_INF_LDS_GAP(wsum_b)
+	uint32_t wsum_m[NWV]; CCT_INF_LDS_GAP(wsum_m)
+	uint32_t wred[2 * NWV]; CCT_INF_LDS_GAP(wred)
+	uint32_t rres[4]; CCT_INF_LDS_GAP(rres)     // result of the round: bytes, copies, landing position, flags of its last lane
 	int ok;
 };
+#ifdef CCT_INF_LDS_PLAIN
+static_assert(sizeof(InfShared<Geo<512>>) == 139808 && sizeof(InfShared<Geo<256>>) == 122336, "the gap macro leaves the device layout alone");
+#endif
 
 struct BitReader {    // workgroup-uniform reader used for headers; every lane holds the same state
 	const uint8_t *src;   // 16-byte aligned base of the staged stream
@@ -187,7 +210,7 @@ __device__ __forceinline__ bool canon_from_counts(const uint32_t *cnt, CanonLds 
 	c.lim[0] = 0; c.adj[0] = 0; c.offs[0] = 0;
 	for (int len = 1; len <= 15; len++) {
 		const uint32_t cn = cnt[len];
-		left = (left << 1) - (int)cn;
+		left = left * 2 - (int)cn;  // not `left << 1`: `left` is negative from the first over-subscribed length on, and C++17 leaves that shift undefined
 		if (left < 0) ok = false;
 		if (cn) maxlen = len;
 		c.lim[len] = ok ? (code + cn) << (15 - len) : 0u;
@@ -605,7 +628,7 @@ __global__ void __launch_bounds__(G::NT) inflate_kernel(InflateArgs a, uint64_t 
 	uint64_t prof[P_N] = {};
 	long long tprev = PROF ? clock64() : 0;
 	const long long tstart = tprev;
-	extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+	CCT_INF_DYNAMIC_LDS(smem_raw);
 	InfShared<G> &S = *reinterpret_cast<InfShared<G> *>(smem_raw);
 	const int s = blockIdx.x;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

@@ -11,6 +11,10 @@
 #include "cct_internal.h"
 #include "png_device.h"
 
+#ifndef CCT_PNG_DYNAMIC_LDS  // the host emulation (tools/debug/inflate_host_emu) supplies the launch's bytes its own way
+#define CCT_PNG_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) uint8_t name[]
+#endif
+
 namespace cct {
 namespace {
 
@@ -200,7 +204,7 @@ __device__ void unfilter_image(const PngUnfilterArgs &a, int img, uint8_t *lds)
 // One workgroup per image.  A file that has failed so far, or whose stream did not inflate to exactly its rows, is left alone.
 __global__ void __launch_bounds__(512) png_unfilter_kernel(PngUnfilterArgs a)
 {
-	extern __shared__ __attribute__((aligned(16))) uint8_t uf_lds[];
+	CCT_PNG_DYNAMIC_LDS(uf_lds);
 	const int img = blockIdx.x;
 	const uint32_t bpp = a.bpp[img] == 1 ? 1u : 2u;
 	const uint32_t want = (uint32_t)a.nrows * (1u + (uint32_t)a.cols * bpp);

@@ -7,6 +7,7 @@
 // Bounds: a device allocation is a malloc of its own, and what DevBuf::ensure adds on top of the bytes the caller asked for is
 // poisoned, so AddressSanitizer reports the first byte behind every buffer; the LDS of a launch is a malloc of exactly the
 // launch's bytes.  Slow (a thread per lane): small shapes.  It checks the algorithm and the bounds, not the timing.
+#define EMU_OWN_HOST_RUNTIME  // the host side of the runtime is this file's (below), not the shim's
 #include "emu_common.h"
 #include <sanitizer/asan_interface.h>
 static uint32_t *g_dyn_lds;

@@ -11,7 +11,6 @@ static inline uint32_t atomicMin(uint32_t *p, uint32_t v)
 	while (v < o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
 	return o;
 }
-static inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 #include "../../../2023-compact-image-compression_amd/csrc/jpeg_ls_kernels.hip"
 using namespace cct;
 // params: 9 uint32 (maxval range qbpp limit a0 reset t1 t2 t3), as tests/jpeg_ls_model.py Params has them
