@@ -128,6 +128,8 @@ _SIGS = {
                                        C.c_size_t, C.c_void_p]),
     "cct_jpegll_encode_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_void_p]),
+    "cct_jpegll_encode_batch_sv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cct_jpegll_info": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cct_jpegll_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                           C.c_size_t, C.c_void_p]),

@@ -795,14 +795,31 @@ def _check_jpl_shape(rows, cols, what="JPEG Lossless"):
         raise ValueError(f"{what} frame of {rows} x {cols} samples: more than {_JPL_MAX_PIXELS} pixels")
 
 
-def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=None, dtype=None):
-    """JPEG Lossless frames with selection value 1 (DICOM transfer syntax 1.2.840.10008.1.2.4.70) on the device: a uint16 or
+def _check_jpl_predictor(predictor):
+    """selection value 1 .. 7, or 0 for "auto" / 0; TypeError for what is neither an integer nor a string, ValueError else"""
+    if isinstance(predictor, str):
+        if predictor != "auto":
+            raise ValueError(f"JPEG Lossless predictor {predictor!r}: 1 to 7, or 'auto'")
+        return 0
+    predictor, = _ints(predictor=predictor)
+    if not 0 <= predictor <= 7:
+        raise ValueError(f"JPEG Lossless predictor {predictor}: 1 to 7, or 'auto' (0)")
+    return predictor
+
+
+def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=None, dtype=None, predictor=1):
+    """JPEG Lossless frames on the device, with selection value 1 unless predictor says otherwise (DICOM transfer syntax
+    1.2.840.10008.1.2.4.70; any other predictor: 1.2.840.10008.1.2.4.57): a uint16 or
     uint8 array of shape (n, rows, cols) or (rows, cols), or a DeviceBuffer with shape= given (dtype= np.uint16 unless
     np.uint8 is named), -> a list of n `bytes`, each one interchange file: SOI, SOF3, DHT, DRI (with restart_rows > 0: a
     restart interval of that many rows, at most 65535 samples), SOS, entropy-coded segment, EOI.  precision is 2 .. 16 and
     defaults to the sample width; uint8 samples take at most 8.  The Huffman table is the frame's own (T.81 Annex K.2);
     tests/jpeg_lossless_model.py states the file.  A sample >= 2^precision raises OverflowError.  dicom_encapsulate wraps
-    the frames as PixelData.  Arguments are checked (TypeError / ValueError) before any device call.
+    the frames as PixelData.  predictor is the selection value 1 .. 7 of T.81 Table H.1 for every frame, or "auto" (0): the
+    device builds the seven histograms and tables of each frame and writes the one with the fewest coded bits, its DHT
+    counted, ties to the lowest; that estimate leaves out byte stuffing and pad bits, so it is the smallest estimate and not
+    provably the smallest file.  Frames of one call may then differ; the Ss is in each file's SOS.
+    Arguments are checked (TypeError / ValueError) before any device call.
     Memory: the call reserves cct_jpegll_bound(rows, cols, restart_rows) bytes per frame on the host, the worst case of 31
     bits a sample doubled by byte stuffing, about 7.75 bytes a sample (2 MB for 512 x 512, 520 MB for 256 such frames;
     pages a file does not reach are never touched), and on the device that plus 4 bytes a sample, at most 512 MB at a time:
@@ -813,6 +830,7 @@ def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=Non
         raise TypeError(f"JPEG Lossless frames take uint8 or uint16 samples, got {dt}")
     src_bits = 8 * dt.itemsize
     precision, restart_rows = _ints(precision=src_bits if precision is None else precision, restart_rows=restart_rows)
+    predictor = _check_jpl_predictor(predictor)
     if not 2 <= precision <= 16:
         raise ValueError(f"JPEG Lossless precision {precision}: 2 to 16")
     if precision > src_bits:
@@ -829,8 +847,8 @@ def jpeg_lossless_encode_batch(images, precision=None, restart_rows=0, shape=Non
     out_stride = L.cct_jpegll_bound(rows, cols, restart_rows)
     out, sizes = _files_out(n, out_stride)
     status = np.zeros(n, dtype=np.uint32)
-    _ffi.check(L.cct_jpegll_encode_batch(ptr, on_device, n, rows, cols, src_bits, precision, restart_rows, out.ctypes.data,
-                                         out_stride, sizes.ctypes.data, status.ctypes.data))
+    _ffi.check(L.cct_jpegll_encode_batch_sv(ptr, on_device, n, rows, cols, src_bits, precision, predictor, restart_rows,
+                                            out.ctypes.data, out_stride, sizes.ctypes.data, status.ctypes.data, None))
     del keep
     return _files_of(out, sizes)
 

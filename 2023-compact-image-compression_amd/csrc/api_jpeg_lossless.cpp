@@ -152,6 +152,15 @@ int cct_jpegll_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int
 int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int src_bits, int precision, int restart_rows,
                             uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, uint32_t *h_status)
 {
+	return cct_jpegll_encode_batch_sv(images, images_on_device, n, rows, cols, src_bits, precision, 1, restart_rows, h_out, out_stride, h_out_sizes,
+	                                  h_status, nullptr);
+}
+
+int cct_jpegll_encode_batch_sv(const void *images, int images_on_device, int n, int rows, int cols, int src_bits, int precision, int predictor,
+                               int restart_rows, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes, uint32_t *h_status,
+                               uint32_t *h_predictors)
+{
+	if (predictor < 0 || predictor > 7) return fail(CCT_E_ARG, "JPEG Lossless: predictor %d: 1 .. 7, or 0 for the frame's best", predictor);
 	int rc = check_shape(n, rows, cols);
 	if (rc) return rc;
 	if (src_bits != 8 && src_bits != 16) return fail(CCT_E_ARG, "JPEG Lossless: samples of %d bits: 8 or 16", src_bits);
@@ -170,17 +179,20 @@ int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int
 	EventPair &ev = g_enc_ws.ev;
 	const size_t N = (size_t)rows * cols, img_bytes = N * (src_bits / 8), dstride = (bound + 3) & ~(size_t)3;
 	const uint32_t rpi = restart_rows ? (uint32_t)restart_rows : (uint32_t)rows, n_int = ((uint32_t)rows + rpi - 1) / rpi;
-	const int per_pass = (int)std::max<size_t>(1, JPL_PASS_BYTES / (dstride + 4 * N));
+	// predictor 0: seven histograms and seven tables a frame where a fixed predictor has one of each
+	const uint32_t ncand = predictor ? 1u : JPL_NCAND;
+	const size_t cand_bytes = predictor ? 0 : (size_t)(JPL_NCAND - 1) * (17 * 4 + sizeof(JplCode));
+	const int per_pass = (int)std::max<size_t>(1, JPL_PASS_BYTES / (dstride + 4 * N + cand_bytes));
 	float ms_sum = 0;
-	std::vector<uint32_t> status;
+	std::vector<uint32_t> status, sel;
 	StreamDrain drain(st);  // copies into caller memory land before any return
 	for (int c0 = 0; c0 < n; c0 += per_pass) {
 		const int nc = std::min(per_pass, n - c0);
 		const void *d_img;
 		if ((rc = rasters_to_device(images, images_on_device, c0, nc, img_bytes, W[E_IMG], st, &d_img))) return rc;
-		const size_t hist_bytes = (size_t)nc * 18 * 4;  // 17 bins and the status word of every frame
+		const size_t hist_bytes = (size_t)nc * (17 * ncand + 2) * 4;  // 17 bins a candidate, the status word and the selection value of every frame
 		if ((rc = W[E_HIST].ensure(hist_bytes))) return rc;
-		if ((rc = W[E_CODES].ensure((size_t)nc * sizeof(JplCode)))) return rc;
+		if ((rc = W[E_CODES].ensure((size_t)nc * ncand * sizeof(JplCode)))) return rc;
 		if ((rc = W[E_BITBUF].ensure((size_t)nc * N * 4))) return rc;
 		if ((rc = W[E_INTS].ensure((size_t)nc * n_int * 3 * 4))) return rc;
 		if ((rc = W[E_OUT].ensure((size_t)nc * dstride))) return rc;
@@ -188,7 +200,8 @@ int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int
 		JplEncArgs a{};
 		a.images = d_img; a.src_bits = (uint32_t)src_bits; a.n = (uint32_t)nc; a.rows = (uint32_t)rows; a.cols = (uint32_t)cols;
 		a.precision = (uint32_t)precision; a.rpi = rpi; a.n_int = n_int; a.restart = restart_rows > 0;
-		a.hist = (uint32_t *)W[E_HIST].p; a.status = a.hist + (size_t)nc * 17;
+		a.predictor = (uint32_t)predictor; a.ncand = ncand;
+		a.hist = (uint32_t *)W[E_HIST].p; a.status = a.hist + (size_t)nc * 17 * ncand; a.sel = a.status + nc;
 		a.codes = (JplCode *)W[E_CODES].p; a.bitbuf = (uint32_t *)W[E_BITBUF].p;
 		a.ibytes = (uint32_t *)W[E_INTS].p; a.iff = a.ibytes + (size_t)nc * n_int; a.ioff = a.iff + (size_t)nc * n_int;
 		a.out = (uint8_t *)W[E_OUT].p; a.out_stride = dstride; a.out_sizes = (uint32_t *)W[E_SIZES].p;
@@ -199,9 +212,14 @@ int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int
 		status.assign(nc, 0);
 		HIP_TRY(hipMemcpyAsync(h_out_sizes + c0, W[E_SIZES].p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(status.data(), a.status, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+		if (h_predictors) {
+			sel.assign(nc, 0);
+			HIP_TRY(hipMemcpyAsync(sel.data(), a.sel, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+		}
 		HIP_TRY(hipStreamSynchronize(st));
 		if ((rc = ev.add_ms(ms_sum))) return rc;
 		for (int i = 0; i < nc; i++) h_status[c0 + i] = status[i] ? CCT_E_OVERFLOW : CCT_OK;
+		if (h_predictors) std::copy(sel.begin(), sel.end(), h_predictors + c0);
 		if ((rc = files_to_host(h_out + (size_t)c0 * out_stride, out_stride, h_out_sizes + c0, nc, W[E_OUT].p, dstride, 0, bound, "frame", c0, "bound", st)))
 			return rc;
 	}

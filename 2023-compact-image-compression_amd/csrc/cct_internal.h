@@ -338,12 +338,19 @@ struct JplCode {             // one frame's Huffman table as its DHT states it, 
 // sample one word: interval k's unstuffed bytes start at word k * rpi * cols, 31 bits a sample fit.  The bytes of word w
 // are taken from its top down.  out_stride >= jpl_bound(): the layout kernel derives every offset from ibytes + iff, which
 // count bytes that exist in bitbuf, so no store leaves [0, bound).
+// predictor 1 .. 7 is the selection value of every frame and ncand is 1.  predictor 0 lets every frame take the cheapest of
+// the seven: ncand is 7, candidate k (selection value k + 1) of frame f has its histogram at hist[(f * 7 + k) * 17] and its
+// table at codes[f * 7 + k]; the pick kernel copies the winner's table over candidate 0.  Either way the frame's table is
+// codes[f * ncand] and its selection value sel[f] from the table / pick kernel on.
+constexpr uint32_t JPL_NCAND = 7;
 struct JplEncArgs {
 	const void *images;        // n * rows * cols samples of src_bits (8 or 16)
 	uint32_t src_bits, n, rows, cols, precision, rpi, n_int, restart;  // restart: a DRI segment and RST markers are written
-	uint32_t *hist;            // n * 17, zero on entry
+	uint32_t predictor, ncand; // 1 .. 7 and 1, or 0 and JPL_NCAND
+	uint32_t *hist;            // n * ncand * 17, zero on entry
 	uint32_t *status;          // n, zero on entry: JPL_ST_OVERFLOW
-	JplCode *codes;            // n
+	uint32_t *sel;             // n: the selection value written into the frame's SOS
+	JplCode *codes;            // n * ncand
 	uint32_t *bitbuf;          // n * rows * cols words
 	uint32_t *ibytes, *iff;    // n * n_int: unstuffed bytes of an interval, and how many of them are 0xFF
 	uint32_t *ioff;            // n * n_int: offset in the file of the interval's first byte

@@ -2,17 +2,20 @@
 // cct_jpegll_encode_batch / cct_jpegll_decode_batch (api_jpeg_lossless.cpp).  tests/jpeg_lossless_model.py is the CPU
 // restatement of both directions.
 //
-// ENCODE (selection value 1, no point transform).  A sample's difference to its prediction, modulo 2^16, falls into one of 17
-// categories; the frame's Huffman code for the category and the category's extra bits make at most 31 bits a sample.
-//   1 hist    differences and a 17-bin histogram per frame, bins replicated 32 times in LDS; flags samples >= 2^P
-//   2 table   one lane per frame runs Annex K.2 (merge the two rarest, ties to the larger symbol; limit to 16 bits; drop
-//             the reserved code) and leaves BITS, HUFFVAL and the code of every category
+// ENCODE (selection value 1 .. 7 for the call, or 0: every frame its cheapest; no point transform).  A sample's difference
+// to its prediction, modulo 2^16, falls into one of 17 categories; the frame's Huffman code for the category and the
+// category's extra bits make at most 31 bits a sample.  The selection value is a template parameter of kernels 1 and 3.
+//   1 hist    differences and a 17-bin histogram per frame, bins replicated 32 times in LDS; flags samples >= 2^P.  With
+//             predictor 0 the seven histograms of the seven selection values, from the same read
+//   2 table   one lane per frame (per frame and candidate) runs Annex K.2 (merge the two rarest, ties to the larger
+//             symbol; limit to 16 bits; drop the reserved code) and leaves BITS, HUFFVAL and the code of every category
+//     pick    predictor 0 only, one lane per frame: the candidate with the fewest coded bits, ties to the lowest
 //   3 emit    a workgroup per restart interval, 1024 samples a step, 4 per lane: a block scan of the lanes' bit counts
 //             places every sample, atomic ORs assemble the bits in LDS, whole words go to the interval's slot of bitbuf
 //             and the partial word is carried into the next step; counts the interval's bytes and how many are 0xFF
 //   4 layout  one lane per frame sums the interval sizes into file offsets and writes the headers and EOI
 //   5 stuff   a workgroup per interval copies the bytes to their place, a 0x00 behind every 0xFF, RSTm in front
-// The raster is read twice (1 and 3).
+// The raster is read twice (1 and 3), with predictor 0 too.
 //
 // DECODE.  Where a code word starts is known only once every one before it has been read.
 //   1 unstuff   a workgroup per frame drops the stuffed zeros, fill bytes and RST markers (a 0xFF is data only when a 0x00
@@ -38,12 +41,36 @@ namespace {
 
 // ---- encode ---------------------------------------------------------------------------------------------------------
 
-// difference of sample g (column c; first: it opens an interval) to its prediction, modulo 2^16
-template <typename Px>
-__device__ __forceinline__ uint32_t jpl_diff(const Px *img, uint32_t g, uint32_t c, bool first, uint32_t cols, uint32_t init)
+// T.81 Table H.1 in 32-bit signed arithmetic, >> an arithmetic shift: selection values 4 .. 6 may leave 0 .. 65535, the
+// difference is masked to 16 bits behind
+__device__ __forceinline__ int jpl_predict(uint32_t ss, int ra, int rb, int rc)
 {
-	const uint32_t pred = first ? init : (c == 0 ? (uint32_t)img[g - cols] : (uint32_t)img[g - 1]);
-	return ((uint32_t)img[g] - pred) & 0xFFFFu;
+	switch (ss) {
+	case 1: return ra;
+	case 2: return rb;
+	case 3: return rc;
+	case 4: return ra + rb - rc;
+	case 5: return ra + ((rb - rc) >> 1);
+	case 6: return rb + ((ra - rc) >> 1);
+	default: return (ra + rb) >> 1;
+	}
+}
+
+// difference of sample g (column c, the i-th of its interval) to its prediction, modulo 2^16.  H.1.2: the interval's first
+// sample is predicted by init, the rest of its first row by Ra, column 0 of a later row by Rb, whatever ss says.  ss = 1 is
+// the statement it was before the other six came.
+template <typename Px>
+__device__ __forceinline__ uint32_t jpl_diff(const Px *img, uint32_t g, uint32_t c, uint32_t i, uint32_t cols, uint32_t init, uint32_t ss)
+{
+	if (ss == 1) {
+		const uint32_t pred = i == 0 ? init : (c == 0 ? (uint32_t)img[g - cols] : (uint32_t)img[g - 1]);
+		return ((uint32_t)img[g] - pred) & 0xFFFFu;
+	}
+	int pred;
+	if (i < cols) pred = i == 0 ? (int)init : (int)img[g - 1];
+	else if (c == 0) pred = (int)img[g - cols];
+	else pred = jpl_predict(ss, (int)img[g - 1], (int)img[g - cols], (int)img[g - cols - 1]);
+	return (uint32_t)((int)img[g] - pred) & 0xFFFFu;
 }
 
 __device__ __forceinline__ uint32_t jpl_category(uint32_t d, uint32_t &extra)
@@ -58,39 +85,61 @@ __device__ __forceinline__ uint32_t jpl_category(uint32_t d, uint32_t &extra)
 	return c;
 }
 
-template <typename Px>
+// SS 1 .. 7: the frame's histogram under that selection value.  SS 0: the seven of them from one read of the raster, Ra, Rb
+// and Rc loaded once per sample; NC * 17 bins, each replicated 32 times, 15 232 bytes of LDS for the seven.
+template <typename Px, uint32_t SS>
 __global__ void __launch_bounds__(256) jpl_hist_kernel(JplEncArgs a, uint32_t bpf)
 {
-	__shared__ uint32_t h[17 * 32];
+	constexpr uint32_t NC = SS ? 1u : JPL_NCAND;
+	__shared__ uint32_t h[NC * 17 * 32];
 	__shared__ uint32_t over;
 	const uint32_t t = threadIdx.x, frame = blockIdx.x / bpf, b = blockIdx.x % bpf;
 	const uint32_t N = a.rows * a.cols, isz = a.rpi * a.cols;
 	const Px *img = (const Px *)a.images + (size_t)frame * N;
-	for (uint32_t i = t; i < 17 * 32; i += 256) h[i] = 0;
+	for (uint32_t i = t; i < NC * 17 * 32; i += 256) h[i] = 0;
 	if (t == 0) over = 0;
 	__syncthreads();
 	bool ov = false;
 	for (uint32_t g = b * 256u + t; g < N; g += bpf * 256u) {
 		ov |= ((uint32_t)img[g] >> a.precision) != 0;
 		uint32_t extra;
-		const uint32_t cat = jpl_category(jpl_diff(img, g, g % a.cols, g % isz == 0, a.cols, 1u << (a.precision - 1)), extra);
-		atomicAdd(&h[cat * 32 + (t & 31u)], 1u);
+		if (SS) {
+			const uint32_t cat = jpl_category(jpl_diff(img, g, g % a.cols, g % isz, a.cols, 1u << (a.precision - 1), SS), extra);
+			atomicAdd(&h[cat * 32 + (t & 31u)], 1u);
+		} else {
+			const uint32_t c = g % a.cols, i = g % isz;
+			const int x = (int)img[g];
+			if (i < a.cols || c == 0) {  // one prediction for all seven
+				const int pred = i == 0 ? (int)(1u << (a.precision - 1)) : (int)img[c == 0 ? g - a.cols : g - 1];
+				const uint32_t cat = jpl_category((uint32_t)(x - pred) & 0xFFFFu, extra);
+				for (uint32_t k = 0; k < NC; k++) atomicAdd(&h[(k * 17 + cat) * 32 + (t & 31u)], 1u);
+			} else {
+				const int ra = (int)img[g - 1], rb = (int)img[g - a.cols], rc = (int)img[g - a.cols - 1];
+#pragma unroll
+				for (uint32_t k = 0; k < NC; k++) {
+					const uint32_t cat = jpl_category((uint32_t)(x - jpl_predict(k + 1, ra, rb, rc)) & 0xFFFFu, extra);
+					atomicAdd(&h[(k * 17 + cat) * 32 + (t & 31u)], 1u);
+				}
+			}
+		}
 	}
 	if (ov) atomicOr(&over, 1u);
 	__syncthreads();
-	if (t < 17) {
+	if (t < NC * 17) {
 		uint32_t s = 0;
 		for (uint32_t k = 0; k < 32; k++) s += h[t * 32 + k];
-		if (s) atomicAdd(&a.hist[frame * 17 + t], s);
+		if (s) atomicAdd(&a.hist[frame * (NC * 17) + t], s);
 	}
 	if (t == 0 && over) atomicOr(&a.status[frame], JPL_ST_OVERFLOW);
 }
 
-// Annex K.2 over the 17 categories and the reserved symbol (index 17, the largest), one lane per frame
+// Annex K.2 over the 17 categories and the reserved symbol (index 17, the largest), one lane per table: per frame, or per
+// (frame, candidate) of the a.n * a.ncand that predictor 0 weighs.  A fixed predictor is the frame's selection value here.
 __global__ void __launch_bounds__(64) jpl_table_kernel(JplEncArgs a)
 {
-	const uint32_t frame = blockIdx.x * 64u + threadIdx.x;
-	if (frame >= a.n) return;
+	const uint32_t frame = blockIdx.x * 64u + threadIdx.x;  // the table's index: frame * ncand + candidate
+	if (frame >= a.n * a.ncand) return;
+	if (a.predictor) a.sel[frame] = a.predictor;
 	uint32_t freq[18];
 	int codesize[18], others[18];
 	for (int i = 0; i < 17; i++) freq[i] = a.hist[frame * 17 + i];
@@ -138,6 +187,26 @@ __global__ void __launch_bounds__(64) jpl_table_kernel(JplEncArgs a)
 	}
 }
 
+// predictor 0, one lane per frame: the candidate whose table codes its histogram in the fewest bits, the HUFFVAL bytes of
+// its DHT counted in (unstuffed bits and no pad bits: an estimate of the file, not its size); ties go to the lowest
+// selection value.  The winner's table moves to the frame's first slot, where the emit and layout kernels read it.
+__global__ void __launch_bounds__(64) jpl_pick_kernel(JplEncArgs a)
+{
+	const uint32_t frame = blockIdx.x * 64u + threadIdx.x;
+	if (frame >= a.n) return;
+	uint32_t best = 0;
+	uint64_t best_cost = ~0ull;
+	for (uint32_t k = 0; k < JPL_NCAND; k++) {
+		const JplCode &c = a.codes[frame * JPL_NCAND + k];
+		const uint32_t *hist = a.hist + (size_t)(frame * JPL_NCAND + k) * 17u;
+		uint64_t cost = 8u * (uint32_t)c.nval;
+		for (uint32_t s = 0; s < 17; s++) cost += (uint64_t)hist[s] * ((uint32_t)c.size[s] + (s < 16 ? s : 0u));
+		if (cost < best_cost) { best_cost = cost; best = k; }
+	}
+	a.sel[frame] = best + 1u;
+	if (best) a.codes[frame * JPL_NCAND] = a.codes[frame * JPL_NCAND + best];
+}
+
 // nb bits of val at bit p of the LDS words w (bit 0 is the top bit of w[0]); nb <= 31, so two words at most
 __device__ __forceinline__ void jpl_put(uint32_t *w, uint32_t p, uint32_t val, uint32_t nb)
 {
@@ -155,8 +224,8 @@ __device__ __forceinline__ uint32_t jpl_ff_bytes(uint32_t v, uint32_t nbytes)  /
 
 // A workgroup per interval.  LDS words: a step adds at most 1024 * 31 bits to a carry of at most 31, 993 words and the one
 // jpl_put may touch behind.  bitbuf: the interval's slot has a word per sample and its bits fit 31 per sample, so the
-// ceil(bits / 32) words written stay inside the slot.
-template <typename Px>
+// ceil(bits / 32) words written stay inside the slot.  SS 1 .. 7: that selection value; SS 0: the frame's own, sel[frame].
+template <typename Px, uint32_t SS>
 __global__ void __launch_bounds__(256) jpl_emit_kernel(JplEncArgs a)
 {
 	__shared__ uint32_t w[JPL_CHUNK + 8];
@@ -168,7 +237,9 @@ __global__ void __launch_bounds__(256) jpl_emit_kernel(JplEncArgs a)
 	const uint32_t N = a.rows * a.cols, r0 = k * a.rpi, nrows = min(a.rpi, a.rows - r0), ns = nrows * a.cols, g0 = r0 * a.cols;
 	const Px *img = (const Px *)a.images + (size_t)frame * N;
 	uint32_t *dst = a.bitbuf + (size_t)frame * N + g0;
-	if (t < 17) { l_size[t] = a.codes[frame].size[t]; l_code[t] = a.codes[frame].code[t]; }
+	const uint32_t ss = SS ? SS : a.sel[frame];
+	const JplCode &code = a.codes[SS ? frame : frame * JPL_NCAND];
+	if (t < 17) { l_size[t] = code.size[t]; l_code[t] = code.code[t]; }
 	if (t == 0) { s_ff = 0; w[0] = 0; }
 	__syncthreads();
 	uint32_t carry_bits = 0, words_out = 0, ff = 0, nbytes = 0;
@@ -182,7 +253,7 @@ __global__ void __launch_bounds__(256) jpl_emit_kernel(JplEncArgs a)
 			val[j] = 0; nb[j] = 0;
 			if (i0 + j < ns) {
 				uint32_t extra;
-				const uint32_t cat = jpl_category(jpl_diff(img, g0 + i0 + j, c, i0 + j == 0, a.cols, 1u << (a.precision - 1)), extra);
+				const uint32_t cat = jpl_category(jpl_diff(img, g0 + i0 + j, c, i0 + j, a.cols, 1u << (a.precision - 1), ss), extra);
 				const uint32_t nx = cat == 16 ? 0u : cat;
 				val[j] = ((uint32_t)l_code[cat] << nx) | extra;
 				nb[j] = (uint32_t)l_size[cat] + nx;
@@ -231,7 +302,7 @@ __global__ void __launch_bounds__(64) jpl_layout_kernel(JplEncArgs a)
 {
 	const uint32_t frame = blockIdx.x * 64u + threadIdx.x;
 	if (frame >= a.n) return;
-	const JplCode &c = a.codes[frame];
+	const JplCode &c = a.codes[frame * a.ncand];
 	uint8_t *f = a.out + (size_t)frame * a.out_stride, *p = f;
 	*p++ = 0xFF; *p++ = 0xD8;
 	*p++ = 0xFF; *p++ = 0xC3; jpl_be16(p, 11); *p++ = (uint8_t)a.precision; jpl_be16(p, a.rows); jpl_be16(p, a.cols);
@@ -240,7 +311,7 @@ __global__ void __launch_bounds__(64) jpl_layout_kernel(JplEncArgs a)
 	for (int i = 0; i < 16; i++) *p++ = c.bits[i];
 	for (uint32_t i = 0; i < c.nval && i < 17; i++) *p++ = c.huffval[i];
 	if (a.restart) { *p++ = 0xFF; *p++ = 0xDD; jpl_be16(p, 4); jpl_be16(p, a.rpi * a.cols); }
-	*p++ = 0xFF; *p++ = 0xDA; jpl_be16(p, 8); *p++ = 1; *p++ = 1; *p++ = 0; *p++ = 1; *p++ = 0; *p++ = 0;
+	*p++ = 0xFF; *p++ = 0xDA; jpl_be16(p, 8); *p++ = 1; *p++ = 1; *p++ = 0; *p++ = (uint8_t)a.sel[frame]; *p++ = 0; *p++ = 0;
 	uint32_t off = (uint32_t)(p - f);
 	for (uint32_t k = 0; k < a.n_int; k++) {
 		if (k) off += 2;
@@ -521,21 +592,40 @@ __global__ void __launch_bounds__(256) jpl_generic_kernel(JplDecArgs a)
 	}
 }
 
+// launches 1 .. 3 of the encoder for one selection value (SS 0: the seven candidates and the pick)
+template <typename Px, uint32_t SS>
+void jpl_encode_front(const JplEncArgs &a, uint32_t bpf, hipStream_t st)
+{
+	hipLaunchKernelGGL((jpl_hist_kernel<Px, SS>), dim3(a.n * bpf), dim3(256), 0, st, a, bpf);
+	hipLaunchKernelGGL(jpl_table_kernel, dim3((a.n * a.ncand + 63u) / 64u), dim3(64), 0, st, a);
+	if (SS == 0) hipLaunchKernelGGL(jpl_pick_kernel, dim3((a.n + 63u) / 64u), dim3(64), 0, st, a);
+	hipLaunchKernelGGL((jpl_emit_kernel<Px, SS>), dim3(a.n * a.n_int), dim3(256), 0, st, a);
+}
+
+template <typename Px>
+void jpl_encode_front(const JplEncArgs &a, uint32_t bpf, hipStream_t st)
+{
+	switch (a.predictor) {
+	case 0: jpl_encode_front<Px, 0>(a, bpf, st); break;
+	case 1: jpl_encode_front<Px, 1>(a, bpf, st); break;
+	case 2: jpl_encode_front<Px, 2>(a, bpf, st); break;
+	case 3: jpl_encode_front<Px, 3>(a, bpf, st); break;
+	case 4: jpl_encode_front<Px, 4>(a, bpf, st); break;
+	case 5: jpl_encode_front<Px, 5>(a, bpf, st); break;
+	case 6: jpl_encode_front<Px, 6>(a, bpf, st); break;
+	default: jpl_encode_front<Px, 7>(a, bpf, st); break;
+	}
+}
+
 }  // namespace
 
 hipError_t launch_jpl_encode(const JplEncArgs &a, hipStream_t st)
 {
 	const uint32_t N = a.rows * a.cols, bpf = std::min(64u, (N + 4095u) / 4096u);
 	const dim3 per_frame((a.n + 63u) / 64u), per_int(a.n * a.n_int);
-	if (a.src_bits == 16) {
-		hipLaunchKernelGGL(jpl_hist_kernel<uint16_t>, dim3(a.n * bpf), dim3(256), 0, st, a, bpf);
-		hipLaunchKernelGGL(jpl_table_kernel, per_frame, dim3(64), 0, st, a);
-		hipLaunchKernelGGL(jpl_emit_kernel<uint16_t>, per_int, dim3(256), 0, st, a);
-	} else {
-		hipLaunchKernelGGL(jpl_hist_kernel<uint8_t>, dim3(a.n * bpf), dim3(256), 0, st, a, bpf);
-		hipLaunchKernelGGL(jpl_table_kernel, per_frame, dim3(64), 0, st, a);
-		hipLaunchKernelGGL(jpl_emit_kernel<uint8_t>, per_int, dim3(256), 0, st, a);
-	}
+	if (a.predictor > 7u || a.ncand != (a.predictor ? 1u : JPL_NCAND)) return hipErrorInvalidValue;
+	if (a.src_bits == 16) jpl_encode_front<uint16_t>(a, bpf, st);
+	else jpl_encode_front<uint8_t>(a, bpf, st);
 	hipLaunchKernelGGL(jpl_layout_kernel, per_frame, dim3(64), 0, st, a);
 	hipLaunchKernelGGL(jpl_stuff_kernel, per_int, dim3(256), 0, st, a);
 	return hipGetLastError();

@@ -375,6 +375,16 @@ int cct_dicom_rle_decode_batch(const uint8_t *h_frames, const uint64_t *h_offset
  * Differences are taken modulo 2^16; the Huffman table is built per frame by Annex K.2 (ties go to the larger symbol, the
  * reserved symbol 256 has frequency 1).  A frame with a sample >= 2^P gets CCT_E_OVERFLOW in h_status[i] and size 0; the
  * other frames are written and the call returns the first non-OK status.  The call takes the encode slot, like the RLE codec.
+ * cct_jpegll_encode_batch_sv: the same call with the predictor chosen (process 14 in general, DICOM transfer syntax
+ * 1.2.840.10008.1.2.4.57; cct_jpegll_encode_batch is this call with predictor 1).  predictor 1 .. 7 is the selection value Ss
+ * of every frame's SOS: Ra, Rb, Rc, Ra + Rb - Rc, Ra + ((Rb - Rc) >> 1), Rb + ((Ra - Rc) >> 1), (Ra + Rb) >> 1 in 32-bit signed
+ * arithmetic with an arithmetic shift (Ra left, Rb above, Rc above left); the three rules above for an interval's first
+ * sample, its first row and column 0 hold under every Ss (T.81 H.1.2).  predictor 0 lets the device choose per frame: it
+ * builds the seven category histograms and Annex K.2 tables and takes the Ss with the smallest
+ * sum_s hist[s] * (size[s] + (s < 16 ? s : 0)) + 8 * (number of HUFFVAL bytes) bits, ties to the lowest Ss.  That counts the
+ * coded bits before byte stuffing and without the pad bits of the intervals: the smallest estimate, not provably the
+ * smallest file.  Frames of one call may differ in Ss.  h_predictors, which may be NULL, receives the Ss written for
+ * frame i, also for a frame that fails with CCT_E_OVERFLOW.  A predictor outside 0 .. 7 is CCT_E_ARG.
  * cct_jpegll_bound(rows, cols, restart_rows): a sample costs at most 31 bits (a 16-bit code and 15 extra bits), an interval
  * of s samples at most ceil(31 s / 8) bytes, doubled by byte stuffing, plus 2 for its RST; headers and EOI stay below 72:
  * 72 + intervals * (2 * ceil(31 s / 8) + 2).  0 for a refused shape; out_stride below it is CCT_E_CAP.
@@ -392,12 +402,17 @@ int cct_dicom_rle_decode_batch(const uint8_t *h_frames, const uint64_t *h_offset
  * leaves whole bytes over, a wrong, missing or spare RST.  Refused files leave the others decoded, nothing is written
  * outside a refused file's own rows*cols slot, and the call returns the first non-OK status.
  * Whole-call errors, before the device is touched: CCT_E_ARG for rows or cols outside 1 .. 65535, rows*cols above 2^26,
- * n < 0, bits or src_bits other than 8 or 16, a precision outside 2 .. src_bits, Ri above 65535; CCT_E_CAP as above.
- * cct_last_timings: [0] the five encode kernels, [4] the decode kernels, HIP events, summed over the passes. */
+ * n < 0, bits or src_bits other than 8 or 16, a precision outside 2 .. src_bits, Ri above 65535, a predictor outside
+ * 0 .. 7 (checked first); CCT_E_CAP as above.
+ * cct_last_timings: [0] the five encode kernels (six with predictor 0), [4] the decode kernels, HIP events, summed over the passes. */
 size_t cct_jpegll_bound(int rows, int cols, int restart_rows);
 int cct_jpegll_encode_batch(const void *images, int images_on_device, int n, int rows, int cols, int src_bits /* 8 or 16 */,
                             int precision, int restart_rows, uint8_t *h_out, size_t out_stride, uint32_t *h_out_sizes,
                             uint32_t *h_status /* CCT_E_* per frame */);
+int cct_jpegll_encode_batch_sv(const void *images, int images_on_device, int n, int rows, int cols, int src_bits /* 8 or 16 */,
+                               int precision, int predictor /* 1 .. 7, 0: the frame's best */, int restart_rows, uint8_t *h_out,
+                               size_t out_stride, uint32_t *h_out_sizes, uint32_t *h_status /* CCT_E_* per frame */,
+                               uint32_t *h_predictors /* may be NULL: the Ss written per frame */);
 int cct_jpegll_info(const uint8_t *h_file, size_t len, int *rows, int *cols, int *precision);
 int cct_jpegll_decode_batch(const uint8_t *h_files, const uint64_t *h_offsets, int n, int rows, int cols, int bits, void *images,
                             int images_on_device, size_t images_cap_px, uint32_t *h_status /* CCT_E_* per file */);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device JPEG Lossless (SOF3, selection value 1) codec, both directions, on the 256 phantom slices of 512 x 512 uint16 that
+"""Device JPEG Lossless (SOF3; selection value 1 unless --jpl-predictor names another, or auto) codec, both directions, on the 256 phantom slices of 512 x 512 uint16 that
 tools/bench_dicom_rle.py codes, resident in HBM.
 
 Encode: jpeg_lossless_encode_batch(DeviceBuffer, precision=16); decode: jpeg_lossless_decode_batch(files, out_dev=DeviceBuffer).
@@ -9,7 +9,10 @@ Beside them: the algorithmic HBM bytes (rasters once, files once) at the 8 TB/s 
 Pillow (libjpeg-turbo) decoding the 8-bit frames of the same slices (value >> 4, clipped to 255), which the device also codes
 and decodes.  The first two files are checked against tests/jpeg_lossless_model.py and all round trip.  One JSON line.
 
-    python tools/bench_jpeg_lossless.py [--reps 7] [--slices 256]
+With --jpl-predictor the encoder's kernel time and the file bytes can be taken per predictor; the JSON line names it, and
+with auto how many frames chose which selection value.
+
+    python tools/bench_jpeg_lossless.py [--reps 7] [--slices 256] [--jpl-predictor 1..7|auto]
 """
 import argparse
 import ctypes as C
@@ -43,7 +46,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--slices", type=int, default=256)
+    ap.add_argument("--jpl-predictor", choices=tuple("1234567") + ("auto",), default="1")
     args = ap.parse_args(argv)
+    pred = 0 if args.jpl_predictor == "auto" else int(args.jpl_predictor)
     import cct_hip
     import jpeg_lossless_model as model
     from cct_hip.synth import ct_phantom
@@ -52,16 +57,20 @@ def main(argv=None):
     uniq = [ct_phantom(i) for i in range(min(n, 32))]
     imgs = np.stack([uniq[i % len(uniq)] for i in range(n)]).astype(np.uint16)
     _, rows, cols = imgs.shape
-    res = {"slices": n, "shape": [rows, cols], "raster_bytes": int(imgs.nbytes), "reps": args.reps}
+    res = {"slices": n, "shape": [rows, cols], "raster_bytes": int(imgs.nbytes), "reps": args.reps, "predictor": args.jpl_predictor}
     d_img = cct_hip.DeviceBuffer.from_numpy(imgs)
     d_out = cct_hip.DeviceBuffer(imgs.nbytes)
-    files = cct_hip.jpeg_lossless_encode_batch(d_img, precision=16, shape=imgs.shape)
-    assert files[:2] == [model.encode_frame(x, 16) for x in imgs[:2]], "files differ from the model"
+    files = cct_hip.jpeg_lossless_encode_batch(d_img, precision=16, shape=imgs.shape, predictor=pred)
+    chosen = [f[f.index(b"\xff\xda") + 7] for f in files]  # Ss of the SOS
+    assert files[:2] == [model.encode_frame(x, 16, predictor=s) for x, s in zip(imgs[:2], chosen)], "files differ from the model"
+    assert pred == 0 or chosen == [pred] * n
+    if pred == 0:
+        res["frames_per_predictor"] = {str(s): chosen.count(s) for s in sorted(set(chosen))}
     file_bytes = sum(map(len, files))
     algo = imgs.nbytes + file_bytes
     res.update(frame_bytes=int(file_bytes), algorithmic_hbm_bytes=int(algo),
                algorithmic_ms_at_8TBps=round(algo / (HBM_PEAK_GBS * 1e9) * 1e3, 4))
-    k, c = median_ms(lambda: cct_hip.jpeg_lossless_encode_batch(d_img, precision=16, shape=imgs.shape), args.reps, L, 0)
+    k, c = median_ms(lambda: cct_hip.jpeg_lossless_encode_batch(d_img, precision=16, shape=imgs.shape, predictor=pred), args.reps, L, 0)
     res["encode"] = {"kernels_ms": round(k, 3), "call_ms": round(c, 1), "GBps_algorithmic": round(algo / (k * 1e-3) / 1e9, 1)}
     k, c = median_ms(lambda: cct_hip.jpeg_lossless_decode_batch(files, rows, cols, out_dev=d_out), args.reps, L, 4)
     res["decode"] = {"kernels_ms": round(k, 3), "call_ms": round(c, 1), "GBps_algorithmic": round(algo / (k * 1e-3) / 1e9, 1)}
@@ -70,7 +79,7 @@ def main(argv=None):
     d_out.free()
     # the 8-bit frames: the device both ways, and one core of Pillow reading them
     low = np.minimum(imgs >> 4, 255).astype(np.uint8)
-    files8 = cct_hip.jpeg_lossless_encode_batch(low)
+    files8 = cct_hip.jpeg_lossless_encode_batch(low, predictor=pred)
     res["frame_bytes_8bit"] = int(sum(map(len, files8)))
     k, c = median_ms(lambda: cct_hip.jpeg_lossless_decode_batch(files8, rows, cols, bits=8), args.reps, L, 4)
     res["decode_8bit"] = {"kernels_ms": round(k, 3), "call_ms": round(c, 1)}

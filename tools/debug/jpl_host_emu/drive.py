@@ -11,6 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "..", "..", "tests"))
 import jpeg_lossless_model as m  # noqa: E402
+import jpeg_lossless_predictors as jp  # noqa: E402
 
 EMU = os.path.join(HERE, "emu")
 
@@ -20,16 +21,53 @@ def run(*args):
     assert r.returncode == 0, (args, r.stdout[-2000:], r.stderr[-4000:])
 
 
-def encode(imgs, precision, restart_rows, tmp):
+def encode(imgs, precision, restart_rows, tmp, predictor=1, with_ss=False):
+    """-> (status, file) per frame, with with_ss (status, file, Ss); predictor 1 .. 7, or 0 for the frame's best"""
     n, rows, cols = imgs.shape
     imgs.tofile(os.path.join(tmp, "in.bin"))
-    run("e", 8 * imgs.dtype.itemsize, precision, rows, cols, n, restart_rows, os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin"))
+    run("e", 8 * imgs.dtype.itemsize, precision, rows, cols, n, restart_rows, predictor, os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin"))
     d, out, pos = open(os.path.join(tmp, "out.bin"), "rb").read(), [], 0
     for _ in range(n):
-        size, status = struct.unpack_from("<II", d, pos)
-        out.append((status, d[pos + 8:pos + 8 + size]))
-        pos += 8 + size
+        size, status, ss = struct.unpack_from("<III", d, pos)
+        out.append((status, d[pos + 12:pos + 12 + size], ss) if with_ss else (status, d[pos + 12:pos + 12 + size]))
+        pos += 12 + size
     return out
+
+
+def encode_predictors(tmp, rng):
+    """selection values 2 .. 7 and the frame's best against the model: files, the Ss reported, differences that leave 16 bits,
+    frames of one batch that choose differently, and an overflowing frame among good ones"""
+    for rows, cols in ((1, 1), (1, 65), (3, 1), (2, 3), (17, 63), (5, 257)):
+        for dt, p in ((np.uint8, 8), (np.uint16, 12), (np.uint16, 16)):
+            c = m.raster_cases(rows, cols, p, dt)
+            imgs = np.stack(list(c.values()))
+            for ss in jp.PREDICTORS[1:]:
+                rr = (0, 1, 2, 5)[(ss + rows + p) % 4]
+                for name, (st, g, s), x in zip(c, encode(imgs, p, rr, tmp, ss, True), imgs):
+                    assert st == 0 and s == ss and g == m.encode_frame(x, p, ss, 0, rr), (rows, cols, p, rr, ss, name)
+            for rr in (0, 2):
+                for name, (st, g, s), x in zip(c, encode(imgs, p, rr, tmp, 0, True), imgs):
+                    pick = jp.auto_pick(x, p, rr)
+                    assert st == 0 and s == pick and g == m.encode_frame(x, p, pick, 0, rr), (rows, cols, p, rr, name, s, pick)
+    wrap = jp.wrap_rasters()
+    imgs = np.stack(list(wrap.values()))
+    for ss in jp.PREDICTORS:
+        for name, (st, g), x in zip(wrap, encode(imgs, 16, 0, tmp, ss), imgs):
+            assert st == 0 and g == m.encode_frame(x, 16, ss), (name, ss)
+    planted = jp.planted()
+    imgs = np.stack([x for x, _, _ in planted.values()] + [rng.integers(0, 256, (16, 24)).astype(np.uint8)])
+    got = encode(imgs, 8, 0, tmp, 0, True)
+    assert [s for _, _, s in got[:3]] == [want for _, _, want in planted.values()] == [1, 2, 3]
+    for (st, g, s), x in zip(got, imgs):
+        assert st == 0 and s == jp.auto_pick(x, 8) and g == m.encode_frame(x, 8, s), s
+    over = rng.integers(0, 4096, (3, 4, 9)).astype(np.uint16)
+    over[1, 2, 3] = 4096
+    for pred in (4, 0):
+        got = encode(over, 12, 0, tmp, pred, True)
+        assert [st for st, _, _ in got] == [0, 1, 0] and got[1][1] == b"" and all(1 <= s <= 7 for _, _, s in got)
+        for i in (0, 2):
+            ss = pred or jp.auto_pick(over[i], 12)
+            assert got[i][2] == ss and got[i][1] == m.encode_frame(over[i], 12, ss), (pred, i)
 
 
 def decode(files, rows, cols, bits, tmp):
@@ -80,6 +118,7 @@ def main(which):
             over[1, 2, 3] = 4096
             got = encode(over, 12, 0, tmp)
             assert [s for s, _ in got] == [0, 1, 0] and got[1][1] == b"" and got[2][1] == m.encode_frame(over[2], 12)
+            encode_predictors(tmp, rng)
             print("encode ok")
         if which in ("dec", "all"):
             for rows, cols, bits, p in ((1, 1, 8, 8), (5, 7, 8, 8), (5, 65, 16, 12), (3, 257, 16, 16)):

@@ -7,7 +7,8 @@
 #include "emu_common.h"
 #include "../../../2023-compact-image-compression_amd/csrc/jpeg_lossless_kernels.hip"
 using namespace cct;
-// encode: e src_bits precision rows cols n restart_rows in.bin out.bin
+// encode: e src_bits precision rows cols n restart_rows predictor in.bin out.bin   (predictor 1 .. 7, 0: the frame's best;
+//         out.bin: per frame size, status, Ss and the file)
 // decode: d rows cols out_bits nslots job.bin files.bin out.bin   (job.bin: per frame 13 uint32 -- src, len, slot, ss, pt, P, ri,
 //         nval, then 16 + 20 bytes BITS / HUFFVAL)
 int main(int argc, char **argv)
@@ -17,23 +18,26 @@ int main(int argc, char **argv)
 		a.src_bits = atoi(argv[2]); a.precision = atoi(argv[3]); a.rows = atoi(argv[4]); a.cols = atoi(argv[5]); a.n = atoi(argv[6]);
 		const uint32_t rr = atoi(argv[7]);
 		a.rpi = rr ? rr : a.rows; a.n_int = (a.rows + a.rpi - 1) / a.rpi; a.restart = rr > 0;
-		auto in = rd(argv[8]);
+		a.predictor = atoi(argv[8]); a.ncand = a.predictor ? 1 : JPL_NCAND;
+		auto in = rd(argv[9]);
 		const size_t N = (size_t)a.rows * a.cols, isz = (size_t)std::min(a.rpi, a.rows) * a.cols;
 		const size_t bound = JPL_HDR_MAX + a.n_int * (2 * ((31 * isz + 7) / 8) + 2), stride = (bound + 3) & ~(size_t)3;
-		std::vector<uint32_t> hist(a.n * 17), status(a.n), ints((size_t)a.n * a.n_int * 3), sizes(a.n);
-		std::vector<JplCode> codes(a.n);
+		std::vector<uint32_t> status(a.n), sel(a.n), ints((size_t)a.n * a.n_int * 3), sizes(a.n);
+		std::vector<uint8_t> hist((size_t)a.n * a.ncand * 17 * 4 + GUARD, 0xEE), codes((size_t)a.n * a.ncand * sizeof(JplCode) + GUARD, 0xEE);
+		memset(hist.data(), 0, hist.size() - GUARD);
 		std::vector<uint8_t> bitbuf(a.n * N * 4 + GUARD, 0xEE), out(a.n * stride + GUARD, 0xEE);
-		a.images = in.data(); a.hist = hist.data(); a.status = status.data(); a.codes = codes.data(); a.bitbuf = (uint32_t *)bitbuf.data();
+		a.images = in.data(); a.hist = (uint32_t *)hist.data(); a.status = status.data(); a.sel = sel.data(); a.codes = (JplCode *)codes.data(); a.bitbuf = (uint32_t *)bitbuf.data();
 		a.ibytes = ints.data(); a.iff = a.ibytes + (size_t)a.n * a.n_int; a.ioff = a.iff + (size_t)a.n * a.n_int;
 		a.out = out.data(); a.out_stride = stride; a.out_sizes = sizes.data();
-		launch_jpl_encode(a, nullptr);
-		std::ofstream f(argv[9], std::ios::binary);
+		if (launch_jpl_encode(a, nullptr) != hipSuccess) { printf("launch refused\n"); return 2; }
+		std::ofstream f(argv[10], std::ios::binary);
 		for (uint32_t i = 0; i < a.n; i++) {
 			uint32_t s = sizes[i], stt = status[i];
 			if (s > bound) { printf("size beyond bound\n"); return 2; }
-			f.write((char *)&s, 4); f.write((char *)&stt, 4); f.write((char *)out.data() + i * stride, s);
+			f.write((char *)&s, 4); f.write((char *)&stt, 4); f.write((char *)&sel[i], 4); f.write((char *)out.data() + i * stride, s);
 		}
-		if (!guard_ok(bitbuf, a.n * N * 4) || !guard_ok(out, a.n * stride)) { printf("guard hit\n"); return 2; }
+		if (!guard_ok(bitbuf, a.n * N * 4) || !guard_ok(out, a.n * stride) || !guard_ok(hist, (size_t)a.n * a.ncand * 17 * 4) ||
+		    !guard_ok(codes, (size_t)a.n * a.ncand * sizeof(JplCode))) { printf("guard hit\n"); return 2; }
 	} else {
 		JplDecArgs a{};
 		a.rows = atoi(argv[2]); a.cols = atoi(argv[3]); a.out_bits = atoi(argv[4]);

@@ -11,6 +11,7 @@
 #include <vector>
 typedef int hipError_t; typedef void *hipStream_t; typedef void *hipEvent_t;
 constexpr hipError_t hipSuccess = 0;
+constexpr hipError_t hipErrorInvalidValue = 1;
 struct uint2 { uint32_t x, y; };
 static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 struct alignas(16) uint4 { uint32_t x, y, z, w; };

@@ -2,7 +2,7 @@
 """Corpus size comparison: the counterpart of the reference's scripts/evaluate.py:52-136 without pydicom.
 
     python tools/evaluate.py DIRECTORY [--results FILE.csv] [--batch 256] [--zip host|device] [--png host|device]
-                             [--png-input host|device] [--rle device] [--jpl device] [--jls device] [--jp2 device|device-native] [--tif lzw|deflate]
+                             [--png-input host|device] [--rle device] [--jpl device] [--jpl-predictor 1..7|auto] [--jls device] [--jp2 device|device-native] [--tif lzw|deflate]
 
 Every slice under DIRECTORY (.npy, .u16/.raw, .u16.zz, 16-bit .png) gets one CSV row `File,Raw,ZIP,PNG,RLE,JP2,CCT` as
 in results/encoder-comparisons.csv: Raw = bytes of the pixel array, ZIP = zlib.compress at the default level
@@ -24,7 +24,9 @@ behind CCT: the length of the encapsulated PixelData of the slice's JPEG Lossles
 len(cct_hip.dicom_encapsulate([frame])) with the frame from cct_hip.jpeg_lossless_encode_batch; without the flag the CSV has
 no such column.  Like the RLE column it takes 2-byte slices as uint16 whatever their dtype (int16 slices are reinterpreted,
 not offset); 1-byte slices are widened to uint16 and coded at precision 16 too, so that the column means one thing, which
-costs them the longer codes of a 16-bit table and is not what precision 8 would give.  --jls device appends a JLS column
+costs them the longer codes of a 16-bit table and is not what precision 8 would give.  --jpl-predictor names the selection
+value of those frames, 1 (the default: the column is what it was) to 7, or auto: the device takes each slice's cheapest
+(DESIGN.md 5d), about 2.5 % smaller than 1 on real CT slices.  --jls device appends a JLS column
 behind JPL (or CCT) in the same way: the encapsulated JPEG-LS lossless file of cct_hip.jpeg_ls_encode_batch at precision 16,
 slices taken as the JPL column takes them.  --jp2 device fills the JP2 column
 with len(cct_hip.jpeg2000_encode_batch(image, precision=16, shift=4, jp2=True)): a lossless .jp2 file of the 16-bit preview
@@ -106,6 +108,8 @@ def main(argv=None):
     ap.add_argument("--jpl", choices=("na", "device"), default="na",
                     help="device: append a JPL column, the encapsulated JPEG Lossless frame from cct_hip.jpeg_lossless_encode_batch at "
                          "precision 16 (2-byte slices viewed as uint16, 1-byte slices widened to uint16)")
+    ap.add_argument("--jpl-predictor", choices=tuple("1234567") + ("auto",), default="1",
+                    help="the selection value of the JPL column's frames: 1 .. 7, or auto for each slice's cheapest of the seven")
     ap.add_argument("--jls", choices=("na", "device"), default="na",
                     help="device: append a JLS column, the encapsulated JPEG-LS lossless file from cct_hip.jpeg_ls_encode_batch at "
                          "precision 16 (slices taken as for --jpl)")
@@ -159,7 +163,8 @@ def main(argv=None):
                 if args.jpl == "device":
                     stack = np.stack([img for _, img in chunk])
                     frames = cct_hip.jpeg_lossless_encode_batch(stack.view(np.uint16) if stack.dtype.itemsize == 2 else stack.astype(np.uint16),
-                                                                precision=16)
+                                                                precision=16,
+                                                                predictor="auto" if args.jpl_predictor == "auto" else int(args.jpl_predictor))
                     for (name, _), fr in zip(chunk, frames):
                         rows[name][JPL] = len(cct_hip.dicom_encapsulate([fr]))
                 if args.jls == "device":
