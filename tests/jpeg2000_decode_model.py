@@ -270,7 +270,11 @@ def parse_packets(P, f, trace=None):
 class MQDecoder:
     """T.800 Annex C.3; bytes beyond the segment read as 0xFF, C is a 32-bit register."""
 
-    def __init__(self, data):
+    def __init__(self, data, trace=None):
+        """trace: "mq_state" and "mq_ctx" as jpeg2000_model.MQEncoder's."""
+        self.trace = trace
+        if trace is not None:
+            self.n_state, self.n_ctx = trace.setdefault("mq_state", {}), trace.setdefault("mq_ctx", {})
         self.d, self.n, self.bp = data, len(data), 0
         self.state = [0] * N_CTX
         self.mps = [0] * N_CTX
@@ -310,7 +314,8 @@ class MQDecoder:
                 return
 
     def decode(self, cx):
-        qe, nmps, nlps, sw = MQ_TABLE[self.state[cx]]
+        st = self.state[cx]
+        qe, nmps, nlps, sw = MQ_TABLE[st]
         mps = self.mps[cx]
         self.a -= qe
         if (self.c >> 16) < qe:
@@ -319,6 +324,8 @@ class MQDecoder:
         else:
             self.c -= qe << 16
             if self.a & 0x8000:
+                if self.trace is not None:
+                    self._count(st, cx, "mps")
                 return mps
             lps = self.a < qe
         if lps:
@@ -329,17 +336,39 @@ class MQDecoder:
         else:
             d = mps
             self.state[cx] = nmps
+        if self.trace is not None:
+            self._count(st, cx, "lps" if lps else "mps")
         self._renorm()
         return d
 
+    def _count(self, st, cx, what):
+        self.n_state[st] = self.n_state.get(st, 0) + 1
+        self.n_ctx[cx, what] = self.n_ctx.get((cx, what), 0) + 1
 
-def t1_decode(data, w, h, orient, nplanes, passes):
-    """One code-block (Annex D): `passes` coding passes from the top plane nplanes - 1 down -> row-major signed coefficients."""
-    mq = MQDecoder(data)
+
+def t1_decode(data, w, h, orient, nplanes, passes, trace=None):
+    """One code-block (Annex D): `passes` coding passes from the top plane nplanes - 1 down -> row-major signed coefficients.
+    trace: "zc", "zc_ctx", "sign", "rl", "mag_ctx", "nplanes" and "block" as jpeg2000_model.t1_encode's, and the MQ decoder's."""
+    mq = MQDecoder(data, trace)
     dec = mq.decode
+    tr = trace
     W = w + 2
     F = [0] * ((h + 2) * W)
     mag = [0] * (w * h)
+    if tr is not None:
+        m.count(tr, "nplanes", nplanes)
+        m.count(tr, "block", (w, h, orient))
+        n_zc, n_zcx, n_mag = (tr.setdefault(key, {}) for key in ("zc", "zc_ctx", "mag_ctx"))  # the hot counters, inline
+
+    def zc(i, kind):
+        cx = zc_context(orient, *neighbours(i))
+        bit = dec(cx)
+        if tr is not None:
+            pattern = ((F[i - W - 1] & 1) | (F[i - W] & 1) << 1 | (F[i - W + 1] & 1) << 2 | (F[i - 1] & 1) << 3 | (F[i + 1] & 1) << 4
+                       | (F[i + W - 1] & 1) << 5 | (F[i + W] & 1) << 6 | (F[i + W + 1] & 1) << 7)
+            n_zc[orient, pattern, kind] = n_zc.get((orient, pattern, kind), 0) + 1
+            n_zcx[orient, cx, bit] = n_zcx.get((orient, cx, bit), 0) + 1
+        return bit
 
     def neighbours(i):
         hh = (F[i - 1] & 1) + (F[i + 1] & 1)
@@ -359,6 +388,8 @@ def t1_decode(data, w, h, orient, nplanes, passes):
             hc, vc, flip = -hc, -vc, 1
         if dec(CTX_SIGN + (3 + vc if hc else vc)) ^ flip:
             F[i] |= F_NEG
+        if tr is not None:
+            m.count(tr, "sign", ((contribution(i - 1), contribution(i + 1), contribution(i - W), contribution(i + W)), (F[i] >> 1) & 1))
         F[i] |= F_SIG
 
     for k in range(passes):
@@ -375,7 +406,7 @@ def t1_decode(data, w, h, orient, nplanes, passes):
                         hh, vv, dd = neighbours(i)
                         if hh + vv + dd == 0:
                             continue
-                        if dec(zc_context(orient, hh, vv, dd)):
+                        if zc(i, "sp"):
                             mag[y * w + x] |= bit
                             sign(i)
                         F[i] |= F_VISIT
@@ -386,6 +417,8 @@ def t1_decode(data, w, h, orient, nplanes, passes):
                         if (f & (F_SIG | F_VISIT)) != F_SIG:
                             continue
                         cx = CTX_MAG + 2 if f & F_REFINED else CTX_MAG + (1 if sum(neighbours(i)) else 0)
+                        if tr is not None:
+                            n_mag[cx] = n_mag.get(cx, 0) + 1
                         if dec(cx):
                             mag[y * w + x] |= bit
                         F[i] = f | F_REFINED
@@ -395,9 +428,13 @@ def t1_decode(data, w, h, orient, nplanes, passes):
                         idx = [(y0 + j + 1) * W + x + 1 for j in range(4)]
                         if all(not F[i] & (F_SIG | F_VISIT) and sum(neighbours(i)) == 0 for i in idx):
                             if not dec(CTX_RL):
+                                if tr is not None:
+                                    m.count(tr, "rl", 4)
                                 continue
                             r = dec(CTX_UNI) << 1
                             r |= dec(CTX_UNI)
+                            if tr is not None:
+                                m.count(tr, "rl", r)
                             mag[(y0 + r) * w + x] |= bit
                             sign(idx[r])
                             first = r + 1
@@ -406,7 +443,7 @@ def t1_decode(data, w, h, orient, nplanes, passes):
                         if F[i] & (F_SIG | F_VISIT):
                             F[i] &= ~F_VISIT
                             continue
-                        if dec(zc_context(orient, *neighbours(i))):
+                        if zc(i, "cu"):
                             mag[y * w + x] |= bit
                             sign(i)
     return [-v if F[(k // w + 1) * W + k % w + 1] & F_NEG else v for k, v in enumerate(mag)]
@@ -450,7 +487,8 @@ def idwt_53(a, levels):
 
 # ---- the file ---------------------------------------------------------------------------------------------------------
 
-def decode(file, rows=None, cols=None, bits=16, shift=0):
+def decode(file, rows=None, cols=None, bits=16, shift=0, trace=None):
+    """trace: what t1_decode collects over the file, and "levels", "precision", "passes", "zbp" and "seglen" as jpeg2000_model.encode's."""
     f = bytes(file)
     try:
         P = walk(f)
@@ -468,8 +506,14 @@ def decode(file, rows=None, cols=None, bits=16, shift=0):
                     continue
                 bx, by = (k % band["ncw"]) * cw, (k // band["ncw"]) * ch
                 w, h = min(cw, band["w"] - bx), min(ch, band["h"] - by)
-                co = t1_decode(bytes(blk["data"]), w, h, band["orient"], band["mb"] - blk["zbp"], blk["passes"])
+                if trace is not None:
+                    for key, item in (("passes", blk["passes"]), ("zbp", blk["zbp"]), ("seglen", len(blk["data"]))):
+                        m.count(trace, key, item)
+                co = t1_decode(bytes(blk["data"]), w, h, band["orient"], band["mb"] - blk["zbp"], blk["passes"], trace)
                 plane[band["y0"] + by:band["y0"] + by + h, band["x0"] + bx:band["x0"] + bx + w] = np.array(co, np.int64).reshape(h, w)
+    if trace is not None:
+        m.count(trace, "levels", P["levels"])
+        m.count(trace, "precision", P["precision"])
     x = _wrap(idwt_53(plane, P["levels"]) + (1 << (P["precision"] - 1)))
     x = np.clip(x, 0, (1 << P["precision"]) - 1) >> shift
     return x.astype(np.uint8 if bits == 8 else np.uint16)

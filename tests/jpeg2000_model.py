@@ -33,12 +33,35 @@ LL, HL, LH, HH = 0, 1, 2, 3
 GAIN = (0, 1, 1, 2)
 GUARD_BITS = 2
 F_SIG, F_NEG, F_VISIT, F_REFINED = 1, 2, 4, 8
+# The eight neighbours in the bit order of a traced neighbour pattern: bit k is the neighbour at NEIGHBOURS[k] = (dy, dx).
+NEIGHBOURS = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))
+
+
+def count(trace, key, item, n=1):
+    """trace[key][item] += n: every traced event is a counter, so traces of several blocks or files add up (merge())."""
+    d = trace.setdefault(key, {})
+    d[item] = d.get(item, 0) + n
+
+
+def merge(traces):
+    out = {}
+    for t in traces:
+        for key, d in t.items():
+            for item, n in d.items():
+                count(out, key, item, n)
+    return out
 
 
 class MQEncoder:
     """T.800 Annex C.2.  The byte "before the first" (BP = BPST - 1) is imaginary and never written."""
 
-    def __init__(self):
+    def __init__(self, trace=None):
+        """trace: "mq_state" {state}, "mq_ctx" {(context, "mps" / "lps")}, "byteout" {"stuff" a byte behind 0xFF, "carry_ff" a carry
+        that makes 0xFF, "carry", "plain"}, "flush" {(C lowered by 0x8000, a final 0xFF dropped)}, "seg_tail" {"ff7f": the coded bytes
+        end in 0xFF 0x7F when the flush begins}.  The bytes do not depend on it."""
+        self.trace = trace
+        if trace is not None:
+            self.n_state, self.n_ctx = trace.setdefault("mq_state", {}), trace.setdefault("mq_ctx", {})
         self.a, self.c, self.ct, self.b, self.pos = 0x8000, 0, 12, 0, -1
         self.out = bytearray()
         self.state = [0] * N_CTX
@@ -52,15 +75,24 @@ class MQEncoder:
         self.b = byte
 
     def _byteout(self):
+        tr = self.trace
         if self.b == 0xFF:
+            if tr is not None:
+                count(tr, "byteout", "stuff")
             self._next(self.c >> 20); self.c &= 0xFFFFF; self.ct = 7
             return
         if self.c >= 0x8000000:
             self.b += 1
             if self.b == 0xFF:
+                if tr is not None:
+                    count(tr, "byteout", "carry_ff")
                 self.c &= 0x7FFFFFF
                 self._next(self.c >> 20); self.c &= 0xFFFFF; self.ct = 7
                 return
+            if tr is not None:
+                count(tr, "byteout", "carry")
+        elif tr is not None:
+            count(tr, "byteout", "plain")
         self._next((self.c >> 19) & 0xFF); self.c &= 0x7FFFF; self.ct = 8
 
     def _renorm(self):
@@ -73,6 +105,10 @@ class MQEncoder:
 
     def encode(self, cx, d):
         qe, nmps, nlps, sw = MQ_TABLE[self.state[cx]]
+        if self.trace is not None:
+            st, key = self.state[cx], (cx, "mps" if d == self.mps[cx] else "lps")
+            self.n_state[st] = self.n_state.get(st, 0) + 1
+            self.n_ctx[key] = self.n_ctx.get(key, 0) + 1
         self.a -= qe
         if d == self.mps[cx]:
             if self.a & 0x8000:
@@ -95,14 +131,21 @@ class MQEncoder:
 
     def flush(self):
         """C.2.9; a final 0xFF is not part of the segment."""
+        tr, self.trace = self.trace, None  # the two BYTEOUTs of the flush are not counted with those of the coding
+        if tr is not None and self.out and self.out[-1] == 0xFF and self.b == 0x7F:
+            count(tr, "seg_tail", "ff7f")
         t = self.c + self.a
         self.c |= 0xFFFF
-        if self.c >= t:
+        lowered = self.c >= t
+        if lowered:
             self.c -= 0x8000
         self.c <<= self.ct; self._byteout()
         self.c <<= self.ct; self._byteout()
         if self.b != 0xFF and self.pos >= 0:
             self.out.append(self.b)
+        if tr is not None:
+            count(tr, "flush", (lowered, self.b == 0xFF))
+        self.trace = tr
         return bytes(self.out)
 
 
@@ -130,17 +173,30 @@ def zc_context(orient, h, v, d):
     return 2 if d >= 2 else d
 
 
-def t1_encode(mag, neg, w, h, orient, nplanes):
+def t1_encode(mag, neg, w, h, orient, nplanes, trace=None):
     """One code-block (Annex D): mag / neg are row-major lists, nplanes the bit length of the largest magnitude (>= 1).
-    -> (bytes of the single codeword segment, coding passes = 3 nplanes - 2)."""
-    mq = MQEncoder()
+    -> (bytes of the single codeword segment, coding passes = 3 nplanes - 2).
+
+    trace (and the MQ coder's, see MQEncoder): "zc" {(orient, neighbour pattern, "sp" / "cu")} with the pattern's bits as NEIGHBOURS,
+    "zc_ctx" {(orient, context, decision)}, "sign" {((W, E, N, S contributions), centre negative)}, "rows" {(orient, pass "sp" / "mr" / "cu",
+    rows of the stripe, mask of the rows the pass codes in one column)}, "rl" {0 .. 3 the row that ends the run, 4 no row},
+    "rl_off" {(orient, mask of significant rows, of visited rows, of rows with a significant neighbour)} of a full column without run-length
+    mode, "edge_sig" {"col" / "row": a sample of the last column / row becomes significant}, "mag_ctx" {context}, "nplanes", "block"
+    {(w, h, orient)}."""
+    mq = MQEncoder(trace)
     enc = mq.encode
+    tr = trace
     W = w + 2
     F = [0] * ((h + 2) * W)  # flags with a border of never-significant samples
     for y in range(h):
         for x in range(w):
             if neg[y * w + x]:
                 F[(y + 1) * W + x + 1] = F_NEG
+    if tr is not None:
+        count(tr, "nplanes", nplanes)
+        count(tr, "block", (w, h, orient))
+        all_rows = (orient, "cu", 4, 15)  # run-length mode: every row is a candidate
+        n_zc, n_ctx, n_rows, n_mag = (tr.setdefault(key, {}) for key in ("zc", "zc_ctx", "rows", "mag_ctx"))  # the hot counters, inline
 
     def neighbours(i):
         hh = (F[i - 1] & 1) + (F[i + 1] & 1)
@@ -160,13 +216,40 @@ def t1_encode(mag, neg, w, h, orient, nplanes):
         else:
             flip = 0
         cx = CTX_SIGN + (3 + vc if hc else vc)  # (0,0) 9, (0,1) 10, (1,-1) 11, (1,0) 12, (1,1) 13
+        if tr is not None:
+            count(tr, "sign", ((contribution(i - 1), contribution(i + 1), contribution(i - W), contribution(i + W)), (F[i] >> 1) & 1))
+            x, y = i % W - 1, i // W - 1
+            if x == w - 1:
+                count(tr, "edge_sig", "col")
+            if y == h - 1:
+                count(tr, "edge_sig", "row")
         enc(cx, ((F[i] >> 1) & 1) ^ flip)
+
+    def cleanup_rows(x, y0):  # traced: the rows of a column that the cleanup pass codes
+        rows, i = 0, (y0 + 1) * W + x + 1
+        for k in range(min(4, h - y0)):
+            if not F[i + k * W] & (F_SIG | F_VISIT):
+                rows |= 1 << k
+        key = (orient, "cu", min(4, h - y0), rows)
+        n_rows[key] = n_rows.get(key, 0) + 1
+
+    def code_zc(i, bit, kind):
+        cx = zc_context(orient, *neighbours(i))
+        if tr is not None:
+            pattern = ((F[i - W - 1] & 1) | (F[i - W] & 1) << 1 | (F[i - W + 1] & 1) << 2 | (F[i - 1] & 1) << 3 | (F[i + 1] & 1) << 4
+                       | (F[i + W - 1] & 1) << 5 | (F[i + W] & 1) << 6 | (F[i + W + 1] & 1) << 7)
+            key = (orient, pattern, kind)
+            n_zc[key] = n_zc.get(key, 0) + 1
+            key = (orient, cx, bit)
+            n_ctx[key] = n_ctx.get(key, 0) + 1
+        enc(cx, bit)
 
     for p in range(nplanes - 1, -1, -1):
         if p != nplanes - 1:
             # significance propagation
             for y0 in range(0, h, 4):
                 for x in range(w):
+                    rows = 0
                     for y in range(y0, min(y0 + 4, h)):
                         i = (y + 1) * W + x + 1
                         if F[i] & F_SIG:
@@ -174,26 +257,37 @@ def t1_encode(mag, neg, w, h, orient, nplanes):
                         hh, vv, dd = neighbours(i)
                         if hh + vv + dd == 0:
                             continue
+                        rows |= 1 << (y - y0)
                         bit = (mag[y * w + x] >> p) & 1
-                        enc(zc_context(orient, hh, vv, dd), bit)
+                        code_zc(i, bit, "sp")
                         if bit:
                             code_sign(i)
                             F[i] |= F_SIG
                         F[i] |= F_VISIT
+                    if tr is not None:
+                        key = (orient, "sp", min(4, h - y0), rows)
+                        n_rows[key] = n_rows.get(key, 0) + 1
             # magnitude refinement
             for y0 in range(0, h, 4):
                 for x in range(w):
+                    rows = 0
                     for y in range(y0, min(y0 + 4, h)):
                         i = (y + 1) * W + x + 1
                         f = F[i]
                         if (f & (F_SIG | F_VISIT)) != F_SIG:
                             continue
+                        rows |= 1 << (y - y0)
                         if f & F_REFINED:
                             cx = CTX_MAG + 2
                         else:
                             cx = CTX_MAG + (1 if sum(neighbours(i)) else 0)
+                        if tr is not None:
+                            n_mag[cx] = n_mag.get(cx, 0) + 1
                         enc(cx, (mag[y * w + x] >> p) & 1)
                         F[i] = f | F_REFINED
+                    if tr is not None:
+                        key = (orient, "mr", min(4, h - y0), rows)
+                        n_rows[key] = n_rows.get(key, 0) + 1
         # cleanup
         for y0 in range(0, h, 4):
             for x in range(w):
@@ -202,6 +296,9 @@ def t1_encode(mag, neg, w, h, orient, nplanes):
                     idx = [(y0 + k + 1) * W + x + 1 for k in range(4)]
                     if all(not F[i] & (F_SIG | F_VISIT) and sum(neighbours(i)) == 0 for i in idx):
                         r = next((k for k in range(4) if (mag[(y0 + k) * w + x] >> p) & 1), 4)
+                        if tr is not None:
+                            count(tr, "rl", r)
+                            n_rows[all_rows] = n_rows.get(all_rows, 0) + 1
                         if r == 4:
                             enc(CTX_RL, 0)
                             continue
@@ -211,12 +308,18 @@ def t1_encode(mag, neg, w, h, orient, nplanes):
                         code_sign(idx[r])
                         F[idx[r]] |= F_SIG
                         first = r + 1
+                    elif tr is not None:
+                        cleanup_rows(x, y0)
+                        count(tr, "rl_off", (orient,) + tuple(sum(1 << k for k, i in enumerate(idx) if t(i)) for t in (
+                            lambda i: F[i] & F_SIG, lambda i: F[i] & F_VISIT, lambda i: sum(neighbours(i)))))
+                elif tr is not None:
+                    cleanup_rows(x, y0)
                 for y in range(y0 + first, min(y0 + 4, h)):
                     i = (y + 1) * W + x + 1
                     if F[i] & (F_SIG | F_VISIT):
                         continue
                     bit = (mag[y * w + x] >> p) & 1
-                    enc(zc_context(orient, *neighbours(i)), bit)
+                    code_zc(i, bit, "cu")
                     if bit:
                         code_sign(i)
                         F[i] |= F_SIG
@@ -278,7 +381,10 @@ def resolutions(rows, cols, levels):
 class BitWriter:
     """Packet header bits (B.10.1): after a byte 0xFF the next byte carries 7 bits; a header does not end in 0xFF."""
 
-    def __init__(self):
+    def __init__(self, trace=None):
+        """trace: "hdr_ff" {"inside": a byte 0xFF with header bits behind it}, "hdr_end" {"partial", "partial_after_ff", "full",
+        "full_ff": how the header's last byte stands, the last with the appended zero byte}."""
+        self.trace = trace
         self.out = bytearray()
         self.cur, self.free, self.cap = 0, 8, 8  # cap: bits the byte under construction takes, free: those still missing
 
@@ -295,6 +401,11 @@ class BitWriter:
             self.put((value >> k) & 1)
 
     def finish(self):
+        if self.trace is not None:
+            partial, ff = self.free != self.cap, bool(self.out) and self.out[-1] == 0xFF
+            count(self.trace, "hdr_end", ("partial_after_ff" if ff else "partial") if partial else ("full_ff" if ff else "full"))
+            if 0xFF in self.out[:-1] or (ff and partial):
+                count(self.trace, "hdr_ff", "inside")
         if self.free != self.cap:
             self.out.append(self.cur << self.free)  # zero padding: never 0xFF
             self.cur, self.free, self.cap = 0, 8, 8
@@ -306,7 +417,10 @@ class BitWriter:
 class TagTree:
     """B.10.2.  Level 0 holds the w x h leaves; every further level halves both sizes, rounding up, down to 1 x 1."""
 
-    def __init__(self, w, h, leaves):
+    def __init__(self, w, h, leaves, trace=None, name="tree"):
+        """trace: "tt_levels" {(w, h, levels)}, "tt_learnt" {(name, level): a node's value is first told at that level, the leaves 0},
+        "tt_low" {(name, level): a node starts from a lower bound above 0 that its parent handed down}."""
+        self.trace, self.name = trace, name
         self.dims = [(w, h)]
         while self.dims[-1] != (1, 1):
             pw, ph = self.dims[-1]
@@ -320,17 +434,23 @@ class TagTree:
                              for y in range(ch) for x in range(cw)])
         self.low = [[0] * len(v) for v in self.val]
         self.known = [[False] * len(v) for v in self.val]
+        if trace is not None:
+            count(trace, "tt_levels", (w, h, len(self.dims)))
 
     def encode(self, bw, x, y, threshold):
         low = 0
         for lv in range(len(self.dims) - 1, -1, -1):
             k = (y >> lv) * self.dims[lv][0] + (x >> lv)
+            if self.trace is not None and low > self.low[lv][k]:
+                count(self.trace, "tt_low", (self.name, lv))
             low = max(low, self.low[lv][k])
             while low < threshold:
                 if low >= self.val[lv][k]:
                     if not self.known[lv][k]:
                         bw.put(1)
                         self.known[lv][k] = True
+                        if self.trace is not None:
+                            count(self.trace, "tt_learnt", (self.name, lv))
                     break
                 bw.put(0)
                 low += 1
@@ -351,17 +471,21 @@ def put_passes(bw, n):
         bw.bits(0x1FF, 9); bw.bits(n - 37, 7)
 
 
-def packet(bands):
-    """One packet: bands = [(ncw, nch, [(passes, zero_planes, data)], mb)] -> header + bodies."""
-    bw = BitWriter()
+def packet(bands, trace=None):
+    """One packet: bands = [(ncw, nch, [(passes, zero_planes, data)], mb)] -> header + bodies.
+    trace (and BitWriter's and TagTree's): "included" {(blocks of the band, blocks included)}, "zbp" {zero bit-planes}, "passes" {n},
+    "lblock" {growth}, "seglen" {bytes}."""
+    bw = BitWriter(trace)
     bw.put(1 if any(ncw * nch for ncw, nch, _, _ in bands) else 0)
     body = bytearray()
     for ncw, nch, blocks, mb in bands:
         if ncw * nch == 0:
             continue
-        incl = TagTree(ncw, nch, [0 if p else 1 for p, _, _ in blocks])
-        zbp = TagTree(ncw, nch, [z if p else mb for p, z, _ in blocks])
-        for k, (passes, _, data) in enumerate(blocks):
+        incl = TagTree(ncw, nch, [0 if p else 1 for p, _, _ in blocks], trace, "incl")
+        zbp = TagTree(ncw, nch, [z if p else mb for p, z, _ in blocks], trace, "zbp")
+        if trace is not None:
+            count(trace, "included", (len(blocks), sum(1 for p, _, _ in blocks if p)))
+        for k, (passes, zeros, data) in enumerate(blocks):
             x, y = k % ncw, k // ncw
             incl.encode(bw, x, y, 1)
             if not passes:
@@ -370,6 +494,9 @@ def packet(bands):
             put_passes(bw, passes)
             need = len(data).bit_length() - (passes.bit_length() - 1)  # Lblock starts at 3
             grow = max(0, need - 3)
+            if trace is not None:
+                for key, item in (("zbp", zeros), ("passes", passes), ("lblock", grow), ("seglen", len(data))):
+                    count(trace, key, item)
             for _ in range(grow):
                 bw.put(1)
             bw.put(0)
@@ -398,7 +525,8 @@ def jp2_header(rows, cols, precision):
             + struct.pack(">I4s", 8 + len(ihdr) + len(colr), b"jp2h") + ihdr + colr)
 
 
-def encode(image, precision, shift=0, levels=5, codeblock=64, jp2=False):
+def encode(image, precision, shift=0, levels=5, codeblock=64, jp2=False, trace=None):
+    """trace: what t1_encode and packet collect over the file, and "levels", "precision", "lengths" {a length the transform ran on}."""
     img = np.asarray(image)
     assert img.ndim == 2 and img.dtype in (np.uint8, np.uint16) and codeblock in (32, 64)
     assert 2 <= precision <= 8 * img.dtype.itemsize and 0 <= shift <= 15 and precision - shift >= 1 and 0 <= levels <= 8
@@ -407,6 +535,14 @@ def encode(image, precision, shift=0, levels=5, codeblock=64, jp2=False):
     if int(v.max()) >= 1 << precision:
         raise OverflowError("a sample does not fit the precision")
     plane = dwt_53(v - (1 << (precision - 1)), levels)
+    if trace is not None:
+        count(trace, "levels", levels)
+        count(trace, "precision", precision)
+        h, w = rows, cols
+        for _ in range(levels):
+            count(trace, "lengths", h)
+            count(trace, "lengths", w)
+            h, w = (h + 1) // 2, (w + 1) // 2
     packets = bytearray()
     for bands in resolutions(rows, cols, levels):
         pk = []
@@ -424,10 +560,10 @@ def encode(image, precision, shift=0, levels=5, codeblock=64, jp2=False):
                         blocks.append((0, mb, b""))
                         continue
                     data, passes = t1_encode(np.abs(blk).ravel().tolist(), (blk < 0).ravel().tolist(), blk.shape[1], blk.shape[0], orient,
-                                             nplanes)
+                                             nplanes, trace)
                     blocks.append((passes, mb - nplanes, data))
             pk.append((ncw if w and h else 0, nch if w and h else 0, blocks, mb))
-        packets += packet(pk)
+        packets += packet(pk, trace)
     psot = 12 + 2 + len(packets)
     cs = (main_header(rows, cols, precision, levels, codeblock) + b"\xff\x90" + struct.pack(">HHIBB", 10, 0, psot, 0, 1) + b"\xff\x93"
           + bytes(packets) + b"\xff\xd9")
@@ -488,6 +624,9 @@ def raster_cases(rows, cols, precision, dtype, seed=0):
 # The smallest shapes at which each mechanism can still go wrong: length-1 lifting, empty subbands and empty packets at 5
 # levels (1 x 1, 1 x 7, 7 x 1); 5 x 3; a one-sample-wide edge code-block and odd subband sizes (33 x 65 at 32, 65 x 33 at
 # 64); two code-blocks across a level-1 subband and partial stripes (130 x 70: 35 rows are no multiple of 4).
+# What this matrix does not reach (2 to 4 and 6 to 8 levels, precisions other than 8 / 12 / 16, tag trees of more than 4 levels or with
+# mixed inclusion, more than 17 bit-planes, planted neighbour patterns and segment lengths) is in tests/jpeg2000_edges.py, and
+# tests/test_jpeg2000_edges_host.py pins what the matrix itself reaches, so SHAPES, LEVELS or raster_cases cannot lose it silently.
 SHAPES = ((1, 1, (32, 64)), (1, 7, (64,)), (7, 1, (32,)), (5, 3, (64,)), (33, 65, (32,)), (65, 33, (64,)), (130, 70, (32, 64)))
 PRECISIONS = {8: np.uint8, 12: np.uint16, 16: np.uint16}
 LEVELS = (0, 1, 5)

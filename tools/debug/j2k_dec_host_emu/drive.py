@@ -1,5 +1,6 @@
 """Feeds ./emu (see emu.cpp) the file sets of tests/jpeg2000_decode_model.py and compares statuses and rasters with the model:
-the encoder model's files, OpenJPEG's own, the hand-built ones, the refused ones and every damaged file.  python drive.py [quick | damaged]"""
+the encoder model's files, OpenJPEG's own, the hand-built ones, the refused ones and every damaged file.  python drive.py [quick | damaged];
+python drive.py edges [group] feeds it the model's files of the planted cases of tests/jpeg2000_edges.py, one call per shape."""
 import os
 import struct
 import subprocess
@@ -36,6 +37,32 @@ def decode(files, rows, cols, bits, shift, tmp):
 
 def same(got, want):
     return got == want if isinstance(want, str) else not isinstance(got, str) and np.array_equal(got, want)
+
+
+def edges(group):
+    """The model's files of tests/jpeg2000_edges.py, mixed codings and precisions in one call per shape, forwards at 16 bits allocated and
+    backwards; at 8 bits allocated what has at most 8 bits of precision (the others are CCT_E_MIXED); the shifted cases with their shift."""
+    import jpeg2000_edges as e
+    files, n = e.files(), 0
+    with tempfile.TemporaryDirectory() as tmp:
+        for rows, cols, cs in e.decode_batches():
+            cs = [c for c in cs if group in (None, c.group)]
+            if not cs:
+                continue
+            for order in (cs, cs[::-1]):
+                for c, g in zip(order, decode([files[c.name] for c in order], rows, cols, 16, 0, tmp)):
+                    assert same(g, c.raster.astype(np.uint16) << c.kw.get("shift", 0)), (c.name, g if isinstance(g, str) else "a raster")
+            if any(c.kw["precision"] <= 8 for c in cs):
+                for c, g in zip(cs, decode([files[c.name] for c in cs], rows, cols, 8, 0, tmp)):
+                    want = "CCT_E_MIXED" if c.kw["precision"] > 8 else c.raster << c.kw.get("shift", 0)
+                    assert same(g, want), (c.name, g if isinstance(g, str) else "a raster")
+            for shift in sorted({c.kw["shift"] for c in cs if c.kw.get("shift")}):
+                sel = [c for c in cs if c.kw.get("shift") == shift]
+                for c, g in zip(sel, decode([files[c.name] for c in sel], rows, cols, 16, shift, tmp)):
+                    assert same(g, c.raster), (c.name, shift)
+            n += len(cs)
+            print("ok", rows, cols, len(cs), "files", flush=True)
+    print("edges ok:", n, "cases")
 
 
 def main(quick):
@@ -83,4 +110,7 @@ def main(quick):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "")
+    if len(sys.argv) > 1 and sys.argv[1] == "edges":
+        edges(sys.argv[2] if len(sys.argv) > 2 else None)
+    else:
+        main(sys.argv[1] if len(sys.argv) > 1 else "")

@@ -1,4 +1,5 @@
-"""Feeds ./emu (see emu.cpp) the rasters of tests/jpeg2000_model.py and compares the files: python drive.py [quick]"""
+"""Feeds ./emu (see emu.cpp) the rasters of tests/jpeg2000_model.py and compares the files: python drive.py [quick];
+python drive.py edges [group] does the same with the planted cases of tests/jpeg2000_edges.py, one launch per batch()."""
 import os
 import struct
 import subprocess
@@ -28,6 +29,26 @@ def encode(imgs, precision, shift, levels, codeblock, jp2, tmp, slab_div=1):
         out.append((status, d[pos + 8:pos + 8 + size]))
         pos += 8 + size
     return out
+
+
+def edges(group):
+    """Every batch of tests/jpeg2000_edges.py (8 levels, 19 bit-planes, 10 x 1 and 9 x 9 tag trees, the adversary's slab): the files are the
+    model's, the sizes stay within the bound and every guard comes back whole (emu.cpp checks both)."""
+    import jpeg2000_edges as e
+    files, n = e.files(), 0
+    with tempfile.TemporaryDirectory() as tmp:
+        for rows, cols, kw, cs in e.batches():
+            cs = [c for c in cs if group in (None, c.group)]
+            if not cs:
+                continue
+            got = encode(np.stack([c.raster for c in cs]), kw["precision"], kw.get("shift", 0), kw["levels"], kw["codeblock"], kw.get("jp2", False), tmp)
+            for c, (st, g) in zip(cs, got):
+                want = files[c.name]
+                at = next((k for k in range(min(len(g), len(want))) if g[k] != want[k]), min(len(g), len(want)))
+                assert st == 0 and g == want, (c.name, st, "first difference at", at, len(g), len(want))
+            n += len(cs)
+            print("ok", rows, cols, kw, len(cs), flush=True)
+    print("edges ok:", n, "cases")
 
 
 def main(quick):
@@ -65,4 +86,7 @@ def main(quick):
 
 
 if __name__ == "__main__":
-    main(len(sys.argv) > 1 and sys.argv[1] == "quick")
+    if len(sys.argv) > 1 and sys.argv[1] == "edges":
+        edges(sys.argv[2] if len(sys.argv) > 2 else None)
+    else:
+        main(len(sys.argv) > 1 and sys.argv[1] == "quick")
