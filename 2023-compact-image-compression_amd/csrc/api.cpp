@@ -50,6 +50,9 @@ struct ShapeTables {  // everything that depends on (width, height) only; lives 
 	uint32_t *d_org = nullptr;
 	uint8_t *d_orient = nullptr;
 	uint16_t *d_pat = nullptr;
+	// decode_kernel's block path: every 16 traversal positions are an aligned 4x4 square of the raster (dec_block_words)
+	bool dec_blocks = false;
+	uint32_t *d_blk = nullptr;
 	// streaming kernel (encode_stream.hip): every tile is a 16x16 grid of 4x4-pixel traversal blocks
 	bool stream = false;
 	uint32_t *d_ptab = nullptr;       // n_orient * 128 * 4
@@ -183,6 +186,7 @@ struct Context {
 	int runtime_bs = 0;  // option "runtime_block_size": 1 sends every block size through the run-time block size kernels (encode_kernel<0>,
 	                     // decode_kernel<0>), which otherwise run the sizes that are not powers of two only; for cross-checks and measurements
 	int last_dec_path = -1;  // read-only option "last_decode_path": 0 a decode_kernel compiled for the block size, 1 the run-time block size kernel
+	int last_dec_block_path = -1;  // read-only option "last_decode_block_path": 1 the last decode launch placed whole 4x4 blocks (decode_kernel<16, true, true>)
 	int dbg_skip = 0;   // option "debug_skip", tuning build only (tuning.h): phase-ablation mask (outputs invalid when set)
 	int tuning_build = TUNING;  // read-only option "tuning_build", tuning build only: how a tool asks which library it loaded
 	int device_deflate = 1;  // option "device_deflate": 0 = DEFLATE stage on the host thread team (libz)
@@ -502,10 +506,65 @@ void build_stream_tables(const std::vector<int32_t> &O, int width, const std::ve
 	t.stream = true;
 }
 
+// decode_kernel's block path (block size 16): is every aligned run of 16 traversal positions of a tile an aligned 4x4 square
+// of the raster, visited in one of at most DEC_BLK_ORDERS orders?  If so a block is four raster rows of four pixels, and its
+// placement is the tile origin plus two table entries.  The words, in the order decode_kernel stages them (dec_block_words):
+//   n_orient * 256   per pattern and block: raster offset dy * width + dx of its top-left pixel inside the tile | order << 16
+//   DEC_BLK_ORDERS * 2   per order: the traversal step that visits cell dy * 4 + dx, a nibble each, low word first
+//   DEC_BLK_ORDERS * 8   per order: the raster offset dy * width + dx of traversal step t, 16 bits each
+// A shape that fails the test keeps dec_blocks false and decodes through the traversal table; that is a property of the
+// shape.  A device error while the tables are put in place is returned (and nothing is left allocated): get_tables fails
+// with it, so a shape never takes the slower path for the life of the context because of one.
+hipError_t build_block_tables(const std::vector<std::vector<uint16_t>> &raws, int width, ShapeTables &t)
+{
+	t.dec_blocks = false;
+	if (width > 1024) return hipSuccess;  // 16-bit offsets inside a tile
+	const size_t no = raws.size();
+	std::vector<uint32_t> words(dec_block_words((int)no), 0);
+	std::vector<uint64_t> orders;  // cell of step t, a nibble each
+	for (size_t o = 0; o < no; o++)
+		for (int b = 0; b < 256; b++) {
+			const uint16_t *k = raws[o].data() + b * 16;
+			int y0 = 64, x0 = 64;
+			for (int i = 0; i < 16; i++) { y0 = std::min(y0, k[i] >> 6); x0 = std::min(x0, k[i] & 63); }
+			if (y0 % 4 != 0 || x0 % 4 != 0) return hipSuccess;
+			uint64_t fwd = 0;
+			uint32_t seen = 0;
+			for (int i = 0; i < 16; i++) {
+				const int dy = (k[i] >> 6) - y0, dx = (k[i] & 63) - x0;
+				if (dy >= 4 || dx >= 4) return hipSuccess;  // not an aligned 4x4 square
+				seen |= 1u << (dy * 4 + dx);
+				fwd |= (uint64_t)(dy * 4 + dx) << (4 * i);
+			}
+			if (seen != 0xFFFFu) return hipSuccess;
+			size_t which = 0;
+			while (which < orders.size() && orders[which] != fwd) which++;
+			if (which == orders.size()) {
+				if (which == DEC_BLK_ORDERS) return hipSuccess;
+				orders.push_back(fwd);
+			}
+			words[o * 256 + b] = (uint32_t)(y0 * width + x0) | ((uint32_t)which << 16);
+		}
+	uint32_t *inv = words.data() + no * 256, *off = inv + DEC_BLK_ORDERS * 2;
+	for (size_t q = 0; q < orders.size(); q++)
+		for (int i = 0; i < 16; i++) {
+			const uint32_t cell = (uint32_t)(orders[q] >> (4 * i)) & 15u;
+			inv[q * 2 + (cell >> 3)] |= (uint32_t)i << (4 * (cell & 7u));
+			off[q * 8 + (i >> 1)] |= ((cell >> 2) * (uint32_t)width + (cell & 3u)) << (16 * (i & 1));
+		}
+	hipError_t e = hipMalloc(&t.d_blk, words.size() * 4);
+	if (e != hipSuccess) { t.d_blk = nullptr; return e; }
+	e = hipMemcpy(t.d_blk, words.data(), words.size() * 4, hipMemcpyHostToDevice);
+	if (e != hipSuccess) { (void)hipFree(t.d_blk); t.d_blk = nullptr; return e; }
+	t.dec_blocks = true;
+	return hipSuccess;
+}
+
 // Does the traversal decompose into aligned 64x64 tiles (4096 consecutive positions each)?  If so
 // build what encode_tiles_kernel needs: per tile its origin and which pattern it follows, and per
 // distinct pattern the LDS byte offset (row-XOR-swizzled raster image) of every position.
-void build_tile_tables(const std::vector<int32_t> &O, int width, ShapeTables &t)
+// raws: per pattern dy * 64 + dx of every position of a tile, for build_block_tables
+void build_tile_tables(const std::vector<int32_t> &O, int width, ShapeTables &t, std::vector<std::vector<uint16_t>> &raws)
 {
 	t.tiled = false;
 	const size_t N = O.size();
@@ -515,7 +574,7 @@ void build_tile_tables(const std::vector<int32_t> &O, int width, ShapeTables &t)
 	std::vector<uint32_t> org(nt);
 	std::vector<uint8_t> orient(nt);
 	std::vector<std::vector<uint16_t>> pats;
-	std::vector<uint16_t> cur(4096);
+	std::vector<uint16_t> cur(4096), raw(4096);
 	for (int ti = 0; ti < nt; ti++) {
 		const int32_t *k = O.data() + (size_t)ti * 4096;
 		int32_t lo = k[0];
@@ -526,6 +585,7 @@ void build_tile_tables(const std::vector<int32_t> &O, int width, ShapeTables &t)
 			const int dy = d / width, dx = d % width;
 			if (dx >= 64 || dy >= 64) return;  // not an aligned 64x64 square
 			cur[i] = (uint16_t)(dy * 128 + (((dx >> 3) ^ (dy & 7)) << 4) + (dx & 7) * 2);
+			raw[i] = (uint16_t)(dy * 64 + dx);
 		}
 		int which = -1;
 		for (size_t p = 0; p < pats.size(); p++)
@@ -533,6 +593,7 @@ void build_tile_tables(const std::vector<int32_t> &O, int width, ShapeTables &t)
 		if (which < 0) {
 			if ((int)pats.size() == TILE_MAX_ORIENT) return;
 			pats.push_back(cur);
+			raws.push_back(raw);
 			which = (int)pats.size() - 1;
 		}
 		org[ti] = (uint32_t)lo;
@@ -574,7 +635,9 @@ int get_tables(int width, int height, const ShapeTables **out)
 		ShapeTables t;
 		HIP_TRY(hipMalloc(&t.d_lut, (N ? N : 1) * sizeof(int32_t)));
 		HIP_TRY(hipMemcpy(t.d_lut, host.data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
-		build_tile_tables(host, width, t);
+		std::vector<std::vector<uint16_t>> raws;
+		build_tile_tables(host, width, t, raws);
+		if (t.tiled) HIP_TRY(build_block_tables(raws, width, t));
 		auto ins = g_ctx.luts.emplace(key, t);
 		*out = &ins.first->second;
 		return CCT_OK;
@@ -844,12 +907,13 @@ int decode_payload_locked(DecSlot &D, const uint8_t *d_payload, size_t stride, c
 		int rc0 = get_tables(width, height, &tb);
 		if (rc0) return rc0;
 		a.lut = tb->d_lut;
-		if (tb->tiled && g_ctx.use_tiles && !g_ctx.runtime_bs) {
-			a.tile_org = tb->d_org; a.tile_orient = tb->d_orient; a.patterns = tb->d_pat;
+		if (tb->tiled && tb->dec_blocks && g_ctx.use_tiles && !g_ctx.runtime_bs) {
+			a.tile_org = tb->d_org; a.tile_orient = tb->d_orient; a.blk_tab = tb->d_blk;
 			a.n_tiles = tb->n_tiles; a.n_orient = tb->n_orient;
 		}
 	}
 	a.N = N; a.NB = NB; a.images = d_images; a.status = d_status;
+	a.narrow_stores = ((uintptr_t)d_images & 7u) != 0;  // a slice is a multiple of 8 bytes: every slice starts as the first does
 	const size_t per = (size_t)n * NB, jper = (size_t)n * ((size_t)NB / 2 + 1);
 	int rc;
 	if ((rc = D.d_role.ensure(per))) return rc;
@@ -862,8 +926,10 @@ int decode_payload_locked(DecSlot &D, const uint8_t *d_payload, size_t stride, c
 	if ((rc = D.d_pcache.ensure((size_t)n * a.pcache_steps * g_ctx.wg_threads * sizeof(uint2)))) return rc;
 	a.ws_pcache = (uint2 *)D.d_pcache.p;
 	const bool run_time = bs_run_time(bs, g_ctx.runtime_bs != 0);
-	HIP_TRY(launch_decode(a, n, bs, g_ctx.wg_threads, st, run_time));
+	bool block_path = false;
+	HIP_TRY(launch_decode(a, n, bs, g_ctx.wg_threads, st, run_time, &block_path));
 	g_ctx.last_dec_path = run_time ? 1 : 0;
+	g_ctx.last_dec_block_path = block_path ? 1 : 0;
 	if (st != D.stream) {
 		// the kernel is still queued on the caller's stream when the slot is released: whatever takes the slot next runs on
 		// D.stream and must not touch d_role / d_slot / d_jord / d_pcache before this launch is through
@@ -921,7 +987,7 @@ int cct_shutdown(void)
 	if (g_gate) { (void)hipFree(g_gate); g_gate = nullptr; }
 	for (auto &kv : g_ctx.luts) {
 		ShapeTables &t = kv.second;
-		void *ptrs[] = {t.d_lut, t.d_org, t.d_orient, t.d_pat, t.d_ptab, t.d_otab, t.d_ttab, t.d_htab};
+		void *ptrs[] = {t.d_lut, t.d_org, t.d_orient, t.d_pat, t.d_blk, t.d_ptab, t.d_otab, t.d_ttab, t.d_htab};
 		for (void *p : ptrs) if (p) (void)hipFree(p);
 	}
 	for (int k = 0; k < N_DEC_SLOTS; k++) {
@@ -2301,6 +2367,7 @@ const Option OPTIONS[] = {
 		return v != 256 && v != 512 && v != 1024 ? fail(CCT_E_ARG, "wg_threads must be 256, 512 or 1024") : CCT_OK; }},
 	{"last_encode_path", &Context::last_path, nullptr, true},
 	{"last_decode_path", &Context::last_dec_path, nullptr, true},
+	{"last_decode_block_path", &Context::last_dec_block_path, nullptr, true},
 	{"last_inflate_lanes", &Context::last_inflate_lanes, nullptr, true},
 	{"debug_skip", &Context::dbg_skip, rule_any, false, true},
 	{"tuning_build", &Context::tuning_build, nullptr, true, true},

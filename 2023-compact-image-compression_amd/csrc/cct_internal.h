@@ -110,6 +110,12 @@ hipError_t launch_encode(const EncArgs &a, int n, int block_size, int threads, h
 // ---- decode kernel geometry ----------------------------------------------------------
 constexpr int DEC_SEG = 16;           // payload bytes parsed per lane per step
 constexpr int DEC_JLIST_CAP = 2048;   // jump records kept in LDS; the rest spill to HBM
+constexpr int DEC_BLK_ORDERS = 8;     // block path: distinct visiting orders of a 4x4 block that a shape may have
+// words of the block tables of a shape with n_orient tile patterns (api.cpp build_block_tables)
+constexpr size_t dec_block_words(int n_orient) { return (size_t)n_orient * 256 + DEC_BLK_ORDERS * 2 + DEC_BLK_ORDERS * 8; }
+// block path: pass B stages a step's pixel values by ordinal, 16 to a stream slot, before it places them; a slot takes 18
+// entries (9 words, an odd count: lanes that work on neighbouring slots use different LDS banks)
+constexpr int DEC_STAGE_PITCH = 18;
 
 struct DecArgs {
 	const uint8_t *payload; size_t stride; const uint32_t *sizes;
@@ -120,17 +126,18 @@ struct DecArgs {
 	uint32_t *ws_slot;        // n * NB: stream slot -> leader block | kind << 30
 	uint32_t *ws_jord;        // n * (NB/2+1) spill: jump ordinals
 	uint8_t *ws_jval;         // n * (NB/2+1) spill: jump distances
-	// traversal made of aligned 64x64 tiles (same tables as encode_tiles_kernel): position -> raster offset from LDS
-	const uint32_t *tile_org; const uint8_t *tile_orient; const uint16_t *patterns;
+	// traversal made of aligned 64x64 tiles of 4x4 blocks (tile tables as encode_tiles_kernel's, block tables from
+	// build_block_tables): block -> raster rows from LDS
+	const uint32_t *tile_org; const uint8_t *tile_orient; const uint32_t *blk_tab;
 	int n_tiles, n_orient, width;   // n_tiles == 0: use lut
 	uint32_t bs_mul;                // decode_kernel<0> only: ord / bs == __umulhi(ord, bs_mul) >> bs_shift (bs_divider)
 	// pass A leaves every lane's view of every parsing step here (pixel ordinal | entry state << 31, value before the
 	// segment) so that pass B does not repeat the workgroup scans: n * pcache_steps * threads entries
 	uint2 *ws_pcache; int pcache_steps;
 	uint16_t bs, bs_shift;          // decode_kernel<0> only (set by launch_decode): the block size and the shift of its divider
+	int narrow_stores;              // block path: `images` is not 8-byte aligned, so pixels are stored one by one
 };
-// bs, bs_shift and bs_mul fill padding: the struct keeps its size and the templated kernels their argument layout
-static_assert(sizeof(DecArgs) == 144, "DecArgs layout: the run-time block size fields must stay in padding");
+static_assert(sizeof(DecArgs) == 152, "DecArgs layout");
 
 // Division by a run-time block size d, 3 <= d <= 64, as a multiply-high and a shift: with s = floor(log2(d - 1)) and
 // m = ceil(2^(32+s) / d) < 2^32, floor(x * m / 2^(32+s)) == floor(x / d) for every x < 2^31.  (m * d = 2^(32+s) + e with
@@ -145,7 +152,8 @@ inline void bs_divider(int d, uint32_t *mul, uint32_t *shift)
 }
 
 // run_time: decode_kernel<0> (launch_decode sets a.bs, a.bs_mul, a.bs_shift) even for a power of two (see bs_run_time)
-hipError_t launch_decode(const DecArgs &a, int n, int block_size, int threads, hipStream_t s, bool run_time);
+// *block_path: the launch took decode_kernel<16, true, true>
+hipError_t launch_decode(const DecArgs &a, int n, int block_size, int threads, hipStream_t s, bool run_time, bool *block_path);
 
 // ---- device DEFLATE (zlib 1.2.11 level 9 restatement, deflate_kernels.hip) ----------------
 // BlockMeta, BlockTables, DeflateArgs, the shared constants and the workspace layout: deflate_workspace.h

@@ -11,7 +11,8 @@
 //   resolve one lane replays the ~100-700 jumps in stream order against a 64-bit window of
 //           already-claimed partner blocks -> role[b] (0 single, 1..63 pair leader, 0xFF partner);
 //           a workgroup scan over role[] then gives every 16-pixel stream slot its block;
-//   pass B  parse again, now scattering each pixel to raster position O[block*bs + t].
+//   pass B  parse again, now scattering each pixel to raster position O[block*bs + t]; where the traversal is made of
+//           4x4 blocks (block size 16, tiled shapes) the values are staged by ordinal and placed a block at a time.
 //
 // Reserved tag bytes (110xxxxx, 1111xxxx) decode as the reference decodes them: one byte, the previous pixel
 // repeats (core.py:496-520 takes no branch).  Streams a reference encoder cannot produce for which the reference
@@ -142,10 +143,16 @@ __device__ __forceinline__ Parse parse_step(const uint4 &w, uint32_t nxt, int nv
 {
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
 	const SegMasks sm = seg_masks(w, nvalid);
-	const SegStats s0 = seg_stats(w, nxt, sm, nvalid, 0);
-	const SegStats s1 = seg_stats(w, nxt, sm, nvalid, 1);
+	// the state scan needs the exit state under both entry hypotheses, which the token structure gives; the counts and the
+	// delta sum are computed once, for the entry state that the scan finds
+	auto exit_of = [&](uint32_t e) -> uint32_t {
+		if (nvalid <= 0) return e;
+		uint32_t second, fulls;
+		seg_structure(sm, e, second, fulls);
+		return (fulls >> (nvalid - 1)) & 1u;
+	};
 	// inclusive scan of state maps inside the wave (lanes without a source compose with the identity map, 2)
-	uint32_t m = s0.exit_state | (s1.exit_state << 1);
+	uint32_t m = exit_of(0) | (exit_of(1) << 1);
 	m = map_compose(m, dpp_move<DPP_ROW_SHR1>(m, 2));
 	m = map_compose(m, dpp_move<DPP_ROW_SHR2>(m, 2));
 	m = map_compose(m, dpp_move<DPP_ROW_SHR4>(m, 2));
@@ -165,7 +172,7 @@ __device__ __forceinline__ Parse parse_step(const uint4 &w, uint32_t nxt, int nv
 	}
 	Parse p;
 	p.entry = map_apply(excl, st_wave);
-	p.st = p.entry ? s1 : s0;
+	p.st = seg_stats(w, nxt, sm, nvalid, p.entry);
 	// scans of pixel count | jump count << 16 (both <= 16 per lane, <= 16384 per step) and of the delta sum
 	const uint32_t ipj = wave_incl_scan(p.st.npix | (p.st.njump << 16));
 	const uint32_t iv = wave_incl_scan((uint32_t)p.st.sdelta);
@@ -191,14 +198,15 @@ __device__ __forceinline__ Parse parse_step(const uint4 &w, uint32_t nxt, int nv
 
 // TAB_LDS: the per-block role bytes and the slot table (5 bytes per block) live in LDS instead of the HBM
 // workspace: pass B looks both up for every pixel (fits up to 24 K blocks, e.g. 512 x 512 at block size 16)
-// TILED: the traversal is made of aligned 64x64 tiles; the position -> raster map comes from the pattern tables of
-// encode_tiles_kernel staged in LDS (<= 32 KB) instead of one 4-byte HBM/L2 load per pixel.
+// TILED (block size 16): the traversal is made of aligned 64x64 tiles whose blocks are aligned 4x4 squares of the raster;
+// pass B stages the pixel values by ordinal in LDS and places whole blocks, four row stores each (see "Block path" below),
+// instead of looking up one traversal entry and storing 2 bytes per pixel.
 // BS == 0 (not TILED): the block size is a.bs (any size from 3 to 64; launch_decode picks it for the sizes that are not powers
 // of two), and a pixel ordinal is divided by it with the multiply-high and shift of bs_divider (cct_internal.h).
 template <int BS, bool TAB_LDS, bool TILED = false>
 __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 {
-	static_assert(BS != 0 || !TILED, "the tiled variant exists for block size 16 only");
+	static_assert(BS == 16 || !TILED, "the tiled variant exists for block size 16 only");
 	extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
 	__shared__ uint32_t scratch[64];
 	__shared__ uint32_t l_jord[DEC_JLIST_CAP];
@@ -228,32 +236,19 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 	auto slot_rd = [&](uint32_t i) -> uint32_t { return TAB_LDS ? l_slot[i] : g_slot[i]; };
 	auto slot_wr = [&](uint32_t i, uint32_t v) { if (TAB_LDS) l_slot[i] = v; else g_slot[i] = v; };
 	typedef __attribute__((address_space(3))) uint16_t lds_u16;
-	// position p of a tile at p + p / 16: consecutive lanes look up positions 16 apart (one block each), which would be
-	// 32 bytes = the same four banks for the whole wave; the pad entry per block spreads them over all banks
-	constexpr uint32_t PAT_STRIDE = 4096 + 256;
-	lds_u16 *l_pat = (lds_u16 *)(dyn_lds + (((size_t)NB * 5 + 15) & ~(size_t)15));   // n_orient * PAT_STRIDE
-	lds_u32 *l_torg = (lds_u32 *)(l_pat + (TILED ? (size_t)a.n_orient * PAT_STRIDE : 0)); // n_tiles
-	lds_u8 *l_tori = (lds_u8 *)(l_torg + (TILED ? a.n_tiles : 0));                   // n_tiles
+	// TILED: block tables (dec_block_words), tile origins, the staging array of pass B, tile orientations
+	lds_u32 *l_blk = (lds_u32 *)(dyn_lds + (((size_t)NB * 5 + 15) & ~(size_t)15));   // n_orient * 256: block offset | order << 16
+	lds_u32 *l_inv = l_blk + (TILED ? (size_t)a.n_orient * 256 : 0);                 // per order: the step that visits cell dy * 4 + dx
+	lds_u16 *l_off = (lds_u16 *)(l_inv + DEC_BLK_ORDERS * 2);                        // per order: raster offset of step t
+	lds_u32 *l_torg = (lds_u32 *)(l_off + DEC_BLK_ORDERS * 16);                      // n_tiles
+	lds_u16 *l_stage = (lds_u16 *)(l_torg + (TILED ? a.n_tiles : 0));                // (T + 1) * DEC_STAGE_PITCH
+	lds_u8 *l_tori = (lds_u8 *)(l_stage + (TILED ? (size_t)(T + 1) * DEC_STAGE_PITCH : 0)); // n_tiles
 	if (TILED) {
-		// the encoder's pattern entries are swizzled LDS byte offsets (dy*128 + ((dx>>3 ^ dy&7) << 4) + (dx&7)*2); pass B wants
-		// the raster offset inside the tile, dy * width + dx (< 65536: launch_decode takes this path for widths <= 1024 only)
-		for (int i = tid; i < a.n_orient * 4096; i += T) {
-			const uint32_t pv = a.patterns[i];
-			const uint32_t dy = pv >> 7, dx = ((((pv >> 4) & 7u) ^ (dy & 7u)) << 3) | ((pv & 15u) >> 1);
-			const uint32_t o = (uint32_t)i >> 12, p = (uint32_t)i & 4095u;
-			l_pat[o * PAT_STRIDE + p + (p >> 4)] = (uint16_t)(dy * (uint32_t)a.width + dx);
-		}
+		for (int i = tid; i < (int)dec_block_words(a.n_orient); i += T) l_blk[i] = a.blk_tab[i];
 		for (int i = tid; i < a.n_tiles; i += T) { l_torg[i] = a.tile_org[i]; l_tori[i] = a.tile_orient[i]; }
 	}
 	// raster offset of traversal position pos
-	auto raster_of = [&](uint32_t pos) -> uint32_t {
-		if (TILED) {
-			const uint32_t tile = pos >> 12;
-			const uint32_t p = pos & 4095u;
-			return l_torg[tile] + l_pat[(uint32_t)l_tori[tile] * PAT_STRIDE + p + (p >> 4)];
-		}
-		return lut ? (uint32_t)lut[pos] : pos;
-	};
+	auto raster_of = [&](uint32_t pos) -> uint32_t { return lut ? (uint32_t)lut[pos] : pos; };
 	const size_t jcap = (size_t)NB / 2 + 1;
 	uint32_t *g_jord = a.ws_jord + (size_t)s * jcap;
 	uint8_t *g_jval = a.ws_jval + (size_t)s * jcap;
@@ -397,11 +392,12 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 
 	// ------------------------------------------------------------------ pass B: pixels
 	if (!(s_status & CCT_ST_STREAM)) {
-		// every lane re-reads its segments and what pass A's scans told it about them: no barrier in this pass; the loads
-		// of the next step are issued before this step's pixels are written
+		// every lane re-reads its segments and what pass A's scans told it about them: no scan in this pass (and no barrier but
+		// the block path's two per step); the loads of the next step are issued before this step's pixels are written
 		uint4 w_n; uint32_t nxt_n;
 		load_seg((uint32_t)tid * DEC_SEG, w_n, nxt_n);
 		uint2 pc_n = pcache[tid];  // (slot 0 of the step cache exists even for an empty payload)
+		uint32_t sbase = 0;        // block path: pixel ordinal of the first staged value
 #ifdef CCT_DEC_PROF
 		long long tb[4] = {0, 0, 0, 0}, tq = clock64();
 #define DECB(j) do { const long long t_ = clock64(); tb[j] += t_ - tq; tq = t_; } while (0)
@@ -440,26 +436,85 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 			// (two jump bytes in a row carry the same pixel ordinal and are refused by the replay, sslot < slots_done, across segments and
 			// steps too; a test on the masks here would also see the jump bytes behind pixel N - 1 of a lane that has no pixel left to clip)
 			if (nvalid > 0 && ((fulls >> (nvalid - 1)) & 1u) && seg_start + (uint32_t)nvalid >= Lr) flags |= CCT_ST_STREAM;  // second byte missing
+			if constexpr (TILED) {
+				// Block path.  Where a pixel goes is a property of its block, so the lane that decodes a token does not look it up:
+				// phase 1 stages the values by pixel ordinal (16 to a stream slot, DEC_STAGE_PITCH entries apart), and in phase 2 a
+				// lane takes a whole slot and writes its block as four rows of four pixels.  The array starts at pixel `sbase`, the
+				// step's first ordinal rounded down to a slot border; the values of a slot that the step leaves incomplete are moved
+				// to the front for the next step, which places the slot.  A step has at most T * 16 pixel tokens, so it completes at
+				// most T slots.  (N is a multiple of 16 and pass B runs only on streams with N pixels: the last step ends on a border.)
+				const uint32_t p_next = min(pcache[(size_t)min(k + 1, nsteps - 1) * T].x & 0x7FFFFFFFu, (uint32_t)N);
+				const uint32_t p_end = k + 1 < nsteps ? p_next : (uint32_t)N;  // first ordinal behind this step
+				const uint32_t ws[5] = {w.x, w.y, w.z, w.w, nxt};
+				uint32_t q = ord - sbase;
+#pragma unroll
+				for (int i = 0; i < 16; i++) {
+					if (!((pix >> i) & 1u)) continue;
+					const uint32_t c = (ws[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+					const uint32_t c1 = (ws[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xFFu;
+					// (reserved tags 110xxxxx / 1111xxxx: no branch of core.py:500-516 is taken, the previous pixel repeats)
+					val += ((sm.S >> i) & 1u) ? tok_delta_short(c) : ((fulls >> i) & 1u) ? tok_delta_full(c, c1) : 0;
+					if ((uint32_t)val > 65535u) flags |= CCT_ST_OVERFLOW;  // to_bytes(2), core.py:506 (negative or too large)
+					l_stage[q + ((q >> 4) << 1)] = (uint16_t)val;
+					q++;
+				}
+				DECB(1);
+				__syncthreads();
+				const uint32_t n_sl = (p_end - sbase) >> 4, n_tail = (p_end - sbase) & 15u;
+				// block -> raster index of its top-left pixel, and its visiting order
+				auto block_at = [&](uint32_t blk, uint32_t &dst, uint32_t &order) {
+					const uint32_t tile = blk >> 8;
+					const uint32_t e = l_blk[(uint32_t)l_tori[tile] * 256u + (blk & 255u)];
+					dst = l_torg[tile] + (e & 0xFFFFu); order = e >> 16;
+				};
+				for (uint32_t i = (uint32_t)tid; i < n_sl; i += (uint32_t)T) {
+					const uint32_t ent = l_slot[(sbase >> 4) + i];
+					const uint32_t blk0 = ent & 0x3FFFFFFFu, kind = ent >> 30;
+					lds_u16 *sv = l_stage + i * DEC_STAGE_PITCH;
+					uint32_t dst0, o0;
+					block_at(blk0, dst0, o0);
+					if (kind == 0 && !a.narrow_stores) {
+						// a single block: cell (dy, dx) holds the value of step inv[dy * 4 + dx]; a row is one 8-byte store (tile origins
+						// and block offsets are multiples of 4 pixels, the width of 8)
+						const uint32_t inv[2] = {l_inv[o0 * 2], l_inv[o0 * 2 + 1]};
+#pragma unroll
+						for (int r = 0; r < 4; r++) {
+							const uint32_t n4 = inv[r >> 1] >> (16 * (r & 1));
+							const uint32_t v0 = sv[n4 & 15u], v1 = sv[(n4 >> 4) & 15u], v2 = sv[(n4 >> 8) & 15u], v3 = sv[(n4 >> 12) & 15u];
+							*reinterpret_cast<uint2 *>(out + dst0 + (uint32_t)r * (uint32_t)a.width) = make_uint2(v0 | (v1 << 16), v2 | (v3 << 16));
+						}
+					} else {
+						// a meshed pair shares two slots: the 32 values alternate between leader and partner, this slot holds steps
+						// (kind - 1) * 8 .. + 7 of both blocks.  Pairs are a few per cent of the slots: pixel stores
+						uint32_t dst1 = dst0, o1 = o0, step0 = 0;
+						if (kind) { block_at(blk0 + (uint32_t)l_role[blk0], dst1, o1); step0 = (kind - 1u) * 8u; }
+						lds_u16 *f0 = l_off + o0 * 16u + step0, *f1 = l_off + o1 * 16u + step0;
+#pragma unroll
+						for (int t = 0; t < 16; t++) {
+							const uint32_t pair_at = (t & 1) ? dst1 + f1[t >> 1] : dst0 + f0[t >> 1];
+							out[kind ? pair_at : dst0 + f0[t]] = sv[t];
+						}
+					}
+				}
+				uint16_t tail_v = 0;
+				if ((uint32_t)tid < n_tail) tail_v = l_stage[n_sl * DEC_STAGE_PITCH + (uint32_t)tid];
+				__syncthreads();  // phase 1 of the next step writes behind the tail
+				if ((uint32_t)tid < n_tail) l_stage[tid] = tail_v;
+				sbase = p_end & ~15u;
 			// a wave-uniform choice for BS == 0: a lane's 16 pixels span at most two slots for every bs >= 16, for no bs < 16
-			if (BS ? BS >= 16 : bs >= 16) {
-				// A lane's <= 16 pixels fall into at most two stream slots: both slots' entry, partner and tile data are fetched
+			} else if (BS ? BS >= 16 : bs >= 16) {
+				// A lane's <= 16 pixels fall into at most two stream slots: both slots' entry and partner are fetched
 				// before the loop.  The loop itself runs over the 16 byte positions with a compile-time index (a byte is a bit-field
 				// extract, not a select chain) and skips the positions that open no pixel token.
-				// per slot and parity (leader / partner of a meshed pair): first traversal position of the block, the tile's raster
-				// origin and the index of the block's first pattern entry (the table is padded by one entry per 16 positions) -- a
-				// pixel then costs one select of each instead of rebuilding them from block numbers
-				struct SlotInfo { uint32_t kind, pos0, pos1, org0, org1, idx0, idx1; };
+				// per slot and parity (leader / partner of a meshed pair): first traversal position of the block -- a pixel then
+				// costs one select instead of rebuilding it from block numbers
+				struct SlotInfo { uint32_t kind, pos0, pos1; };
 				auto slot_info = [&](uint32_t sl) {
-					SlotInfo si{0, 0, 0, 0, 0, 0, 0};
+					SlotInfo si{0, 0, 0};
 					const uint32_t ent = slot_rd(min(sl, (uint32_t)NB - 1u));
 					const uint32_t blk0 = ent & 0x3FFFFFFFu; si.kind = ent >> 30;
 					const uint32_t blk1 = si.kind ? blk0 + role_rd(blk0) : blk0;
 					si.pos0 = blk0 * bs; si.pos1 = blk1 * bs;
-					if (TILED) {
-						const uint32_t t0 = si.pos0 >> 12, t1 = si.pos1 >> 12, b0 = si.pos0 & 4095u, b1 = si.pos1 & 4095u;
-						si.org0 = l_torg[t0]; si.idx0 = (uint32_t)l_tori[t0] * PAT_STRIDE + b0 + (b0 >> 4);
-						si.org1 = l_torg[t1]; si.idx1 = (uint32_t)l_tori[t1] * PAT_STRIDE + b1 + (b1 >> 4);
-					}
 					return si;
 				};
 				const uint32_t slA = bdiv(ord);
@@ -479,19 +534,12 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 					const uint32_t kind = inA ? A.kind : B.kind;
 					uint32_t odd = 0, off = t;
 					if (kind) { const uint32_t mm = (kind - 1u) * bs + t; odd = mm & 1u; off = mm >> 1; }  // index inside the 2*bs interleave
-					uint32_t ras;
-					if (TILED) {
-						const uint32_t org = inA ? (odd ? A.org1 : A.org0) : (odd ? B.org1 : B.org0);
-						const uint32_t idx = inA ? (odd ? A.idx1 : A.idx0) : (odd ? B.idx1 : B.idx0);
-						ras = org + l_pat[idx + off + (BS > 16 ? off >> 4 : 0u)];  // (off < BS: inside the block)
-					} else ras = raster_of((inA ? (odd ? A.pos1 : A.pos0) : (odd ? B.pos1 : B.pos0)) + off);
-					out[ras] = (uint16_t)val;
+					out[raster_of((inA ? (odd ? A.pos1 : A.pos0) : (odd ? B.pos1 : B.pos0)) + off)] = (uint16_t)val;
 					ord++;
 				}
 			} else {
-				// a lane's pixels fall into at most two stream slots: slot entry, partner and tile data are fetched once per slot
+				// slot entry and partner are fetched once per slot
 				uint32_t cur_sl = 0xFFFFFFFFu, kind = 0, blk0 = 0, blk1 = 0;
-				uint32_t org0 = 0, org1 = 0, pat0 = 0, pat1 = 0;
 				for (uint32_t pm = pix; pm; pm &= pm - 1) {
 					const int i = __ffs((int)pm) - 1;
 					const uint32_t c = seg_byte(w, nxt, i);
@@ -505,25 +553,14 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 						const uint32_t ent = slot_rd(sl);
 						blk0 = ent & 0x3FFFFFFFu; kind = ent >> 30;
 						blk1 = kind ? blk0 + role_rd(blk0) : blk0;
-						if (TILED) {
-							const uint32_t t0 = (blk0 * bs) >> 12, t1 = (blk1 * bs) >> 12;
-							org0 = l_torg[t0]; pat0 = (uint32_t)l_tori[t0] * PAT_STRIDE;
-							org1 = l_torg[t1]; pat1 = (uint32_t)l_tori[t1] * PAT_STRIDE;
-						}
 					}
-					uint32_t pos, odd = 0;
+					uint32_t pos;
 					if (kind == 0) pos = blk0 * bs + t;
 					else {
 						const uint32_t mm = (kind - 1u) * bs + t;  // index inside the 2*bs interleave
-						odd = mm & 1u;
-						pos = (odd ? blk1 : blk0) * bs + (mm >> 1);
+						pos = ((mm & 1u) ? blk1 : blk0) * bs + (mm >> 1);
 					}
-					uint32_t ras;
-					if (TILED) {
-						const uint32_t p = pos & 4095u;
-						ras = (odd ? org1 : org0) + l_pat[(odd ? pat1 : pat0) + p + (p >> 4)];
-					} else ras = raster_of(pos);
-					out[ras] = (uint16_t)val;
+					out[raster_of(pos)] = (uint16_t)val;
 					ord++;
 				}
 			}
@@ -531,7 +568,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 			if (flags) atomicOr(&s_status, flags);
 		}
 #ifdef CCT_DEC_PROF
-		if (s == 0 && tid == 0) printf("[decode prof] pass B wave 0: masks %lld slots %lld pixels %lld\n", tb[0], tb[1], tb[2]);
+		if (s == 0 && tid == 0) printf("[decode prof] pass B wave 0: masks %lld %s %lld %s %lld\n", tb[0], TILED ? "stage" : "slots", tb[1], TILED ? "place" : "pixels", tb[2]);
 #endif
 	}
 	__syncthreads();
@@ -548,8 +585,9 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecArgs a)
 
 }  // namespace
 
-hipError_t launch_decode(const DecArgs &args, int n, int block_size, int threads, hipStream_t s, bool run_time)
+hipError_t launch_decode(const DecArgs &args, int n, int block_size, int threads, hipStream_t s, bool run_time, bool *block_path)
 {
+	*block_path = false;
 	if (block_size < 3 || block_size > 64) return hipErrorInvalidValue;
 	run_time = bs_run_time(block_size, run_time);
 	DecArgs a = args;
@@ -560,7 +598,8 @@ hipError_t launch_decode(const DecArgs &args, int n, int block_size, int threads
 	}
 	const size_t tab_bytes = (((size_t)a.NB * 5 + 15) & ~(size_t)15) + 16;
 	const bool tab_lds = tab_bytes <= 100 * 1024;
-	const size_t tile_bytes = (size_t)a.n_orient * (4096 + 256) * 2 + (size_t)a.n_tiles * 5 + 16;
+	// block tables, tile origins and orientations, the staging array of pass B
+	const size_t tile_bytes = dec_block_words(a.n_orient) * 4 + (size_t)a.n_tiles * 5 + (size_t)(threads + 1) * DEC_STAGE_PITCH * 2 + 16;
 	const bool tiled = !run_time && tab_lds && block_size == 16 && a.lut && a.n_tiles > 0 && tab_bytes + tile_bytes <= 144 * 1024 && a.width <= 1024;
 	void (*k)(DecArgs) = nullptr;
 	switch (run_time ? 0 : block_size) {
@@ -578,6 +617,7 @@ hipError_t launch_decode(const DecArgs &args, int n, int block_size, int threads
 		if (e != hipSuccess) return e;
 	}
 	hipLaunchKernelGGL(k, dim3(n), dim3(threads), lds, s, a);
+	*block_path = tiled;
 	return hipGetLastError();
 }
 
